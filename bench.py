@@ -11,13 +11,21 @@ N > 1 (launched by torch.distributed.run, one rank per GPU): the SAME graph and 
 minibatch's rows sharded over the ranks -- strong scaling.  Default exchange: the engine's push over
 xGMI (f2v_train_sharded: new rows stored straight into the reading peers' HBM, device-side flag
 barrier; torch.distributed only carries the IPC handles); if it cannot be set up on this machine the
-run falls back to an RCCL all-gather per minibatch and says so.  After the timed region every rank
-checks its replica bit for bit against a single-GPU run of the same epochs.
+run falls back to an RCCL all-gather per minibatch and says so.  With --full, after the timed region every
+rank checks its replica bit for bit against a single-GPU run of the same epochs.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` and `cpu_baseline` (the genuine
-reference binary oracle/_ref timed on this box's host cores on a bounded sample of the same workload).
+Prints ONE JSON line on rank 0: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (milliseconds of one
+timed step) and the configuration.  A plain run does only what that line needs: set-up, settling and warmup, the K timed
+steps, --dump-outputs DIR, the line.  --full adds everything else: `roofline` (with its profiler passes and on-box ceilings),
+the oracle check of one more minibatch, other batch sizes, `extra.sustained`, option 7, BASELINE configs 0, 1, 3 and 4,
+`cpu_baseline` (the genuine reference binary oracle/_ref timed on this box's host cores on a bounded sample of the same
+workload) and, N > 1, the bit-for-bit replica check.
 
-roofline, bound "hbm": `achieved` = COMPULSORY bytes per launch of the dominant kernel (distinct embedding rows read +
+--dump-outputs DIR: what the timed steps left in the embedding matrix, the rows of a fixed seeded sample of at most 32 MB
+(every row where the whole matrix fits), as DIR/embeddings_sample.npy (float32) and their ids as DIR/embeddings_sample_rows.npy
+(float64).  Settling runs at lr = 0 and restarts the rand() stream, so the same arguments give the same timed computation.
+
+roofline (--full), bound "hbm": `achieved` = COMPULSORY bytes per launch of the dominant kernel (distinct embedding rows read +
 rows written + neighbour ids + work items: what must cross HBM even if every re-read inside the launch hit a cache,
 counted on the host by the engine) / that kernel's average launch time (HIP events on the engine's stream around the
 epoch loop); `frac` = achieved / 8 TB/s and cannot exceed 1.  The SURVEY 8d figure (every neighbour row charged to HBM,
@@ -25,7 +33,7 @@ epoch loop); `frac` = achieved / 8 TB/s and cannot exceed 1.  The SURVEY 8d figu
 rows are cache hits and it passes the HBM peak.  `traffic` = bytes that left the XCDs' L2s per launch (PMC passes of
 tools/profile_traffic.sh, committed under profiles/): HBM + Infinity Cache together; rocprofv3 exposes no counter on
 the memory side of the Infinity Cache on this part, so HBM bytes lie between `compulsory` ... `traffic`.
-After the timed region (N = 1) one more minibatch is checked on sampled rows against the CPU oracle (`config.verified_rows`).
+With --full, after the timed region (N = 1) one more minibatch is checked on sampled rows against the CPU oracle (`config.verified_rows`).
 """
 import argparse
 import json
@@ -195,6 +203,24 @@ def verify_rows(F, eng, rowptr, colids, args, n_rows=32):
     return int(len(rows))
 
 
+DUMP_SAMPLE_BYTES = 32 << 20
+
+
+def dump_outputs(out_dir, X):
+    """--dump-outputs: the N x D matrix X the timed steps left, as the rows of a fixed seeded sample of at most DUMP_SAMPLE_BYTES
+    (every row where the whole matrix fits) -> DIR/embeddings_sample.npy (float32) and DIR/embeddings_sample_rows.npy (their ids,
+    float64).  -> list of the paths written."""
+    n, dim = X.shape
+    k = min(n, max(1, DUMP_SAMPLE_BYTES // (4 * dim)))
+    rows = np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    paths = []
+    for name, a in (("embeddings_sample", np.ascontiguousarray(X[rows], dtype=np.float32)), ("embeddings_sample_rows", rows.astype(np.float64))):
+        paths.append(os.path.join(out_dir, name + ".npy"))
+        np.save(paths[-1], a)
+    return paths
+
+
 def kernel_name(args, pushing, form, wide_width=0, wide_early=0):
     """The step kernel the last f2v_train of this shape launched: `form` is the engine's own answer ("last_train_form": 0 one
     launch per minibatch, 1 chained, 2 chained in the wide form) -- the launch rules live in f2v_engine.hip, not here."""
@@ -312,6 +338,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything the headline does not need: roofline (--live-pmc, --no-ceilings), --verify-rows, "
+                         "--extra-batches / --dist-extra-batches, --sustained-s, --option7, --cora, --config4, --config5-scale, the CPU baseline "
+                         "(--no-cpu-baseline) and, N > 1, the replica check (--no-verify); those options act only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed seeded sample of the embedding rows they computed to DIR as .npy files")
     ap.add_argument("--scale", type=int, default=20, help="RMAT scale (2^scale vertices, edge factor 16)")
     ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--batch", type=int, default=65536)
@@ -476,9 +508,10 @@ def main():
             for kv in args.param:
                 k, v = kv.split("=")
                 self.eng.set_param(k, int(v))
-            self.eng.set_param("count_compulsory", 1)
+            if args.full:
+                self.eng.set_param("count_compulsory", 1)  # (roofline: O(nnz) more per new launch plan)
             self.state = {"exchange": exchange, "comm": None, "note": note_text}
-            self.schedule = []  # every (epochs, batch) trained so far: the verification replays it on one engine
+            self.schedule = []  # every (epochs, batch, chunk, lr) trained and every srand(1) so far: the verification replays it on one engine
             self.reset()
 
         def reset(self):
@@ -514,17 +547,17 @@ def main():
             st["comm"] = comm
             return comm
 
-        def run_epochs(self, k, batch):
+        def run_epochs(self, k, batch, lr=0.02):
             """-> per-rank statistics of these k epochs (launches, bytes, device seconds where known)."""
             eng = self.eng
             if not use_dist:
-                eng.train(self.option, k, batch, 5, 0.02, 0)
-                self.schedule.append((k, batch, eng.get_param("hub_chunk")))
+                eng.train(self.option, k, batch, 5, lr, 0)
+                self.schedule.append((k, batch, eng.get_param("hub_chunk"), lr))
                 return eng.stats()
             s0 = eng.stats()
             comm = self.make_comm()
-            fdist.ShardedTrainer(eng, rank, world, comm, exchange_when_single=True).train(self.option, k, batch, 5, 0.02, 0)
-            self.schedule.append((k, batch, eng.get_param("hub_chunk")))  # the chunk this call ran with: part of the summation order
+            fdist.ShardedTrainer(eng, rank, world, comm, exchange_when_single=True).train(self.option, k, batch, 5, lr, 0)
+            self.schedule.append((k, batch, eng.get_param("hub_chunk"), lr))  # the chunk this call ran with: part of the summation order
             s1 = eng.stats()
             if self.state["exchange"] == "push":
                 st = dict(s1)  # f2v_train_sharded restarts the statistics like f2v_train
@@ -534,16 +567,20 @@ def main():
             return st
 
         def settle(self, batch):
-            """Same workload, untimed, until the device has been under steady load for --settle-ms."""
+            """Same workload, untimed, until the device has been under steady load for --settle-ms.  At lr = 0, which leaves every
+            row as it was (x + 0 * f; a zero may lose its sign), and the rand() stream starts again from srand(1) behind it: what
+            follows computes the same whatever number of epochs the settling took."""
             if args.settle_ms <= 0:
                 return 0
-            self.run_epochs(2, batch)  # launch plans are built here, on the host: not load yet
+            self.run_epochs(2, batch, lr=0.0)  # launch plans are built here, on the host: not load yet
             self.eng.synchronize()
             done, t0 = 2, time.perf_counter()
             while max_over_ranks((time.perf_counter() - t0) * 1e3) < args.settle_ms and done < 1000:
-                self.run_epochs(4, batch)
+                self.run_epochs(4, batch, lr=0.0)
                 self.eng.synchronize()
                 done += 4
+            self.eng.srand(1)
+            self.schedule.append("srand")
             return done
 
         def timed(self, k, w, batch):
@@ -588,10 +625,14 @@ def main():
                     ref.set_param(pk, int(pv))
             ref.srand(1)
             ref.init_embeddings(self.init_kind)
-            for i, (k, b, chunk) in enumerate(self.schedule):
+            for i, call in enumerate(self.schedule):
+                if call == "srand":
+                    ref.srand(1)
+                    continue
+                k, b, chunk, lr = call
                 try:
                     ref.set_param("hub_chunk", chunk)  # the chunk is part of the summation order (a sharded run picks it per slice)
-                    ref.train(self.option, k, b, 5, 0.02, 0)
+                    ref.train(self.option, k, b, 5, lr, 0)
                 except Exception:
                     note(rank, "single-GPU replay failed in call %d of %d (%d epochs at batch %d)" % (i, len(self.schedule), k, b))
                     raise
@@ -619,9 +660,9 @@ def main():
             # bits, but not the launch forms this line is about
             failed.append("a launch of the timed region was lost and recovered from (option %d, batch %d): its time is the slow launch forms'" % (sess.option, batch))
         verified = None
-        if use_dist and not args.no_verify:
+        if use_dist and args.full and not args.no_verify:
             verified = sess.verify_replica()
-            note(rank, "replica compared with a single-GPU run of the same %d epochs: %s" % (sum(e[0] for e in sess.schedule), "identical" if verified else "DIFFERENT"))
+            note(rank, "replica compared with a single-GPU run of the same %d epochs: %s" % (sum(e[0] for e in sess.schedule if e != "srand"), "identical" if verified else "DIFFERENT"))
             if not verified:
                 failed.append("%s exchange: replica differs from the single-GPU run (option %d, batch %d, n=%d)" % (sess.state["exchange"], sess.option, batch, sess.n))
                 if sess.state["exchange"] == "push":
@@ -659,7 +700,7 @@ def main():
         "config": {"workload": "RMAT scale-%d edge-factor 16 (n=%d, nnz=%d directed CSR nonzeros), option %d, D=%d, ns=5, lr=0.02, batch=%d; step = 1 epoch"
                    % (args.scale, n, nnz, args.option, args.dim, args.batch),
                    "batch": args.batch, "hub_chunk": eng.get_param("hub_chunk"),
-                   "settle": "%d untimed epochs of the same workload (>= %g ms) before the %d warmup steps" % (main_settle, args.settle_ms, args.warmup),
+                   "settle": "%d untimed epochs of the same workload at lr = 0 (>= %g ms), then srand(1), before the %d warmup steps" % (main_settle, args.settle_ms, args.warmup),
                    "parallelism": "1 GPU" if not use_dist else "minibatch rows sharded over %d GPUs, replicated graph+matrix, %s" % (world, {
                        "push": "new rows pushed over xGMI into the HBM of the peers that read them (HIP kernel + device-side flag barrier)",
                        "allgather": "%s all-gather of the new rows" % ("RCCL" if args.dist_backend == "nccl" else "gloo (host-bounce self-test)"),
@@ -682,6 +723,24 @@ def main():
             res["config"]["push_fused"] = eng.get_param("push_fused")
             ps = eng.push_stats()
             res["config"]["rows_pushed_over_allgather_rows"] = ps["rows_pushed"] / max(ps["rows_allgather"], 1)
+
+    def finish():
+        if failed:
+            res["failed"] = True
+            res["failures"] = failed
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(res), file=real_stdout, flush=True)
+        if failed:
+            sys.exit(3)
+
+    if args.dump_outputs and rank == 0:  # (N > 1: rank 0's replica)
+        note(rank, "outputs of the timed steps written: %s" % ", ".join(dump_outputs(args.dump_outputs, eng.get_embeddings())))
+    if not args.full:
+        sess.close()
+        return finish()
     if not use_dist and args.verify_rows > 0:
         # (before the ceilings below: the first launch behind their 4-GiB allocation and release took 19-28 ms under rocprofv3 and
         # lifted the kernel's profiled average; the figures of the timed region come from `st`, taken above)
@@ -800,7 +859,7 @@ def main():
         wall = time.perf_counter() - t0
         marks = eng.train_marks()
         eng.set_param("epoch_marks", 0)
-        sess.schedule.append((iters, args.batch, eng.get_param("hub_chunk")))
+        sess.schedule.append((iters, args.batch, eng.get_param("hub_chunk"), 0.02))
         dev = eng.stats()["device_seconds"]
         rates = []
         if len(marks) >= 2:
@@ -885,6 +944,8 @@ def main():
                     t_ref = ref_seconds(1200) - ref_seconds(0)
                 extra["config0_cora_D16"]["reference_cpu_1_thread_seconds"] = t_ref
                 extra["config0_cora_D16"]["reference_cpu_1_thread_edges_per_s"] = len(cci) * 1200 / t_ref
+            else:
+                extra["config0_cora_D16"]["reference_cpu_1_thread_seconds"] = "not measured: oracle/_ref was not built (oracle/build_ref.sh needs the reference's sources)"
         except Exception as ex:
             extra["config0_cora_D16"]["reference_cpu_1_thread_seconds"] = "failed: %r" % (ex,)
     def load_orkut_like():
@@ -975,16 +1036,7 @@ def main():
             res["cpu_baseline"] = cpu_baseline(args, extra.get("option7") if args.cpu_scale == args.scale else None)
         except Exception as ex:  # the baseline is reported, never required for the GPU number
             res["cpu_baseline"] = {"value": None, "unit": "edges/s", "cores": os.cpu_count(), "kind": "reference", "sample": "failed: %r" % (ex,)}
-    if failed:
-        res["failed"] = True
-        res["failures"] = failed
-    if use_dist:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        print(json.dumps(res), file=real_stdout, flush=True)
-    if failed:
-        sys.exit(3)
+    finish()
 
 
 if __name__ == "__main__":

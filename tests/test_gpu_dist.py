@@ -362,7 +362,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--scale", "15", "--batch", "8192",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--dist-backend", "gloo", "--scale", "15", "--batch", "8192",
                         "--steps", "2", "--warmup", "1", "--settle-ms", "0", "--config5-scale", "0", "--config4", "0", "--dist-extra-batches", ""],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]

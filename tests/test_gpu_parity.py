@@ -1273,11 +1273,11 @@ def test_two_ranks_ipc_preflight_children(tmp_path):
 
 
 def test_bench_contract_on_a_small_graph(tmp_path):
-    """bench.py end to end on a small RMAT graph: ONE JSON line on stdout carrying the contract's keys, a roofline fraction that
+    """bench.py --full end to end on a small RMAT graph: ONE JSON line on stdout carrying the contract's keys, a roofline fraction that
     cannot exceed 1, the in-run oracle check, the chained small batches and the config-5 leg (at a small scale here)."""
     import json
     import sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scale", "15", "--batch", "8192", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--scale", "15", "--batch", "8192", "--steps", "3", "--warmup", "1",
                         "--no-cpu-baseline", "--extra-batches", "384,2048", "--config5-scale", "16", "--config5-batch", "16384", "--config4", "0",
                         "--settle-ms", "5", "--sustained-s", "0.2"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -1307,3 +1307,47 @@ def test_bench_contract_on_a_small_graph(tmp_path):
         assert c["epochs10_bit_identical_to_oracle"] and c["epochs10_max_abs_vs_reference_output"] < 3e-5 and 0 < c["seconds_device"] < 5
         assert c["launch_form"] == "chained, wide form"   # (D = 16 included: 64-byte rows, minibatches end on 128-byte lines)
     assert "reference_cpu_1_thread_seconds" in res["extra"]["config0_cora_D16"]
+    if O.ref_binary(False) is not None:  # oracle/_ref is built where the reference's sources are present
+        assert res["extra"]["config0_cora_D16"]["reference_cpu_1_thread_seconds"] > 0
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_what_they_computed(F, tmp_path):
+    """bench.py without --full: the headline line only (no roofline, extras or CPU baseline) over exactly --steps timed steps, and
+    --dump-outputs writes the rows the timed steps left -- the same bits in two runs whose settling took different numbers of
+    epochs, and the same as one engine's warmup + timed epochs from srand(1) on the initial matrix."""
+    import json
+    import sys
+    from force2vec_amd.graph import rmat_csr
+    steps, warmup, batch = 4, 2, 8192
+    rowptr, colids = rmat_csr(15, 16, 1)  # bench.py's graph at --scale 15
+    dumps = []
+    for settle_ms in ("5", "60"):
+        d = str(tmp_path / ("settle_" + settle_ms))
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scale", "15", "--batch", str(batch), "--steps", str(steps),
+                            "--warmup", str(warmup), "--settle-ms", settle_ms, "--dump-outputs", d], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout
+        res = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in res, key
+        assert res["steps"] == steps and res["warmup"] == warmup and res["unit"] == "edges/s" and res["dtype"] == "f32" and "failed" not in res
+        assert abs(res["value"] * res["ms_per_step"] * 1e-3 - len(colids)) <= 1e-9 * len(colids)  # edges/s = nnz per timed step
+        assert not {"roofline", "extra", "cpu_baseline"} & set(res) and "verified_rows" not in res["config"]
+        names = sorted(os.listdir(d))
+        assert names == ["embeddings_sample.npy", "embeddings_sample_rows.npy"], names
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in names) <= 64 << 20
+        dumps.append((np.load(os.path.join(d, "embeddings_sample.npy")), np.load(os.path.join(d, "embeddings_sample_rows.npy"))))
+    (x1, r1), (x2, r2) = dumps
+    assert x1.dtype == np.float32 and r1.dtype == np.float64 and x1.shape == (len(r1), 128)
+    assert np.array_equal(r1, r2) and np.array_equal(x1, x2)
+    assert len(r1) == len(rowptr) - 1  # 2^15 rows of 512 bytes: the whole matrix
+    eng = F.Engine(rowptr, colids, 128)
+    eng.srand(1)
+    eng.init_embeddings(F._lib.INIT_SYMMETRIC)
+    eng.srand(1)
+    eng.train(5, warmup, batch, 5, 0.02, 0)
+    eng.train(5, steps, batch, 5, 0.02, 0)
+    want = eng.get_embeddings()[r1.astype(np.int64)]
+    eng.close()
+    assert np.array_equal(x1, want)

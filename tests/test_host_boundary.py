@@ -430,6 +430,26 @@ def test_bench_self_launch_propagates_failure():
     assert "torch.distributed.run" in r.stderr
 
 
+def test_bench_dump_outputs_is_a_fixed_sample_within_64_mb(tmp_path):
+    """bench.py --dump-outputs: a matrix that fits is written whole; a larger one as the rows of a fixed seeded sample (the same
+    rows in every run), float32 rows and float64 ids, 64 MB at most in all."""
+    import bench
+    small = np.arange(300 * 8, dtype=np.float32).reshape(300, 8)
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    assert np.array_equal(np.load(tmp_path / "small" / "embeddings_sample.npy"), small)
+    assert np.array_equal(np.load(tmp_path / "small" / "embeddings_sample_rows.npy"), np.arange(300.0))
+    big = np.broadcast_to(np.arange(1 << 18, dtype=np.float32)[:, None], (1 << 18, 256))  # 256 MB
+    picks = []
+    for name in ("a", "b"):
+        paths = bench.dump_outputs(str(tmp_path / name), big)
+        assert sum(os.path.getsize(p) for p in paths) <= 64 << 20
+        x, rows = np.load(paths[0]), np.load(paths[1])
+        assert x.dtype == np.float32 and rows.dtype == np.float64 and x.shape == (len(rows), 256) and len(rows) == (32 << 20) // (4 * 256)
+        assert np.all(np.diff(rows) > 0) and np.array_equal(x, big[rows.astype(np.int64)])
+        picks.append(rows)
+    assert np.array_equal(picks[0], picks[1])
+
+
 def _walk_graphs():
     """(name, rowptr, colids): real, power-law, and graphs made to defeat the walk generator's predictions"""
     from force2vec_amd.graph import rmat_csr

@@ -15,7 +15,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 # every engine's stream needs a hardware queue of its own: streams multiplexed onto one queue would put one engine's step
 # kernels BEHIND another's spinning barrier kernel (the barrier could then only time out)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+# -- at least 16 queues, whatever the environment sets (a smaller value there must not win)
+if int(os.environ.get("GPU_MAX_HW_QUEUES") or 0) < 16:
+    os.environ["GPU_MAX_HW_QUEUES"] = "16"
 import numpy as np
 
 import force2vec_amd as F
