@@ -2,7 +2,12 @@
 
 csrc/ holds the HIP kernels and the C ABI (libf2v.so, include/f2v.h); this package is the
 host-side mirror of the reference's interface for the one hot path (options 5-11 force
-kernels + SGD row update).  Importing it never imports anything from oracle/."""
+kernels + SGD row update).  Importing it never imports anything from oracle/.
+
+Training progress: `Engine.objective(option, ns=5)` evaluates the training objective (the
+reference's per-epoch loglike, defined in include/f2v.h) of the current matrix on the GPU;
+with `Engine.set_param("loss_every", k)` every f2v_train logs it after every k-th epoch and
+its last, read back with `Engine.train_losses()`."""
 from . import _lib  # noqa: F401
 from ._lib import F2VError  # noqa: F401
 from .engine import Engine, algorithms, output_name, push_masks, read_embd, read_embd_bin, sm_table, write_embd, write_embd_bin  # noqa: F401

@@ -22,6 +22,11 @@ class Stats(C.Structure):
                 ("snapshot_seconds", C.c_double), ("recoveries", C.c_uint64), ("recovered", C.c_uint32), ("merge_finalize", C.c_uint32)]
 
 
+class Objective(C.Structure):  # f2v_objective_t
+    _fields_ = [("loss", C.c_double), ("attraction", C.c_double), ("repulsion", C.c_double),
+                ("positive_pairs", C.c_uint64), ("negative_pairs", C.c_uint64)]
+
+
 # every entry point declared in include/f2v.h: name -> (restype, argtypes)
 SIGNATURES = {
     "f2v_last_error": (C.c_char_p, []),
@@ -54,6 +59,8 @@ SIGNATURES = {
     "f2v_synchronize": (C.c_int, [C.c_void_p]),
     "f2v_get_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "f2v_train_marks": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_uint32, u32p]),
+    "f2v_objective": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.POINTER(Objective)]),
+    "f2v_train_losses": (C.c_int, [C.c_void_p, u32p, C.POINTER(C.c_double), C.c_uint32, u32p]),
     "f2v_push_export": (C.c_int, [C.c_void_p, C.c_void_p]),
     "f2v_push_attach": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "f2v_push_selftest": (C.c_int, [C.c_void_p]),

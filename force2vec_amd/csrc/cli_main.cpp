@@ -6,7 +6,8 @@
 // binary CSR "<input>.f2vcsr"), -binout 1 (also write "<output>.embd.bin", raw fp32 N x D), -notext 1, -fastrng 1
 // (NON-parity fast mode: device-side initial embeddings and option-7 walks), -gpus <n> (one forked process per GPU,
 // devices -device .. -device+n-1: every minibatch's rows sharded over them, new rows pushed over xGMI --
-// f2v_train_sharded; the ranks meet through files in a private temporary directory; same output, written by rank 0).
+// f2v_train_sharded; the ranks meet through files in a private temporary directory; same output, written by rank 0),
+// -loss <k> (print the training objective after every k-th epoch and the last, in the line the reference has commented out).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -27,7 +28,7 @@ namespace {
 struct Settings {
     std::string input, output, init;
     long batch = 384, iter = 1200, threads = (long)std::thread::hardware_concurrency(), dim = 128, nsamples = 5, option = 5, bs = 0;
-    long device = 0, seed = 1, cache = 0, binout = 0, fastrng = 0, notext = 0, gpus = 1, samegpu = 0;
+    long device = 0, seed = 1, cache = 0, binout = 0, fastrng = 0, notext = 0, gpus = 1, samegpu = 0, loss = 0;
     double gamma = 1.0, lr = 0.02;
 };
 
@@ -89,6 +90,7 @@ int main(int argc, char *argv[]) {
         {"-gpus", Kind::Integer, &s.gpus, "<int>, number of GPUs (1..8): one process per GPU from -device on, minibatch rows sharded, rows exchanged over xGMI. (default:1)"},
         {"-samegpu", Kind::Integer, &s.samegpu, "<int>, 1 = all ranks of a -gpus run on device -device (self-test on a one-GPU machine)."},
         {"-fastrng", Kind::Integer, &s.fastrng, "<int>, 1 = NON-PARITY fast mode: initial embeddings and option-7 walks from a device-side RNG."},
+        {"-loss", Kind::Integer, &s.loss, "<int>, k > 0: print \"Iteration:<epoch> :LOGLIKELIHOOD: <loss>\" after every k-th epoch and the last (the training objective, include/f2v.h; one GPU). (default:0)"},
     };
     const size_t nflags = sizeof flags / sizeof flags[0];
     for (int p = 1; p < argc; p++) {
@@ -124,6 +126,14 @@ int main(int argc, char *argv[]) {
         printf("-gpus must be 1..%d.\n", F2V_PUSH_MAX_RANKS);
         return 1;
     }
+    if (s.loss < 0 || s.loss > 0x7FFFFFFF) {
+        printf("-loss must be a non-negative number of epochs.\n");
+        return 1;
+    }
+    if (s.loss > 0 && s.gpus > 1) {
+        printf("-loss is not available with -gpus > 1 (a rank does not hold the whole matrix between minibatches).\n");
+        return 1;
+    }
     std::vector<VALUETYPE> seconds;
     int rank = 0;
     std::string meet;  // directory the ranks of a -gpus run meet in
@@ -151,11 +161,20 @@ int main(int argc, char *argv[]) {
             algo.text_output = s.notext == 0;
             algo.init_path = s.init;
             if (s.fastrng && f2v_set_param(algo.h, "fast_rng", 1) != F2V_OK) throw std::runtime_error(f2v_last_error());
+            if (s.loss > 0 && f2v_set_param(algo.h, "loss_every", s.loss) != F2V_OK) throw std::runtime_error(f2v_last_error());
             algo.srand((unsigned)s.seed);
             if (s.gpus > 1) algo.join_ranks(rank, (int)s.gpus, meet);
             if (rank == 0) std::cout << "Running: " << variant->name << std::endl;
             auto method = (s.bs != 0 && variant->with_bs) ? variant->with_bs : variant->plain;
             seconds = (algo.*method)((INDEXTYPE)s.iter, (INDEXTYPE)s.threads, (INDEXTYPE)s.batch, (INDEXTYPE)s.nsamples, (VALUETYPE)s.lr);
+            if (s.loss > 0 && rank == 0) {  // the reference's commented-out print (sample/algorithms.cpp:645), from the run's log
+                uint32_t count = 0;
+                if (f2v_train_losses(algo.h, nullptr, nullptr, 0, &count) != F2V_OK) throw std::runtime_error(f2v_last_error());
+                std::vector<uint32_t> epochs(count);
+                std::vector<double> values(3 * (size_t)count);
+                if (f2v_train_losses(algo.h, epochs.data(), values.data(), count, &count) != F2V_OK) throw std::runtime_error(f2v_last_error());
+                for (uint32_t m = 0; m < count; m++) std::cout << "Iteration:" << epochs[m] << " :LOGLIKELIHOOD: " << values[3 * m] << std::endl;
+            }
             const double t = algo.gpu_train_seconds;
             if (rank == 0 && s.gpus == 1)
                 printf("GPU epoch loop: %.6f s, %.4g nnz/s, %.1f GB/s algorithmic\n", t, t > 0 ? algo.stats.nnz / t : 0.0,

@@ -46,6 +46,7 @@ using namespace f2v;
 constexpr size_t kIpcMaxBytes = (size_t)1 << 31;  // allocations of this size and more cannot be opened through HIP IPC (f2v_push_export)
 constexpr uint32_t kPadRows = 4096;  // slack behind row N for the padded in-place all-gather of the last minibatch
 constexpr int kMaxFinLevels = 32;  // fan-in >= 2: 2^32 chunks
+constexpr uint32_t kLossLogMax = 4096;  // "loss_every": entries one f2v_train keeps
 struct Plan {
     size_t item_off = 0;
     uint32_t n_items = 0, n_hubs = 0, n_chunks = 0, n_slots = 0;
@@ -138,6 +139,16 @@ struct f2v_ctx {
     bool unit_degi = false;  // the option being run is 10 (StepArgs::unit_degi): set by every entry point that takes an option
     uint32_t mark_every = 0;       // "epoch_marks"
     std::vector<double> marks;     // f2v_train_marks
+    // the training objective (f2v_objective, "loss_every"): row-piece items (built once, from rowptr alone), one ObjPartial per
+    // workgroup, and the results -- slot k < kLossLogMax: entry k of f2v_train's log, slot kLossLogMax: f2v_objective's
+    Item *d_obj_items = nullptr;
+    uint32_t obj_items = 0;
+    ObjPartial *d_obj_part = nullptr, *d_obj_out = nullptr;
+    uint32_t loss_every = 0;                      // "loss_every"
+    uint64_t loss_seed = 1;                       // "loss_seed"
+    double last_loss_us = 0.0;                    // "last_loss_us"
+    std::vector<uint32_t> loss_epochs;            // f2v_train_losses
+    std::vector<double> loss_values;              // ... loss, attraction, repulsion per entry
     uint32_t last_wide_width = 0;  // the layout width of the last wide-form f2v_train ("last_wide_width")
     bool last_wide_early = false;  // ... and whether it ran the kernel's EARLY form ("last_wide_early")
     int last_train_form = 0;  // how the last f2v_train launched: 0 one launch per minibatch, 1 chained, 2 chained in the wide form ("last_train_form")
@@ -1262,6 +1273,93 @@ int flush_pending(f2v_ctx *c) {
     return F2V_OK;
 }
 
+// ---- the training objective (f2v_objective, "loss_every") ---------------------------------------------------------------------
+int math_of_option(int option);
+
+// The whole matrix as it stands without folding anything back: d_X[cur] when nothing is pending, the second matrix after a completed
+// epoch (every row updated); nullptr otherwise (flush first).
+const float *settled_matrix(const f2v_ctx *c) {
+    if (c->upd_hi == c->upd_lo) return c->d_X[c->cur];
+    if (c->upd_lo == 0 && c->upd_hi == c->n) return c->d_X[c->cur ^ 1];
+    return nullptr;
+}
+
+uint64_t mix64_host(uint64_t z) {  // f2v_kernels.hip.h: mix64
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// The objective kernel's items (every row cut into pieces of at most kObjChunk neighbours; the last piece of a row, also of a row
+// without neighbours, takes its negative samples), sorted by neighbour count, longest first, ties in row order -- a function of
+// rowptr alone -- and the buffers of its results.  Once per handle, outside every timed loop.
+int objective_prepare(f2v_ctx *c) {
+    if (c->d_obj_items) return F2V_OK;
+    std::vector<uint32_t> count(kObjChunk + 1, 0);
+    uint64_t total = 0;
+    for (uint32_t r = 0; r < c->n; r++) {
+        const uint32_t deg = c->rowptr[r + 1] - c->rowptr[r];
+        const uint32_t pieces = deg ? (deg + kObjChunk - 1) / kObjChunk : 1u;
+        total += pieces;
+        count[kObjChunk] += pieces - 1;
+        count[deg ? deg - (pieces - 1) * kObjChunk : 0]++;
+    }
+    if (total > 0xFFFFFFFFull - kObjItemsPerWg) return fail(F2V_EINVAL, "f2v_objective: %llu work items are too many", (unsigned long long)total);
+    std::vector<uint32_t> start(kObjChunk + 1, 0);  // counting sort, longest first
+    for (int k = (int)kObjChunk - 1; k >= 0; k--) start[k] = start[k + 1] + count[k + 1];
+    std::vector<Item> items(total);
+    for (uint32_t r = 0; r < c->n; r++) {
+        const uint32_t rp = c->rowptr[r], deg = c->rowptr[r + 1] - rp;
+        const uint32_t pieces = deg ? (deg + kObjChunk - 1) / kObjChunk : 1u;
+        for (uint32_t p = 0; p < pieces; p++) {
+            const uint32_t cnt = std::min(kObjChunk, deg - p * kObjChunk);
+            items[start[cnt]++] = Item{r, rp + p * kObjChunk, cnt, p + 1 == pieces ? kItemLast : 0u};
+        }
+    }
+    const uint32_t wgs = (uint32_t)((total + kObjItemsPerWg - 1) / kObjItemsPerWg);
+    HIPC(hipMalloc((void **)&c->d_obj_items, std::max<size_t>(total, 1) * sizeof(Item)));
+    HIPC(hipMalloc((void **)&c->d_obj_part, std::max<size_t>(wgs, 1) * sizeof(ObjPartial)));
+    HIPC(hipMalloc((void **)&c->d_obj_out, (kLossLogMax + 1) * sizeof(ObjPartial)));
+    if (total) HIPC(hipMemcpy(c->d_obj_items, items.data(), total * sizeof(Item), hipMemcpyHostToDevice));
+    c->obj_items = (uint32_t)total;
+    return F2V_OK;
+}
+
+template <int SIG, int VEC, bool EXACT>
+void launch_objective_t(f2v_ctx *c, const ObjArgs &a, uint32_t wgs) {
+    hipLaunchKernelGGL((objective_kernel<SIG, VEC, EXACT>), dim3(wgs), dim3(64 * 4), 0, c->stream, a);
+}
+
+// Enqueue one evaluation of matrix X (two launches, no synchronisation, no allocation): *out receives the sums.
+int launch_objective(f2v_ctx *c, const float *X, int option, uint32_t ns, ObjPartial *out) {
+    ObjArgs a{};
+    a.X = X;
+    a.rowptr = c->d_rowptr;
+    a.colids = c->d_colids;
+    a.items = c->d_obj_items;
+    a.part = c->d_obj_part;
+    a.seed_mix = mix64_host(c->loss_seed);
+    a.n_items = c->obj_items;
+    a.n = c->n;
+    a.D = c->D;
+    a.ns = ns;
+    a.unit_degi = option == 10 ? 1u : 0u;
+    const bool sig = math_of_option(option) != 5;
+    const uint32_t wgs = (c->obj_items + kObjItemsPerWg - 1) / kObjItemsPerWg;
+    if (wgs) {
+        int rc = dispatch_layout(c, [&](auto V, auto E) {
+            if (sig) launch_objective_t<1, decltype(V)::value, decltype(E)::value>(c, a, wgs);
+            else launch_objective_t<0, decltype(V)::value, decltype(E)::value>(c, a, wgs);
+        });
+        if (rc != F2V_OK) return rc;
+        HIPC(hipGetLastError());
+    }
+    hipLaunchKernelGGL(objective_reduce_kernel, dim3(1), dim3(1024), 0, c->stream, (const ObjPartial *)c->d_obj_part, wgs, out);
+    HIPC(hipGetLastError());
+    return F2V_OK;
+}
+
 // A combine-tree node's wait timed out (the words of d_kerr are in `e`): nodes that give up store nothing, so the rows
 // of the affected hub vertices were not updated from that launch on -- the embeddings are invalid and must be set again.
 // The handle stays usable: the error words are cleared and it runs one launch per tree level from now on (no in-grid waits).
@@ -1963,7 +2061,7 @@ int f2v_destroy(f2v_handle c) {
     (void)hipSetDevice(c->device);
     (void)push_detach(c);
     void *ptrs[] = {c->d_rowptr, c->d_colids, c->d_walks, c->d_walks_alt, c->d_ids, c->d_X[0], c->d_X[1],
-                    c->d_partials, c->d_table, c->d_items, c->d_hubs, c->d_ready, c->d_kerr, c->d_wg, c->d_rowflag, c->d_snap, c->d_wide, c->d_jobs, c->d_ring, c->d_ring_partials, c->d_ring_flags, c->d_ring_ready, c->push.flags, c->push.d_err, c->push.d_masks, c->push.d_patch, c->push.landing_buf};
+                    c->d_partials, c->d_table, c->d_items, c->d_hubs, c->d_ready, c->d_kerr, c->d_wg, c->d_rowflag, c->d_snap, c->d_wide, c->d_jobs, c->d_ring, c->d_ring_partials, c->d_ring_flags, c->d_ring_ready, c->d_obj_items, c->d_obj_part, c->d_obj_out, c->push.flags, c->push.d_err, c->push.d_masks, c->push.d_patch, c->push.landing_buf};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
 #ifdef F2V_TEST_HOOKS
@@ -2270,6 +2368,15 @@ int f2v_set_param(f2v_handle c, const char *name, int64_t value) {
         drop_plans(c);
         return F2V_OK;
     }
+    if (!strcmp(name, "loss_every")) {
+        if (value < 0 || value > 0x7FFFFFFF) return fail(F2V_EINVAL, "loss_every out of range");
+        c->loss_every = (uint32_t)value;
+        return F2V_OK;
+    }
+    if (!strcmp(name, "loss_seed")) {
+        c->loss_seed = (uint64_t)value;
+        return F2V_OK;
+    }
     if (!strcmp(name, "chain_timeout_ms")) {
         if (value < 1 || value > 600000) return fail(F2V_EINVAL, "chain_timeout_ms must be 1..600000");
         c->chain_timeout_ms = value;
@@ -2330,6 +2437,9 @@ int f2v_get_param(f2v_handle c, const char *name, int64_t *out) {
     if (!strcmp(name, "chain_timeout_ms")) { *out = c->chain_timeout_ms; return F2V_OK; }
     if (!strcmp(name, "chain_wide")) { *out = c->wide ? 1 : 0; return F2V_OK; }
     if (!strcmp(name, "epoch_marks")) { *out = c->mark_every; return F2V_OK; }
+    if (!strcmp(name, "loss_every")) { *out = c->loss_every; return F2V_OK; }
+    if (!strcmp(name, "loss_seed")) { *out = (int64_t)c->loss_seed; return F2V_OK; }
+    if (!strcmp(name, "last_loss_us")) { *out = (int64_t)(c->last_loss_us + 0.5); return F2V_OK; }
     if (!strcmp(name, "wide_phases")) { *out = c->wide_phases; return F2V_OK; }
     if (!strcmp(name, "wide_max_batch")) { *out = c->wide_max_batch; return F2V_OK; }
     if (!strcmp(name, "wide_min_width")) { *out = c->wide_min_width; return F2V_OK; }
@@ -2635,9 +2745,44 @@ int f2v_train_marks(f2v_handle c, double *seconds_out, uint32_t cap, uint32_t *c
     return F2V_OK;
 }
 
+int f2v_objective(f2v_handle c, int option, uint32_t ns, f2v_objective_t *out) {
+    if (!c || !out) return fail(F2V_EINVAL, "f2v_objective: null argument");
+    if (!math_of_option(option)) return fail(F2V_EINVAL, "f2v_objective: option %d is outside 5..11", option);
+    if (c->n < 2) return fail(F2V_EINVAL, "f2v_objective: the graph needs at least two vertices");
+    if (!c->have_x)
+        return fail(F2V_ESTATE, c->x_invalid ? "f2v_objective: the embeddings are invalid since a launch gave up a bounded wait: set or initialise them again"
+                                             : "f2v_objective: embeddings were never initialised");
+    HIPC(hipSetDevice(c->device));
+    int rc = flush_pending(c);
+    if (rc != F2V_OK) return rc;
+    if ((rc = objective_prepare(c)) != F2V_OK) return rc;
+    if ((rc = launch_objective(c, c->d_X[c->cur], option, ns, c->d_obj_out + kLossLogMax)) != F2V_OK) return rc;
+    ObjPartial r;
+    HIPC(hipMemcpyAsync(&r, c->d_obj_out + kLossLogMax, sizeof r, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    if ((rc = check_kernel_err(c, "f2v_objective")) != F2V_OK) return rc;
+    out->attraction = r.attraction;
+    out->repulsion = r.repulsion;
+    out->loss = r.attraction + r.repulsion;
+    out->positive_pairs = r.positive_pairs;
+    out->negative_pairs = r.negative_pairs;
+    return F2V_OK;
+}
+
+int f2v_train_losses(f2v_handle c, uint32_t *epochs_out, double *values_out, uint32_t cap, uint32_t *count_out) {
+    if (!c || (cap && (!epochs_out || !values_out))) return fail(F2V_EINVAL, "f2v_train_losses: null argument");
+    if (count_out) *count_out = (uint32_t)c->loss_epochs.size();
+    for (uint32_t k = 0; k < cap && k < c->loss_epochs.size(); k++) {
+        epochs_out[k] = c->loss_epochs[k];
+        for (int v = 0; v < 3; v++) values_out[3 * k + v] = c->loss_values[3 * k + v];
+    }
+    return F2V_OK;
+}
+
 int f2v_train_sharded(f2v_handle c, int option, uint32_t iters, uint32_t batch, uint32_t ns, float lr, int bs_mode,
                       double *seconds_out) {
     if (!c) return fail(F2V_EINVAL, "null handle");
+    if (c->loss_every) return fail(F2V_EINVAL, "f2v_train_sharded: \"loss_every\" is not supported (a rank does not hold the whole matrix between minibatches)");
     if (!c->push.attached) return fail(F2V_ESTATE, "f2v_train_sharded: f2v_push_attach first");
     const int math = math_of_option(option);
     c->last_replicated = false;
@@ -2672,6 +2817,10 @@ int train_impl(f2v_ctx *c, int option, uint32_t iters, uint32_t batch, uint32_t 
     if (!c->have_x) return fail(F2V_ESTATE, "f2v_train: embeddings not initialised (f2v_init_embeddings)");
     if (batch == 0) return fail(F2V_EINVAL, "f2v_train: batch must be positive");
     if (math == 7 && bs_mode) return fail(F2V_EINVAL, "option 7 has no -bs 1 variant");
+    c->loss_epochs.clear();  // (a call run again from its snapshot starts the log afresh)
+    c->loss_values.clear();
+    c->last_loss_us = 0.0;
+    if (c->loss_every && c->n < 2) return fail(F2V_EINVAL, "f2v_train: \"loss_every\" needs a graph of at least two vertices");
     HIPC(hipSetDevice(c->device));
     int rc;
     const uint32_t n = c->n;
@@ -2785,6 +2934,29 @@ int train_impl(f2v_ctx *c, int option, uint32_t iters, uint32_t batch, uint32_t 
     std::vector<hipEvent_t> mark_ev;  // "epoch_marks"
     c->marks.clear();
     if ((rc = events.make(&ev0, hipEventDefault)) != F2V_OK || (rc = events.make(&ev1, hipEventDefault)) != F2V_OK) return rc;
+    // "loss_every" = k: the objective of the matrix after epochs k, 2k, ... and after the last one, enqueued between the epochs (no
+    // synchronisation, no allocation in the loop), each bracketed by a pair of events: their time is taken out of the epoch loop's and
+    // the marks'.  The results stay on the device until the end of the call.
+    const uint32_t loss_k = c->loss_every;
+    const uint32_t loss_planned = loss_k ? std::min<uint32_t>(iters / loss_k + (iters % loss_k ? 1u : 0u), kLossLogMax) : 0u;
+    std::vector<hipEvent_t> loss_ev(2 * (size_t)loss_planned);
+    std::vector<uint32_t> loss_log;  // the epochs of the evaluations enqueued so far
+    std::vector<size_t> mark_loss;   // evaluations enqueued before each mark
+    if (loss_planned) {
+        if ((rc = objective_prepare(c)) != F2V_OK) return rc;
+        for (auto &e : loss_ev)
+            if ((rc = events.make(&e, hipEventDefault)) != F2V_OK) return rc;
+    }
+    auto loss_due = [&](uint32_t g) { return loss_k && (g % loss_k == 0 || g == iters) && loss_log.size() < loss_planned; };
+    auto evaluate = [&](uint32_t g, const float *X) -> int {  // epoch g (1-based) left matrix X
+        const size_t m = loss_log.size();
+        HIPC(hipEventRecord(loss_ev[2 * m], c->stream));
+        const int r = launch_objective(c, X, option, ns, c->d_obj_out + m);
+        if (r != F2V_OK) return r;
+        HIPC(hipEventRecord(loss_ev[2 * m + 1], c->stream));
+        loss_log.push_back(g);
+        return F2V_OK;
+    };
     HIPC(hipEventRecord(ev0, c->stream));
 #ifdef F2V_TEST_HOOKS
     // F2V_PUSH_CHAOS=<seed> (self-test build only): every rank stalls at random minibatches (different ones on every rank)
@@ -2818,6 +2990,8 @@ int train_impl(f2v_ctx *c, int option, uint32_t iters, uint32_t batch, uint32_t 
         // which each replay finds at a fixed place (its parity's region of d_ids), refreshed by a stream-ordered copy.
         hipGraph_t graph[2] = {nullptr, nullptr};
         hipGraphExec_t exec[2] = {nullptr, nullptr};
+        if (loss_planned && (rc = flush_pending(c)) != F2V_OK) return rc;  // (what the first captured step would do): epoch e then reads
+        const int cur0 = c->cur;                                             // d_X[cur0 ^ (e & 1)] and writes the other one
         for (int par = 0; par < 2; par++) {
             HIPC(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
             c->capturing = true;  // a replayed launch cannot carry a fresh sequence number: one launch per tree level
@@ -2841,6 +3015,7 @@ int train_impl(f2v_ctx *c, int option, uint32_t iters, uint32_t batch, uint32_t 
                 HIPC(hipMemcpyAsync(c->d_ids + (size_t)(it & 1) * per_epoch, ids.data() + (size_t)it * per_epoch, per_epoch * sizeof(uint32_t),
                                     hipMemcpyHostToDevice, c->stream));
             HIPC(hipGraphLaunch(exec[it & 1], c->stream));
+            if (loss_due(it + 1) && (rc = evaluate(it + 1, c->d_X[cur0 ^ ((it + 1) & 1)])) != F2V_OK) return rc;
         }
         if (iters & 1) c->cur ^= 1;  // an odd number of epochs ends on the other matrix than the two captured ones did
         c->stats = one;
@@ -2959,6 +3134,9 @@ int train_impl(f2v_ctx *c, int option, uint32_t iters, uint32_t batch, uint32_t 
                 uint32_t E = 1;
                 if (epochs_max > 1 && K >= nb && plan.n_node_wgs == 0 && !c->ring_refused) E = std::min(epochs_max, iters - it);
                 if ((rc = launch_wide(c, math, plan, d_epoch_ids, (uint32_t)stride, ns, lr, bs_mode, &E, per_epoch)) != F2V_OK) return rc;
+                for (uint32_t e = 0; e + 1 < E; e++) {  // epochs inside a multi-epoch launch: epoch e left matrix e + 1 of its ring
+                    if (loss_due(it + e + 1) && (rc = evaluate(it + e + 1, c->d_ring + (size_t)(e + 1) * n * c->D)) != F2V_OK) return rc;
+                }
                 it += E - 1;
             }
         } else if (chained) {
@@ -2995,6 +3173,15 @@ int train_impl(f2v_ctx *c, int option, uint32_t iters, uint32_t batch, uint32_t 
             if ((rc = events.make(&e, hipEventDefault)) != F2V_OK) return rc;
             HIPC(hipEventRecord(e, c->stream));
             mark_ev.push_back(e);
+            mark_loss.push_back(loss_log.size());
+        }
+        if (loss_due(it + 1)) {
+            const float *X = settled_matrix(c);
+            if (!X) {
+                if ((rc = flush_pending(c)) != F2V_OK) return rc;
+                X = c->d_X[c->cur];
+            }
+            if ((rc = evaluate(it + 1, X)) != F2V_OK) return rc;
         }
         if (c->merge_fin) {
             const int slot = (int)(err_seq++ % kErrRing);  // (by copies made, not by epoch: a launch may carry 32 epochs)
@@ -3030,14 +3217,29 @@ int train_impl(f2v_ctx *c, int option, uint32_t iters, uint32_t batch, uint32_t 
     HIPC(hipEventSynchronize(ev1));
     float ms = 0.f;
     HIPC(hipEventElapsedTime(&ms, ev0, ev1));
-    c->stats.device_seconds = ms * 1e-3;
-    if (seconds_out) *seconds_out = ms * 1e-3;
-    for (hipEvent_t e : mark_ev) {
+    std::vector<double> loss_ms(loss_log.size() + 1, 0.0);  // evaluation time before entry m: not the epoch loop's
+    for (size_t m = 0; m < loss_log.size(); m++) {
+        float em = 0.f;
+        HIPC(hipEventElapsedTime(&em, loss_ev[2 * m], loss_ev[2 * m + 1]));
+        loss_ms[m + 1] = loss_ms[m] + em;
+    }
+    c->last_loss_us = loss_ms.back() * 1e3;
+    c->stats.device_seconds = loss_log.empty() ? ms * 1e-3 : (ms - loss_ms.back()) * 1e-3;
+    if (seconds_out) *seconds_out = c->stats.device_seconds;
+    for (size_t k = 0; k < mark_ev.size(); k++) {
         float mm = 0.f;
-        HIPC(hipEventElapsedTime(&mm, ev0, e));
-        c->marks.push_back(mm * 1e-3);
+        HIPC(hipEventElapsedTime(&mm, ev0, mark_ev[k]));
+        c->marks.push_back(loss_log.empty() ? mm * 1e-3 : (mm - loss_ms[mark_loss[k]]) * 1e-3);
     }
     if ((rc = check_kernel_err(c, sharded ? "f2v_train_sharded" : "f2v_train")) != F2V_OK) return rc;
+    if (!loss_log.empty()) {  // the log's one copy to the host
+        std::vector<ObjPartial> r(loss_log.size());
+        HIPC(hipMemcpy(r.data(), c->d_obj_out, r.size() * sizeof(ObjPartial), hipMemcpyDeviceToHost));
+        for (size_t m = 0; m < r.size(); m++) {
+            c->loss_epochs.push_back(loss_log[m]);
+            c->loss_values.insert(c->loss_values.end(), {r[m].attraction + r[m].repulsion, r[m].attraction, r[m].repulsion});
+        }
+    }
     if (exchanging) return check_push_err(c, "f2v_train_sharded");
     return F2V_OK;
 }

@@ -2151,6 +2151,181 @@ __global__ __launch_bounds__(256) void stream_copy_kernel(const f32x4_copy_t *sr
         if (base + (uint64_t)u * 256u < n4) __builtin_nontemporal_store(v[u], dst + base + (uint64_t)u * 256u);
 }
 
+// ---- the training objective (f2v_objective, "loss_every"; definition in include/f2v.h) ------------------------------------------
+// Work items are pieces of rows -- Item{row, first neighbour, neighbours, kItemLast on the row's last piece, which also takes the
+// row's ns negative samples} of at most kObjChunk neighbours, so a hub is many items -- built once per handle from rowptr alone and
+// sorted by neighbour count, longest first.  A quarter-wave (16 lanes, one DPP row) owns one item: x_i stays in registers, lane t
+// holds dims [64k + 4t, +4) for k < VEC; it gathers U rows at a time, reduces every pair's fp32 squared distance / dot product in
+// the lane and over its 16 lanes (item_allreduce_tree), and lane u < U of the quarter then evaluates pair u's fp64 term, so one fp64
+// log serves U pairs of every quarter.  Sums: per lane in pair order, per item a fixed xor tree over its 16 lanes, per workgroup its
+// 16 items in order -> one ObjPartial per workgroup; objective_reduce_kernel adds those in a fixed order.  No float atomics: the
+// value depends on (X, CSR, option, ns, seed) and D alone, not on the launch's timing or on any tunable of the step kernels.
+constexpr uint32_t kObjChunk = 64;       // neighbours per item at most
+constexpr uint32_t kObjItemsPerWg = 16;  // 4 waves x 4 quarter-waves
+struct ObjPartial {
+    double attraction, repulsion;
+    unsigned long long positive_pairs, negative_pairs;
+};
+
+struct ObjArgs {
+    const float *X;
+    const uint32_t *rowptr, *colids;
+    const Item *items;
+    ObjPartial *part;  // one per workgroup
+    uint64_t seed_mix;  // mix64(seed)
+    uint32_t n_items, n, D, ns;
+    uint32_t unit_degi;
+};
+
+// Row of 64*VEC (zero-padded) dims as VEC 16-byte pieces per lane of a quarter-wave: piece k of lane t = dims [64k + 4t, +4)
+template <int VEC, bool EXACT>
+__device__ __forceinline__ void obj_load(const float *src, uint32_t t, uint32_t D, float (&out)[VEC][4]) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+        const uint32_t d0 = 64u * k + 4u * t;
+        if (EXACT || (D % 4u == 0u && d0 < D)) {
+            const float4 v = *reinterpret_cast<const float4 *>(src + d0);
+            out[k][0] = v.x; out[k][1] = v.y; out[k][2] = v.z; out[k][3] = v.w;
+        } else {
+#pragma unroll
+            for (int v = 0; v < 4; ++v) out[k][v] = (d0 + v < D) ? src[d0 + v] : 0.0f;
+        }
+    }
+}
+
+__device__ __forceinline__ double softplus(double z) { return fmax(z, 0.0) + log1p(exp(-fabs(z))); }
+
+// SIG = 0: t-distribution (options 5, 8, 11), 1: sigmoid (6, 7, 9, 10)
+template <int SIG, int VEC, bool EXACT>
+__global__ __launch_bounds__(256) void objective_kernel(const ObjArgs a) {
+    constexpr int U = VEC >= 8 ? 2 : (VEC >= 4 ? 4 : 8);  // row gathers in flight per quarter-wave
+    __shared__ double s_att[kObjItemsPerWg], s_rep[kObjItemsPerWg];
+    __shared__ uint32_t s_pos[kObjItemsPerWg], s_neg[kObjItemsPerWg];
+    const uint32_t t = threadIdx.x & 15u;
+    const uint32_t q = threadIdx.x >> 4;
+    const uint32_t w = blockIdx.x * kObjItemsPerWg + q;
+    const uint32_t D = a.D;
+    double att = 0.0, rep = 0.0;
+    uint32_t npos = 0, nneg = 0;
+    if (w < a.n_items) {
+        const Item it = a.items[w];
+        const uint32_t cnt = it.cnt;
+        const uint32_t total = cnt + ((it.flags & kItemLast) ? a.ns : 0u);
+        float xi[VEC][4];
+        obj_load<VEC, EXACT>(a.X + (size_t)it.row * D, t, D, xi);
+        double degi = 1.0;
+        if (SIG && !a.unit_degi) degi = 1.0 / (double)(a.rowptr[it.row + 1] - a.rowptr[it.row] + 1u);
+        const uint64_t sbase = (uint64_t)it.row * a.ns;
+        for (uint32_t b = 0; b < total; b += U) {
+            float xj[U][VEC][4];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const uint32_t p = (b + u < total) ? b + u : total - 1u;
+                const uint32_t j = p < cnt ? a.colids[it.nb + p] : (uint32_t)(mix64(a.seed_mix ^ (sbase + (p - cnt))) % (uint64_t)(a.n - 1u));
+                obj_load<VEC, EXACT>(a.X + (size_t)j * D, t, D, xj[u]);
+            }
+            float s[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                float bs[VEC];
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) {
+                    float e[4];
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) {
+                        if constexpr (SIG) {
+                            e[v] = xi[k][v] * xj[u][k][v];
+                        } else {
+                            const float d = xi[k][v] - xj[u][k][v];
+                            e[v] = d * d;
+                        }
+                    }
+                    bs[k] = (e[0] + e[1]) + (e[2] + e[3]);
+                }
+                s[u] = item_allreduce_tree<16>(inlane_tree<VEC>(bs));
+            }
+            float mine = s[0];  // lane t < U of the quarter takes pair b + t
+#pragma unroll
+            for (int u = 1; u < U; ++u) mine = (t == (uint32_t)u) ? s[u] : mine;
+            const uint32_t p = b + t;
+            if (t < (uint32_t)U && p < total) {
+                const double z = (double)mine;
+                if (p < cnt) {
+                    att += SIG ? degi * softplus(-z) : log1p(z);
+                    npos++;
+                } else {
+                    rep += SIG ? softplus(z) : -(log(1e-6 + z) - log1p(z));
+                    nneg++;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 1; m < 16; m <<= 1) {  // the item's 16 lanes, xor tree (both partners form the same sum)
+        att = att + __shfl_xor(att, m, 16);
+        rep = rep + __shfl_xor(rep, m, 16);
+        npos += __shfl_xor(npos, m, 16);
+        nneg += __shfl_xor(nneg, m, 16);
+    }
+    if (t == 0) {
+        s_att[q] = att;
+        s_rep[q] = rep;
+        s_pos[q] = npos;
+        s_neg[q] = nneg;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        ObjPartial r{0.0, 0.0, 0ull, 0ull};
+        for (uint32_t k = 0; k < kObjItemsPerWg; ++k) {
+            r.attraction = r.attraction + s_att[k];
+            r.repulsion = r.repulsion + s_rep[k];
+            r.positive_pairs += s_pos[k];
+            r.negative_pairs += s_neg[k];
+        }
+        a.part[blockIdx.x] = r;
+    }
+}
+
+// One workgroup: thread k adds partials k, k + 1024, ... in order, then a fixed pairwise tree over the threads.
+__global__ __launch_bounds__(1024) void objective_reduce_kernel(const ObjPartial *part, uint32_t n_part, ObjPartial *out) {
+    __shared__ double s_att[1024], s_rep[1024];
+    __shared__ unsigned long long s_pos[1024], s_neg[1024];
+    const uint32_t k = threadIdx.x;
+    double att = 0.0, rep = 0.0;
+    unsigned long long pos = 0, neg = 0;
+    constexpr uint32_t G = 8;  // loads in flight per thread
+    for (uint32_t base = k; base < n_part; base += G * 1024u) {
+        ObjPartial v[G];
+#pragma unroll
+        for (uint32_t g = 0; g < G; ++g) {
+            const uint32_t i = base + g * 1024u;
+            v[g] = i < n_part ? part[i] : ObjPartial{0.0, 0.0, 0ull, 0ull};
+        }
+#pragma unroll
+        for (uint32_t g = 0; g < G; ++g) {
+            att = att + v[g].attraction;
+            rep = rep + v[g].repulsion;
+            pos += v[g].positive_pairs;
+            neg += v[g].negative_pairs;
+        }
+    }
+    s_att[k] = att;
+    s_rep[k] = rep;
+    s_pos[k] = pos;
+    s_neg[k] = neg;
+    __syncthreads();
+    for (uint32_t s = 512; s > 0; s >>= 1) {
+        if (k < s) {
+            s_att[k] = s_att[k] + s_att[k + s];
+            s_rep[k] = s_rep[k] + s_rep[k + s];
+            s_pos[k] += s_pos[k + s];
+            s_neg[k] += s_neg[k + s];
+        }
+        __syncthreads();
+    }
+    if (k == 0) *out = ObjPartial{s_att[0], s_rep[0], s_pos[0], s_neg[0]};
+}
+
 #ifdef F2V_TEST_HOOKS
 // Self-test of the reduction order: out[r] = tree sum of in[r*width .. +width)
 __global__ void wave_reduce_test_kernel(const float *in, uint32_t rows, uint32_t width, float *out) {

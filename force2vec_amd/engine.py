@@ -8,11 +8,16 @@ runs in the HIP kernels; nothing here (or anywhere in this package) computes on 
 import ctypes as C
 import os
 import time
+from collections import namedtuple
 
 import numpy as np
 
 from . import _lib
 from ._lib import INIT_SYMMETRIC, INIT_UNIT, check
+
+
+# f2v_objective_t (include/f2v.h): loss = attraction + repulsion; the pair counts are the kernel's work proof (nnz, n * ns)
+Objective = namedtuple("Objective", "loss attraction repulsion positive_pairs negative_pairs")
 
 
 def _u32(a):
@@ -201,6 +206,21 @@ class Engine:
         out = np.zeros(max(n.value, 1), dtype=np.float64)
         self._ck(self._L.f2v_train_marks(self._h, out.ctypes.data_as(C.POINTER(C.c_double)), n.value, C.byref(n)))
         return out[: n.value]
+
+    def objective(self, option, ns=5):
+        """The training objective of the current matrix (include/f2v.h: definition; deterministic) -> Objective."""
+        o = _lib.Objective()
+        self._ck(self._L.f2v_objective(self._h, option, ns, C.byref(o)))
+        return Objective(o.loss, o.attraction, o.repulsion, o.positive_pairs, o.negative_pairs)
+
+    def train_losses(self):
+        """The last f2v_train's "loss_every" log -> (epochs uint32[k], 1-based; values float64[k, 3]: loss, attraction, repulsion)."""
+        n = C.c_uint32()
+        self._ck(self._L.f2v_train_losses(self._h, None, None, 0, C.byref(n)))
+        epochs = np.zeros(max(n.value, 1), dtype=np.uint32)
+        values = np.zeros((max(n.value, 1), 3), dtype=np.float64)
+        self._ck(self._L.f2v_train_losses(self._h, _u32(epochs), values.ctypes.data_as(C.POINTER(C.c_double)), n.value, C.byref(n)))
+        return epochs[: n.value], values[: n.value]
 
     def stats(self):
         s = _lib.Stats()

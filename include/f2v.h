@@ -260,6 +260,47 @@ F2V_API int f2v_get_stats(f2v_handle h, f2v_stats *out);
  * synchronisation inside the loop. */
 F2V_API int f2v_train_marks(f2v_handle h, double *seconds_out, uint32_t cap, uint32_t *count_out);
 
+/* ---- the training objective ------------------------------------------------------------------------------------------------
+ * The reference accumulates a `loglike` per epoch and never prints it (sample/algorithms.cpp:607, :621, :645); this is that
+ * quantity, defined so that it is deterministic.  Evaluated at the current matrix X; lower is better; fp64 sums:
+ *   positive pairs (i, j): the CSR nonzeros, duplicates included, for EVERY option -- for options 7 and 10 too the graph's edges,
+ *     not an epoch's walk samples (those change every epoch and would make the curve noise);
+ *   negative samples: row i has ns of them, s(i,k) = mix64(mix64(seed) ^ ((uint64)i * ns + k)) % (n - 1), k < ns -- mix64 is
+ *     the splitmix64 finaliser (z += 0x9E3779B97F4A7C15; z = (z ^ z>>30) * 0xBF58476D1CE4E5B9; z = (z ^ z>>27) * 0x94D049BB133111EB;
+ *     z ^ z>>31), seed the handle parameter "loss_seed" (default 1), the range randIndex(N-1, 0)'s, self-samples not excluded.  The
+ *     handle's rand() stream is never touched (evaluating changes no later result), and the negatives are the same at every
+ *     evaluation of a handle, so successive values compare;
+ *   t-distribution options (5, 8, 11), the reference's own loglike expression (:607, :621):
+ *     attraction = sum_(i,j) log(1 + |x_i - x_j|^2),  repulsion = -sum_(i,k) [log(1e-6 + r) - log(1 + r)],  r = |x_i - x_s(i,k)|^2;
+ *   sigmoid options (6, 7, 9, 10), the function whose gradient the reference's update ascends:
+ *     attraction = sum_i degi * sum_(j in N(i)) softplus(-x_i . x_j),  repulsion = sum_(i,k) softplus(x_i . x_s(i,k)),
+ *     degi = 1 / (deg(i) + 1) (options 6, 7, 9: :852, :1159), 1 for option 10; softplus(z) = max(z, 0) + log1p(exp(-|z|)) exactly,
+ *     not the 2048-entry sigmoid table;
+ *   loss = attraction + repulsion.  A pair's squared distance / dot product is summed in fp32 (as the step kernels do), every log
+ *   term and every sum in fp64.
+ * The value is a function of (X, CSR, option, ns, seed) alone: bitwise identical between calls, handles and GPUs and under every
+ * tunable ("waves_per_block", "quarter_wave", "rows_in_flight", "piece_affinity" ...) -- a fixed work partition (pieces of rows of
+ * at most 64 neighbours, from rowptr alone) and fixed-order sums, no float atomics.  positive_pairs / negative_pairs count the
+ * pairs the kernel evaluated: nnz and n * ns. */
+typedef struct {
+    double loss, attraction, repulsion;
+    uint64_t positive_pairs, negative_pairs;
+} f2v_objective_t;
+/* The objective of the current matrix (pending minibatches are committed first, as f2v_get_embeddings does).  ns = 0: repulsion 0.
+ * F2V_EINVAL for an option outside 5..11 or a graph of fewer than two vertices, F2V_ESTATE without valid embeddings. */
+F2V_API int f2v_objective(f2v_handle h, int option, uint32_t ns, f2v_objective_t *out);
+/* With "loss_every" = k > 0 f2v_train also evaluates the objective -- with the call's option and ns -- after its epochs k, 2k, ...
+ * and after its last epoch (at most 4096 entries per call, the first ones), on the device between the epochs: no host
+ * synchronisation, the multi-epoch wide launches stay (an epoch inside one is evaluated from its matrix of the ring), and the
+ * results are copied to the host once, at the end of the call.  seconds_out, f2v_stats.device_seconds and the epoch marks keep
+ * their meaning, the epoch loop alone: the evaluations are bracketed by events and their time taken out; f2v_get_param
+ * ("last_loss_us") answers it.  A call f2v_train runs again from its snapshot starts the log afresh.  Entry m: the 1-based epoch
+ * of the call in epochs_out[m], loss / attraction / repulsion in values_out[3m .. 3m+2] (up to `cap` entries; `count_out`
+ * receives how many there are).  Equal, bit for bit, to f2v_objective after training the same epochs in separate calls.
+ * f2v_train_sharded with "loss_every" > 0 fails with F2V_EINVAL: a rank does not hold the whole matrix between minibatches (out
+ * of scope). */
+F2V_API int f2v_train_losses(f2v_handle h, uint32_t *epochs_out, double *values_out, uint32_t cap, uint32_t *count_out);
+
 /* ---- host-side I/O of the drop-in boundary (no device needed) ----------------------------
  * f2v_read_mtx replaces SetInputMatricesAsCSR (sample/commonutility.h:44-54 -> ReadASCII
  * sample/IO.h:59-156, CSC sample/CSC.h:146-188, CSR sample/CSR.h:154-186): MatrixMarket
