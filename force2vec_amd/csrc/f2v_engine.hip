@@ -273,10 +273,11 @@ int pick_vec(uint32_t D) {
     return v;
 }
 
-// Hub chunk for minibatches of `batch` rows: a chunk is one quarter-wave's serial stretch (about
-// 0.6 us per neighbour), the launch as a whole streams ~516 B per nonzero at ~6 TB/s; keeping the
-// longest stretch at about half the launch's streaming time gives chunk ~ batch nonzeros / 14000
-// (measured optimum on RMAT-20: 16 at B=4096, 32 at B=16384, 128 at B=65536).  It depends only on
+// Hub chunk for minibatches of `batch` rows: a chunk is one quarter-wave's serial stretch (one dependent
+// round trip per group of U = 4 neighbours, whose rows are in flight together), the launch as a whole streams ~516 B
+// per nonzero at ~6 TB/s; keeping the longest stretch at about half the launch's streaming time gives chunk ~ batch
+// nonzeros / 14000 (measured optimum on RMAT-20: 16 at B=4096, 32 at B=16384, 128 at B=65536 -- measured while the
+// step kernel still waited for each row before requesting the next, ~0.6 us per neighbour; not re-fitted since).  It depends only on
 // the graph and the number of rows one launch covers (the batch, or a rank's slice of it in f2v_train_sharded).
 uint32_t auto_chunk(const f2v_ctx *c, uint32_t batch) {
     const double est = (double)std::min(batch, c->n) * ((double)c->nnz / (double)c->n) / 14000.0;

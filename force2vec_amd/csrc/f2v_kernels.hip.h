@@ -827,9 +827,56 @@ __device__ __forceinline__ HandSrc hand_src_window(const StepArgs &a, uint32_t D
 // fetched one group ahead.
 // FULL: D == 4*LPI*NB.  Otherwise D is any smaller multiple of 4 (rows stay 16-byte aligned): lane t's block b is live
 // iff 4*LPI*b + 4t < D, dead pieces read as zero -- the zero padding of the canonical tree -- and are never stored.
+// `idle`: a valid row id in memory (the item's own, or its wavefront's first item's), read in place of the list when cnt == 0.
 template <int OPT, int LPI, int NB, bool NEG, int U, bool FULL, bool CHAIN>
-__device__ __forceinline__ void qprocess(const StepArgs &a, const HandSrc &hs, const uint32_t *ids, uint32_t cnt, uint32_t maxcnt, uint32_t t, uint32_t D,
-                                         const float (&xi)[NB][4], float (&Y)[NB][4], double c0, const float *table, bool &bad) {
+__device__ __forceinline__ void qprocess(const StepArgs &a, const HandSrc &hs, const uint32_t *ids, const uint32_t *idle, uint32_t cnt, uint32_t maxcnt,
+                                         uint32_t t, uint32_t D, const float (&xi)[NB][4], float (&Y)[NB][4], double c0, const float *table, bool &bad) {
+    // The unconditional gather below costs registers: most forms lose a wave per SIMD for it and gain more (D = 16 / 32 / 64:
+    // -46 / -46 / -16 %; profiles/r05_gather_in_flight.txt), but options 6/7 at a D short of the U = 4 form's width (D = 100:
+    // 80 -> 84 VGPRs, 6 -> 5 waves) measured 2.8 % slower -- those forms keep the one-row-at-a-time gather of the chained path.
+    constexpr bool kAllInFlight = !CHAIN && !(OPT != 5 && !FULL && U == 4);
+    if constexpr (kAllInFlight) {
+        // Every slot of a group loads its row, and every id of the next group is fetched, UNCONDITIONALLY: behind a branch
+        // (`if (g + u < cnt)`) the compiler cannot show a counted wait enough at the join and waits vmcnt(0) for each row before
+        // the next one's address -- one row in flight per item instead of U.  A slot past the item's end reads the list's last
+        // id (the row of an earlier slot: a cache hit), an empty list reads `idle`: nothing speculative leaves the item's list
+        // or the matrix.  The interactions stay predicated: the same sums in the same order.
+        const uint32_t last = cnt != 0u ? cnt - 1u : 0u;
+        const uint32_t *list = cnt != 0u ? ids : idle;
+        uint32_t j[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) j[u] = list[(uint32_t)u < last ? (uint32_t)u : last];
+        for (uint32_t g = 0; g < maxcnt; g += U) {
+            float4 xj[U][NB];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const float *src = row_src(a, j[u], D);
+#pragma unroll
+                for (int b = 0; b < NB; ++b) {
+                    if constexpr (FULL) {
+                        xj[u][b] = *reinterpret_cast<const float4 *>(src + t * 4 + 4 * LPI * b);
+                    } else {
+                        const bool live = 4u * LPI * b + 4u * t < D;  // (a dead piece reads the row's first 16 bytes and drops them)
+                        const float4 v = *reinterpret_cast<const float4 *>(src + (live ? t * 4 + 4 * LPI * b : 0u));
+                        xj[u][b] = live ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+                    }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const uint32_t k = g + U + u;
+                j[u] = list[k < last ? k : last];
+            }
+            // (keeps every load above the predicated interactions: left free, the compiler sinks row 0's loads into the first one's
+            // block, behind the others, and waits vmcnt(0) there -- for the next ids too)
+            asm volatile("" ::: "memory");
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (g + u < cnt) pair_update_q<OPT, LPI, NB, NEG>(xi, xj[u], Y, a.lr, c0, table);
+            }
+        }
+        return;
+    }
     uint32_t j[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) j[u] = ((uint32_t)u < cnt) ? ids[u] : 0u;
@@ -1111,7 +1158,8 @@ __device__ __forceinline__ void qstep_body(const StepArgs &a, const uint32_t blk
     }
 
     bool bad = false;  // chained minibatches: a wait for an earlier minibatch's row gave up -- this item stores nothing
-    qprocess<OPT, LPI, NB, false, U, FULL, CHAIN>(a, hs, a.nbr_ids + it.nb, it.cnt, wave_max_of_items<LPI>(it.cnt), t, D, xi, Y, c0, table, bad);
+    const uint32_t *idle = &a.items[active ? idx : IPW * w].row;  // (an empty list's stand-in id: this item's row, or the wave's first item's)
+    qprocess<OPT, LPI, NB, false, U, FULL, CHAIN>(a, hs, a.nbr_ids + it.nb, idle, it.cnt, wave_max_of_items<LPI>(it.cnt), t, D, xi, Y, c0, table, bad);
     if (lds_samples) {
         if (active && last_chunk) {
             for (uint32_t sidx = 0; sidx < a.ns; ++sidx) {
@@ -1124,7 +1172,7 @@ __device__ __forceinline__ void qstep_body(const StepArgs &a, const uint32_t blk
     } else {
         const uint32_t scnt = (active && last_chunk) ? a.ns : 0u;
         const uint32_t sbase = a.bs_mode ? (row - a.batch_lo) : 0u;
-        qprocess<OPT, LPI, NB, true, U, FULL, CHAIN>(a, hs, a.sample_ids + sbase, scnt, wave_max_of_items<LPI>(scnt), t, D, xi, Y, c0, table, bad);
+        qprocess<OPT, LPI, NB, true, U, FULL, CHAIN>(a, hs, a.sample_ids + sbase, idle, scnt, wave_max_of_items<LPI>(scnt), t, D, xi, Y, c0, table, bad);
     }
 
     if (CHAIN && __builtin_amdgcn_ballot_w64(bad) != 0ull) {
@@ -1758,7 +1806,7 @@ __global__ __launch_bounds__(256, (NB <= 2 && U <= 4) ? (MODE == 2 ? 2 : OPT == 
         } else {
             const uint32_t scnt = (!idle && last_chunk) ? a.ns : 0u;
             const uint32_t sbase = a.bs_mode ? (row - a.batch_lo) : 0u;
-            qprocess<OPT, LPI, NB, true, U, FULL, true>(a, hs, a.sample_ids + sbase, scnt, wave_max_of_items<LPI>(scnt), t, D, xi, Y, c0, table, bad);
+            qprocess<OPT, LPI, NB, true, U, FULL, true>(a, hs, a.sample_ids + sbase, nullptr, scnt, wave_max_of_items<LPI>(scnt), t, D, xi, Y, c0, table, bad);
         }
         const bool wave_bad = __builtin_amdgcn_ballot_w64(bad) != 0ull;  // (wave-uniform: a wave stores all its items or none)
         if (wave_bad) wg_bad = 1u;
@@ -2065,9 +2113,19 @@ __global__ __launch_bounds__(256, 5) void plan_gather_kernel(const float *X, flo
         if (idx < n_items) it[k] = items[idx];
         else { it[k].row = 0; it[k].nb = 0; it[k].cnt = 0; it[k].flags = 0; }
     }
+    // an item's list read as qprocess reads it: every slot loads, ids clamped to the list's last one, an empty list reads the
+    // item's own row id (a lane group past the plan's end: the last item's)
+    auto list_of = [&](int k) -> const uint32_t * {
+        const uint32_t idx = IPW * group_of(k) + q;
+        return it[k].cnt != 0u ? nbr_ids + it[k].nb : &items[idx < n_items ? idx : n_items - 1u].row;
+    };
+    auto last_of = [&](int k) { return it[k].cnt != 0u ? it[k].cnt - 1u : 0u; };
     uint32_t j[U];
+    {
+        const uint32_t *list = list_of(0), last = last_of(0);
 #pragma unroll
-    for (int u = 0; u < U; ++u) j[u] = ((uint32_t)u < it[0].cnt) ? nbr_ids[it[0].nb + u] : 0u;
+        for (int u = 0; u < U; ++u) j[u] = list[(uint32_t)u < last ? (uint32_t)u : last];
+    }
     float keep = 0.f;
 #pragma unroll
     for (int k = 0; k < G; ++k) {
@@ -2075,23 +2133,22 @@ __global__ __launch_bounds__(256, 5) void plan_gather_kernel(const float *X, flo
         float4 acc[NB];
 #pragma unroll
         for (int b = 0; b < NB; ++b) acc[b] = (mode & 1u) ? *reinterpret_cast<const float4 *>(X + (size_t)it[k].row * D + t * 4 + 4 * LPI * b) : make_float4(0.f, 0.f, 0.f, 0.f);
-        const uint32_t *ids = nbr_ids + it[k].nb;
+        const uint32_t *list = list_of(k), last = last_of(k);
+        const uint32_t *next = list_of(k + 1 < G ? k + 1 : k), next_last = last_of(k + 1 < G ? k + 1 : k);  // (the last group: unused)
         const uint32_t cnt = it[k].cnt, maxcnt = wave_max_of_items<LPI>(cnt);
         uint32_t g = 0;
         do {
             float4 xj[U][NB];
 #pragma unroll
             for (int u = 0; u < U; ++u)
-                if (g + u < cnt) {
 #pragma unroll
-                    for (int b = 0; b < NB; ++b) xj[u][b] = *reinterpret_cast<const float4 *>(X + (size_t)j[u] * D + t * 4 + 4 * LPI * b);
-                }
-            const bool last = g + U >= maxcnt;  // (uniform)
+                for (int b = 0; b < NB; ++b) xj[u][b] = *reinterpret_cast<const float4 *>(X + (size_t)j[u] * D + t * 4 + 4 * LPI * b);
+            const bool lastg = g + U >= maxcnt;  // (uniform)
+            const uint32_t *src = lastg ? next : list;
+            const uint32_t src_last = lastg ? next_last : last, base = lastg ? 0u : g + U;
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (last) j[u] = (k + 1 < G && (uint32_t)u < it[k + 1 < G ? k + 1 : k].cnt) ? nbr_ids[it[k + 1 < G ? k + 1 : k].nb + u] : 0u;
-                else j[u] = (g + U + u < cnt) ? ids[g + U + u] : 0u;
-            }
+            for (int u = 0; u < U; ++u) j[u] = src[base + u < src_last ? base + u : src_last];
+            asm volatile("" ::: "memory");  // (every load above the predicated sums, as in qprocess)
 #pragma unroll
             for (int u = 0; u < U; ++u)
                 if (g + u < cnt) {
