@@ -7,9 +7,14 @@ kernels + SGD row update).  Importing it never imports anything from oracle/.
 Training progress: `Engine.objective(option, ns=5)` evaluates the training objective (the
 reference's per-epoch loglike, defined in include/f2v.h) of the current matrix on the GPU;
 with `Engine.set_param("loss_every", k)` every f2v_train logs it after every k-th epoch and
-its last, read back with `Engine.train_losses()`."""
+its last, read back with `Engine.train_losses()`.
+
+Queries: `Engine.nearest(ids=..., k=10, metric="dot" | "l2" | "cos")` returns the k most similar rows of
+the matrix for each query (rows or caller-supplied vectors) without the matrix leaving the GPU;
+`Engine.neighbour_recall(k, metric)` is the graph-reconstruction precision@k."""
 from . import _lib  # noqa: F401
 from ._lib import F2VError  # noqa: F401
+from ._lib import NEAREST_EXCLUDE_NEIGHBOURS, NEAREST_EXCLUDE_SELF, NEAREST_MAX_K, NEAREST_PAD_ID, SIM_COSINE, SIM_DOT, SIM_L2  # noqa: F401
 from .engine import Engine, algorithms, output_name, push_masks, read_embd, read_embd_bin, sm_table, write_embd, write_embd_bin  # noqa: F401
 from .graph import read_csr_bin, read_mtx, rmat_csr, write_csr_bin  # noqa: F401
 

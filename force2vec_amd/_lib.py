@@ -10,6 +10,10 @@ SELFTEST_LIB_PATH = os.path.join(HERE, "libf2v_selftest.so")
 
 F2V_OK, F2V_EINVAL, F2V_ENODEV, F2V_ENOMEM, F2V_EIO, F2V_ESTATE = 0, -1, -2, -3, -4, -5
 INIT_SYMMETRIC, INIT_UNIT = 0, 1
+SIM_DOT, SIM_L2, SIM_COSINE = 0, 1, 2
+NEAREST_MAX_K = 128
+NEAREST_EXCLUDE_SELF, NEAREST_EXCLUDE_NEIGHBOURS = 1, 2
+NEAREST_PAD_ID = 0xFFFFFFFF  # id of a slot past the last candidate (its score is -inf)
 
 u32p = C.POINTER(C.c_uint32)
 f32p = C.POINTER(C.c_float)
@@ -61,6 +65,9 @@ SIGNATURES = {
     "f2v_train_marks": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_uint32, u32p]),
     "f2v_objective": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.POINTER(Objective)]),
     "f2v_train_losses": (C.c_int, [C.c_void_p, u32p, C.POINTER(C.c_double), C.c_uint32, u32p]),
+    "f2v_nearest_rows": (C.c_int, [C.c_void_p, u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, u32p, f32p, C.POINTER(C.c_double)]),
+    "f2v_nearest_vectors": (C.c_int, [C.c_void_p, f32p, C.c_uint32, C.c_uint32, C.c_int, u32p, f32p, C.POINTER(C.c_double)]),
+    "f2v_neighbour_recall": (C.c_int, [C.c_void_p, u32p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "f2v_push_export": (C.c_int, [C.c_void_p, C.c_void_p]),
     "f2v_push_attach": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "f2v_push_selftest": (C.c_int, [C.c_void_p]),

@@ -5,6 +5,7 @@
 // matrix lives in HBM; nothing here computes forces.
 #ifndef F2V_ALGORITHMS_HPP_
 #define F2V_ALGORITHMS_HPP_
+#include <algorithm>
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -68,7 +69,7 @@ class algorithms {
     int rank = 0, world = 1;         // > 1 after join_ranks: one process per GPU, minibatch rows sharded (f2v_train_sharded)
 
     algorithms(CSRGraph &A_csr, std::string input, std::string outputd, INDEXTYPE dim, VALUETYPE /*gamma*/, INDEXTYPE /*bsize*/, int device = 0)
-        : DIM(dim), rows(A_csr.rows), filename(input), outputdir(outputd) {
+        : DIM(dim), rows(A_csr.rows), filename(input), outputdir(outputd), csr_rowptr(A_csr.rowptr), csr_colids(A_csr.colids) {
         if (f2v_create(A_csr.rowptr, A_csr.colids, A_csr.rows, A_csr.nnz, dim, device, &h) != F2V_OK) throw std::runtime_error(f2v_last_error());
     }
     ~algorithms() { f2v_destroy(h); }
@@ -128,11 +129,51 @@ class algorithms {
         world = w;
     }
 
+    // -nearest <k>: every vertex's k nearest rows under `metric` (self excluded) as "<embd output name>.nn", one line per vertex
+    // "v j1 s1 ... jk sk" (0-based ids, scores %.9g, slots past the last candidate omitted), in query blocks through the same ABI
+    // as any other caller's; then the graph-reconstruction precision@k.  Call after a run (last_output names the .embd file).
+    std::string last_output;
+    void writeNearest(uint32_t k, int metric, const char *metric_name) {
+        const std::string name = last_output + ".nn";
+        FILE *f = fopen(name.c_str(), "w");
+        if (!f) throw std::runtime_error("cannot write " + name);
+        const uint32_t block = 65536;
+        std::vector<uint32_t> q(block), ids((size_t)block * k);
+        std::vector<float> scores((size_t)block * k);
+        double seconds = 0.0, sec = 0.0;
+        uint64_t hits = 0, possible = 0;
+        for (uint32_t lo = 0; lo < rows; lo += block) {
+            const uint32_t cnt = rows - lo < block ? rows - lo : block;
+            for (uint32_t i = 0; i < cnt; i++) q[i] = lo + i;
+            if (f2v_nearest_rows(h, q.data(), cnt, k, metric, F2V_NEAREST_EXCLUDE_SELF, ids.data(), scores.data(), &sec) != F2V_OK) {
+                fclose(f);
+                throw std::runtime_error(f2v_last_error());
+            }
+            seconds += sec;
+            for (uint32_t i = 0; i < cnt; i++) {
+                // precision@k from the ids in hand, as f2v_neighbour_recall defines it (a second sweep would only repeat the scoring)
+                const uint32_t v = lo + i, *nb = csr_colids + csr_rowptr[v], deg = csr_rowptr[v + 1] - csr_rowptr[v];
+                uint32_t distinct = 0;
+                for (uint32_t p = 0; p < deg && distinct < k; p++)
+                    if (nb[p] != v && (p == 0 || nb[p - 1] != nb[p])) distinct++;
+                possible += distinct;
+                for (uint32_t j = 0; j < k && ids[(size_t)i * k + j] != 0xFFFFFFFFu; j++)
+                    if (std::binary_search(nb, nb + deg, ids[(size_t)i * k + j])) hits++;
+                fprintf(f, "%u", lo + i);
+                for (uint32_t j = 0; j < k && ids[(size_t)i * k + j] != 0xFFFFFFFFu; j++) fprintf(f, " %u %.9g", ids[(size_t)i * k + j], scores[(size_t)i * k + j]);
+                fputc('\n', f);
+            }
+        }
+        if (fclose(f) != 0) throw std::runtime_error("cannot write " + name);
+        printf("Nearest: k=%u metric=%s %.6f s, precision@k %llu/%llu\n", k, metric_name, seconds, (unsigned long long)hits, (unsigned long long)possible);
+    }
+
     // writeToFile, sample/algorithms.h:118-136 (file name rule in f2v_output_name)
     void writeToFile(int option, int bs, INDEXTYPE B, INDEXTYPE IT, INDEXTYPE ns) {
         char name[4096];
         check(f2v_output_name(filename.c_str(), outputdir.c_str(), option, bs, B, DIM, IT, ns, name, sizeof name));
         std::cout << "Creating output file in following directory:" << name << std::endl;
+        last_output = name;
         std::vector<float> x((size_t)rows * DIM);
         check(f2v_get_embeddings(h, x.data()));
         if (text_output) check(f2v_write_embd(name, x.data(), rows, DIM));
@@ -140,6 +181,7 @@ class algorithms {
     }
 
    private:
+    const INDEXTYPE *csr_rowptr, *csr_colids;  // the caller's graph (it outlives this object): writeNearest counts hits in it
     unsigned last_seed = 1;
     bool seeded = false;  // srand() was the last thing to touch the handle's rand() stream: a lost run can be repeated from it
     static void check(int rc) {

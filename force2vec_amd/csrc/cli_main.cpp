@@ -7,7 +7,9 @@
 // (NON-parity fast mode: device-side initial embeddings and option-7 walks), -gpus <n> (one forked process per GPU,
 // devices -device .. -device+n-1: every minibatch's rows sharded over them, new rows pushed over xGMI --
 // f2v_train_sharded; the ranks meet through files in a private temporary directory; same output, written by rank 0),
-// -loss <k> (print the training objective after every k-th epoch and the last, in the line the reference has commented out).
+// -loss <k> (print the training objective after every k-th epoch and the last, in the line the reference has commented out),
+// -nearest <k> [-metric dot|l2|cos] (after training: every vertex's k nearest rows as "<embd output name>.nn" and the
+// graph-reconstruction precision@k; default metric: the option's own similarity).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -28,7 +30,8 @@ namespace {
 struct Settings {
     std::string input, output, init;
     long batch = 384, iter = 1200, threads = (long)std::thread::hardware_concurrency(), dim = 128, nsamples = 5, option = 5, bs = 0;
-    long device = 0, seed = 1, cache = 0, binout = 0, fastrng = 0, notext = 0, gpus = 1, samegpu = 0, loss = 0;
+    long device = 0, seed = 1, cache = 0, binout = 0, fastrng = 0, notext = 0, gpus = 1, samegpu = 0, loss = 0, nearest = 0;
+    std::string metric;
     double gamma = 1.0, lr = 0.02;
 };
 
@@ -91,6 +94,8 @@ int main(int argc, char *argv[]) {
         {"-samegpu", Kind::Integer, &s.samegpu, "<int>, 1 = all ranks of a -gpus run on device -device (self-test on a one-GPU machine)."},
         {"-fastrng", Kind::Integer, &s.fastrng, "<int>, 1 = NON-PARITY fast mode: initial embeddings and option-7 walks from a device-side RNG."},
         {"-loss", Kind::Integer, &s.loss, "<int>, k > 0: print \"Iteration:<epoch> :LOGLIKELIHOOD: <loss>\" after every k-th epoch and the last (the training objective, include/f2v.h; one GPU). (default:0)"},
+        {"-nearest", Kind::Integer, &s.nearest, "<int>, k in 1..128: after training write <output file>.nn, one line per vertex \"v j1 s1 ... jk sk\" (its k nearest rows, self excluded), and print the precision@k against the graph (one GPU). (default:0)"},
+        {"-metric", Kind::Text, &s.metric, "<string>, similarity of -nearest: dot | l2 | cos. (default: l2 for options 5, 8, 11, dot for the sigmoid options)"},
     };
     const size_t nflags = sizeof flags / sizeof flags[0];
     for (int p = 1; p < argc; p++) {
@@ -134,6 +139,20 @@ int main(int argc, char *argv[]) {
         printf("-loss is not available with -gpus > 1 (a rank does not hold the whole matrix between minibatches).\n");
         return 1;
     }
+    if (s.nearest < 0 || s.nearest > F2V_NEAREST_MAX_K) {
+        printf("-nearest must be 0..%d.\n", F2V_NEAREST_MAX_K);
+        return 1;
+    }
+    if (s.metric.empty()) s.metric = (s.option == 5 || s.option == 8 || s.option == 11) ? "l2" : "dot";
+    const int metric = s.metric == "dot" ? F2V_SIM_DOT : s.metric == "l2" ? F2V_SIM_L2 : s.metric == "cos" ? F2V_SIM_COSINE : -1;
+    if (metric < 0) {
+        printf("-metric must be dot, l2 or cos.\n");
+        return 1;
+    }
+    if (s.nearest > 0 && s.gpus > 1) {
+        printf("-nearest is not available with -gpus > 1 (it queries one GPU's matrix).\n");
+        return 1;
+    }
     std::vector<VALUETYPE> seconds;
     int rank = 0;
     std::string meet;  // directory the ranks of a -gpus run meet in
@@ -175,6 +194,7 @@ int main(int argc, char *argv[]) {
                 if (f2v_train_losses(algo.h, epochs.data(), values.data(), count, &count) != F2V_OK) throw std::runtime_error(f2v_last_error());
                 for (uint32_t m = 0; m < count; m++) std::cout << "Iteration:" << epochs[m] << " :LOGLIKELIHOOD: " << values[3 * m] << std::endl;
             }
+            if (s.nearest > 0 && rank == 0) algo.writeNearest((uint32_t)s.nearest, metric, s.metric.c_str());
             const double t = algo.gpu_train_seconds;
             if (rank == 0 && s.gpus == 1)
                 printf("GPU epoch loop: %.6f s, %.4g nnz/s, %.1f GB/s algorithmic\n", t, t > 0 ? algo.stats.nnz / t : 0.0,

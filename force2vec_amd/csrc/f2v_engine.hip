@@ -32,6 +32,7 @@
 #endif
 #include "f2v_internal.h"
 #include "f2v_kernels.hip.h"
+#include "f2v_nearest.hip.h"
 
 using namespace f2v;
 
@@ -149,6 +150,18 @@ struct f2v_ctx {
     double last_loss_us = 0.0;                    // "last_loss_us"
     std::vector<uint32_t> loss_epochs;            // f2v_train_losses
     std::vector<double> loss_values;              // ... loss, attraction, repulsion per entry
+    // nearest-neighbour queries (f2v_nearest_rows / _vectors, f2v_neighbour_recall): buffers of one query chunk, allocated on first
+    // use and grown on demand; "nearest_splits" (0 = from nq and N), "nearest_block" (0 = from D and nq | 32 | 128), "nearest_chunk"
+    struct Nearest {
+        float *d_Q = nullptr, *d_rq = nullptr, *d_rc = nullptr, *d_scores = nullptr;
+        uint32_t *d_qids = nullptr, *d_ids = nullptr;
+        unsigned long long *d_ws = nullptr, *d_counts = nullptr;
+        size_t q_cap = 0, ws_cap = 0, out_cap = 0;  // queries d_Q / d_rq / d_qids hold, keys d_ws holds, slots d_ids / d_scores hold
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        uint32_t splits = 0, block = 0, chunk = 8192;
+        uint32_t lds_allowed = 0;  // nearest_kernel instantiations whose dynamic-LDS limit has been raised (launch_nearest_t)
+        int rows_sorted = -1;      // the CSR's ids ascend inside every row: -1 not checked yet (nearest_enter)
+    } nn;
     uint32_t last_wide_width = 0;  // the layout width of the last wide-form f2v_train ("last_wide_width")
     bool last_wide_early = false;  // ... and whether it ran the kernel's EARLY form ("last_wide_early")
     int last_train_form = 0;  // how the last f2v_train launched: 0 one launch per minibatch, 1 chained, 2 chained in the wide form ("last_train_form")
@@ -2062,7 +2075,8 @@ int f2v_destroy(f2v_handle c) {
     (void)hipSetDevice(c->device);
     (void)push_detach(c);
     void *ptrs[] = {c->d_rowptr, c->d_colids, c->d_walks, c->d_walks_alt, c->d_ids, c->d_X[0], c->d_X[1],
-                    c->d_partials, c->d_table, c->d_items, c->d_hubs, c->d_ready, c->d_kerr, c->d_wg, c->d_rowflag, c->d_snap, c->d_wide, c->d_jobs, c->d_ring, c->d_ring_partials, c->d_ring_flags, c->d_ring_ready, c->d_obj_items, c->d_obj_part, c->d_obj_out, c->push.flags, c->push.d_err, c->push.d_masks, c->push.d_patch, c->push.landing_buf};
+                    c->d_partials, c->d_table, c->d_items, c->d_hubs, c->d_ready, c->d_kerr, c->d_wg, c->d_rowflag, c->d_snap, c->d_wide, c->d_jobs, c->d_ring, c->d_ring_partials, c->d_ring_flags, c->d_ring_ready, c->d_obj_items, c->d_obj_part, c->d_obj_out, c->push.flags, c->push.d_err, c->push.d_masks, c->push.d_patch, c->push.landing_buf,
+                    c->nn.d_Q, c->nn.d_rq, c->nn.d_rc, c->nn.d_scores, c->nn.d_qids, c->nn.d_ids, c->nn.d_ws, c->nn.d_counts};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
 #ifdef F2V_TEST_HOOKS
@@ -2071,6 +2085,8 @@ int f2v_destroy(f2v_handle c) {
 #endif
     if (c->h_kerr) (void)hipHostFree(c->h_kerr);
     for (hipEvent_t e : c->ev_snap)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->nn.ev)
         if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -2378,6 +2394,22 @@ int f2v_set_param(f2v_handle c, const char *name, int64_t value) {
         c->loss_seed = (uint64_t)value;
         return F2V_OK;
     }
+    if (!strcmp(name, "nearest_splits")) {  // candidate ranges a query block's work is cut into (0: chosen from nq and N); results do not depend on it
+        if (value < 0 || value > 256) return fail(F2V_EINVAL, "nearest_splits must be 0..256");
+        c->nn.splits = (uint32_t)value;
+        return F2V_OK;
+    }
+    if (!strcmp(name, "nearest_block")) {  // queries per workgroup (0: 128 where D <= 128 and more than 32 queries share a launch, else 32)
+        if (value != 0 && value != 32 && value != 128) return fail(F2V_EINVAL, "nearest_block must be 0, 32 or 128");
+        if (value == 128 && c->D > 128) return fail(F2V_EINVAL, "nearest_block = 128 needs dim <= 128 (the query block lives in LDS)");
+        c->nn.block = (uint32_t)value;
+        return F2V_OK;
+    }
+    if (!strcmp(name, "nearest_chunk")) {  // queries per launch: bounds the workspace (chunk x splits x k keys)
+        if (value < 1 || value > 65536) return fail(F2V_EINVAL, "nearest_chunk must be 1..65536");
+        c->nn.chunk = (uint32_t)value;
+        return F2V_OK;
+    }
     if (!strcmp(name, "chain_timeout_ms")) {
         if (value < 1 || value > 600000) return fail(F2V_EINVAL, "chain_timeout_ms must be 1..600000");
         c->chain_timeout_ms = value;
@@ -2440,6 +2472,9 @@ int f2v_get_param(f2v_handle c, const char *name, int64_t *out) {
     if (!strcmp(name, "epoch_marks")) { *out = c->mark_every; return F2V_OK; }
     if (!strcmp(name, "loss_every")) { *out = c->loss_every; return F2V_OK; }
     if (!strcmp(name, "loss_seed")) { *out = (int64_t)c->loss_seed; return F2V_OK; }
+    if (!strcmp(name, "nearest_splits")) { *out = c->nn.splits; return F2V_OK; }
+    if (!strcmp(name, "nearest_block")) { *out = c->nn.block; return F2V_OK; }
+    if (!strcmp(name, "nearest_chunk")) { *out = c->nn.chunk; return F2V_OK; }
     if (!strcmp(name, "last_loss_us")) { *out = (int64_t)(c->last_loss_us + 0.5); return F2V_OK; }
     if (!strcmp(name, "wide_phases")) { *out = c->wide_phases; return F2V_OK; }
     if (!strcmp(name, "wide_max_batch")) { *out = c->wide_max_batch; return F2V_OK; }
@@ -3245,9 +3280,201 @@ int train_impl(f2v_ctx *c, int option, uint32_t iters, uint32_t batch, uint32_t 
     return F2V_OK;
 }
 
+// ---- nearest-neighbour queries (f2v_nearest.hip.h; definition in include/f2v.h) -------------------------------------------------
+template <bool L2, int WQ, int MI, int NI>
+int launch_nearest_t(f2v_ctx *c, const NnArgs &a, uint32_t qblocks, uint32_t splits) {
+    const size_t lds = nn_lds_bytes(32u * WQ * MI, a.D);
+    const uint32_t form = 1u << ((L2 ? 2 : 0) + (WQ == 2 ? 1 : 0));
+    if (!(c->nn.lds_allowed & form)) {  // more than 64 KB of dynamic LDS has to be allowed once per kernel (D is fixed per handle)
+        HIPC(hipFuncSetAttribute(reinterpret_cast<const void *>(&nearest_kernel<L2, WQ, MI, NI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        c->nn.lds_allowed |= form;
+    }
+    hipLaunchKernelGGL((nearest_kernel<L2, WQ, MI, NI>), dim3(qblocks, splits), dim3(kNnThreads), lds, c->stream, a);
+    HIPC(hipGetLastError());
+    return F2V_OK;
+}
+
+template <class T>
+int nn_grow(f2v_ctx *c, T *&p, size_t count) {
+    HIPC(hipStreamSynchronize(c->stream));
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    hipError_t e = hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T));
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? F2V_ENOMEM : F2V_ENODEV, "nearest-neighbour workspace: %s", hipGetErrorString(e));
+    return F2V_OK;
+}
+
+// What the three entry points share behind their preamble.  Queries are rows `qids` of the matrix (nullptr with `all`: rows 0 .. nq-1)
+// or the host vectors `vecs`; they are run in chunks of "nearest_chunk" queries, each chunk as gather / norms / nearest_kernel /
+// merge (/ count) on the handle's stream between two events.  ids_out / scores_out may be nullptr (the recall count needs neither).
+int nearest_run(f2v_ctx *c, const uint32_t *qids, bool all, const float *vecs, uint32_t nq, uint32_t k, int metric, uint32_t flags,
+                uint32_t *ids_out, float *scores_out, uint64_t *recall_out, double *seconds_out) {
+    f2v_ctx::Nearest &w = c->nn;
+    const float *X = c->d_X[c->cur];
+    const uint32_t D = c->D, n = c->n;
+    const bool rows = qids || all, cosine = metric == F2V_SIM_COSINE;
+    int rc;
+    for (hipEvent_t &e : w.ev)
+        if (!e) HIPC(hipEventCreate(&e));
+    if (!w.d_counts) HIPC(hipMalloc((void **)&w.d_counts, 2 * sizeof(unsigned long long)));
+    if (recall_out) HIPC(hipMemsetAsync(w.d_counts, 0, 2 * sizeof(unsigned long long), c->stream));
+    if (cosine && !w.d_rc && (rc = nn_grow(c, w.d_rc, n)) != F2V_OK) return rc;
+    const uint32_t tiles = (n + kNnTile - 1) / kNnTile;
+    double seconds = 0.0;
+    std::vector<uint32_t> iota;
+    for (uint32_t done = 0; done < nq; done += w.chunk) {
+        const uint32_t cq = std::min(w.chunk, nq - done);
+        const uint32_t qb = w.block ? w.block : (D <= 128 && cq > 32 ? 128u : 32u);
+        const uint32_t qblocks = (cq + qb - 1) / qb;
+        uint32_t splits = w.splits;
+        if (!splits)  // enough workgroups for every CU a few times over, but never more keys per query than the merge reads quickly
+            splits = std::min({(1024u + qblocks - 1) / qblocks, std::max(1u, 8192u / k), 256u});
+        splits = std::min(splits, tiles);
+        const uint32_t tps = (tiles + splits - 1) / splits;
+        splits = (tiles + tps - 1) / tps;
+        if (w.q_cap < cq) {
+            if ((rc = nn_grow(c, w.d_Q, (size_t)cq * D)) != F2V_OK || (rc = nn_grow(c, w.d_rq, cq)) != F2V_OK || (rc = nn_grow(c, w.d_qids, cq)) != F2V_OK) return rc;
+            w.q_cap = cq;
+        }
+        const size_t keys = (size_t)qblocks * qb * splits * k, slots = (size_t)cq * k;
+        if (w.ws_cap < keys) {
+            if ((rc = nn_grow(c, w.d_ws, keys)) != F2V_OK) return rc;
+            w.ws_cap = keys;
+        }
+        if (w.out_cap < slots) {
+            if ((rc = nn_grow(c, w.d_ids, slots)) != F2V_OK || (rc = nn_grow(c, w.d_scores, slots)) != F2V_OK) return rc;
+            w.out_cap = slots;
+        }
+        if (all) {
+            iota.resize(cq);
+            for (uint32_t i = 0; i < cq; i++) iota[i] = done + i;
+        }
+        if (rows) HIPC(hipMemcpyAsync(w.d_qids, all ? iota.data() : qids + done, (size_t)cq * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        else HIPC(hipMemcpyAsync(w.d_Q, vecs + (size_t)done * D, (size_t)cq * D * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        HIPC(hipEventRecord(w.ev[0], c->stream));
+        if (rows) hipLaunchKernelGGL(nearest_gather_kernel, dim3(std::min<size_t>(((size_t)cq * D + 255) / 256, 4096)), dim3(256), 0, c->stream, X, (const uint32_t *)w.d_qids, cq, D, w.d_Q);
+        if (cosine) {
+            if (done == 0) hipLaunchKernelGGL(nearest_rnorm_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, X, n, D, w.d_rc);
+            hipLaunchKernelGGL(nearest_rnorm_kernel, dim3((cq + 255) / 256), dim3(256), 0, c->stream, (const float *)w.d_Q, cq, D, w.d_rq);
+        }
+        HIPC(hipGetLastError());
+        NnArgs a{};
+        a.X = X;
+        a.Q = w.d_Q;
+        a.rq = cosine ? w.d_rq : nullptr;
+        a.rc = cosine ? w.d_rc : nullptr;
+        a.qids = rows ? w.d_qids : nullptr;
+        a.rowptr = c->d_rowptr;
+        a.colids = c->d_colids;
+        a.ws = w.d_ws;
+        a.n = n;
+        a.D = D;
+        a.nq = cq;
+        a.k = k;
+        a.flags = flags;
+        a.splits = splits;
+        a.tiles_per_split = tps;
+        a.cosine = cosine ? 1u : 0u;
+        if (metric == F2V_SIM_L2) rc = qb == 128 ? launch_nearest_t<true, 2, 2, 2>(c, a, qblocks, splits) : launch_nearest_t<true, 1, 1, 1>(c, a, qblocks, splits);
+        else rc = qb == 128 ? launch_nearest_t<false, 2, 2, 2>(c, a, qblocks, splits) : launch_nearest_t<false, 1, 1, 1>(c, a, qblocks, splits);
+        if (rc != F2V_OK) return rc;
+        hipLaunchKernelGGL(nearest_merge_kernel, dim3(cq), dim3(256), 0, c->stream, (const nn_key_t *)w.d_ws, splits, k, w.d_ids, w.d_scores);
+        if (recall_out)
+            hipLaunchKernelGGL(nearest_recall_kernel, dim3((cq + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)w.d_ids, (const uint32_t *)w.d_qids, cq, k,
+                               (const uint32_t *)c->d_rowptr, (const uint32_t *)c->d_colids, w.d_counts);
+        HIPC(hipGetLastError());
+        HIPC(hipEventRecord(w.ev[1], c->stream));
+        if (ids_out) HIPC(hipMemcpyAsync(ids_out + (size_t)done * k, w.d_ids, slots * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (scores_out) HIPC(hipMemcpyAsync(scores_out + (size_t)done * k, w.d_scores, slots * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+        float ms = 0.f;
+        HIPC(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
+        seconds += ms * 1e-3;
+    }
+    if ((rc = check_kernel_err(c, "nearest-neighbour query")) != F2V_OK) return rc;
+    if (recall_out) {
+        HIPC(hipMemcpyAsync(recall_out, w.d_counts, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+    }
+    if (seconds_out) *seconds_out = seconds;
+    return F2V_OK;
+}
+
+// The entry points' common argument and state checks (f2v_objective's preamble).  -> 1: nq == 0, nothing to do and nothing touched.
+// `by_row`: the call searches CSR rows (EXCLUDE_NEIGHBOURS, the recall count), which needs their ids ascending -- f2v_create documents
+// that order but no earlier kernel depended on it, so it is verified here, once per handle, on the host copy.
+int nearest_enter(f2v_ctx *c, const char *who, uint32_t nq, uint32_t k, int metric, uint32_t flags, bool by_row) {
+    if (c->n >= 0xFFFFFFFFu - kNnTile) return fail(F2V_EINVAL, "%s: too many vertices for 32-bit candidate tiles", who);
+    if (k == 0 || k > F2V_NEAREST_MAX_K) return fail(F2V_EINVAL, "%s: k = %u is outside 1..%d", who, k, F2V_NEAREST_MAX_K);
+    if (metric != F2V_SIM_DOT && metric != F2V_SIM_L2 && metric != F2V_SIM_COSINE) return fail(F2V_EINVAL, "%s: unknown metric %d", who, metric);
+    if (flags & ~(F2V_NEAREST_EXCLUDE_SELF | F2V_NEAREST_EXCLUDE_NEIGHBOURS)) return fail(F2V_EINVAL, "%s: unknown flag in 0x%x", who, flags);
+    if (by_row) {
+        if (c->nn.rows_sorted < 0) {
+            c->nn.rows_sorted = 1;
+            for (uint32_t r = 0; r < c->n && c->nn.rows_sorted; r++)
+                for (uint32_t p = c->rowptr[r] + 1; p < c->rowptr[r + 1]; p++)
+                    if (c->colids[p] < c->colids[p - 1]) { c->nn.rows_sorted = 0; break; }
+        }
+        if (!c->nn.rows_sorted) return fail(F2V_EINVAL, "%s: the CSR's column ids are not ascending inside every row (needed to search a row)", who);
+    }
+    if (!c->have_x)
+        return fail(F2V_ESTATE, c->x_invalid ? "%s: the embeddings are invalid since a launch gave up a bounded wait: set or initialise them again"
+                                             : "%s: embeddings were never initialised", who);
+    if (nq == 0) return 1;
+    HIPC(hipSetDevice(c->device));
+    return flush_pending(c);
+}
+
 }  // namespace
 
 extern "C" {
+
+int f2v_nearest_rows(f2v_handle c, const uint32_t *query_ids, uint32_t nq, uint32_t k, int metric, uint32_t flags, uint32_t *ids_out,
+                     float *scores_out, double *seconds_out) {
+    if (!c || (nq && (!query_ids || !ids_out))) return fail(F2V_EINVAL, "f2v_nearest_rows: null argument");
+    for (uint32_t i = 0; i < nq; i++)
+        if (query_ids[i] >= c->n) return fail(F2V_EINVAL, "f2v_nearest_rows: query_ids[%u] = %u is not a vertex", i, query_ids[i]);
+    int rc = nearest_enter(c, "f2v_nearest_rows", nq, k, metric, flags, (flags & F2V_NEAREST_EXCLUDE_NEIGHBOURS) != 0);
+    if (rc == 1) {
+        if (seconds_out) *seconds_out = 0.0;
+        return F2V_OK;
+    }
+    if (rc != F2V_OK) return rc;
+    return nearest_run(c, query_ids, false, nullptr, nq, k, metric, flags, ids_out, scores_out, nullptr, seconds_out);
+}
+
+int f2v_nearest_vectors(f2v_handle c, const float *queries, uint32_t nq, uint32_t k, int metric, uint32_t *ids_out, float *scores_out,
+                        double *seconds_out) {
+    if (!c || (nq && (!queries || !ids_out))) return fail(F2V_EINVAL, "f2v_nearest_vectors: null argument");
+    int rc = nearest_enter(c, "f2v_nearest_vectors", nq, k, metric, 0, false);
+    if (rc == 1) {
+        if (seconds_out) *seconds_out = 0.0;
+        return F2V_OK;
+    }
+    if (rc != F2V_OK) return rc;
+    return nearest_run(c, nullptr, false, queries, nq, k, metric, 0, ids_out, scores_out, nullptr, seconds_out);
+}
+
+int f2v_neighbour_recall(f2v_handle c, const uint32_t *query_ids, uint32_t nq, uint32_t k, int metric, uint64_t *hits_out,
+                         uint64_t *possible_out, double *seconds_out) {
+    if (!c || !hits_out || !possible_out) return fail(F2V_EINVAL, "f2v_neighbour_recall: null argument");
+    if (!query_ids) nq = c->n;
+    for (uint32_t i = 0; query_ids && i < nq; i++)
+        if (query_ids[i] >= c->n) return fail(F2V_EINVAL, "f2v_neighbour_recall: query_ids[%u] = %u is not a vertex", i, query_ids[i]);
+    int rc = nearest_enter(c, "f2v_neighbour_recall", nq, k, metric, 0, true);
+    if (rc == 1) {  // no queries: 0 of 0
+        *hits_out = *possible_out = 0;
+        if (seconds_out) *seconds_out = 0.0;
+        return F2V_OK;
+    }
+    if (rc != F2V_OK) return rc;
+    uint64_t counts[2] = {0, 0};
+    rc = nearest_run(c, query_ids, !query_ids, nullptr, nq, k, metric, F2V_NEAREST_EXCLUDE_SELF, nullptr, nullptr, counts, seconds_out);
+    if (rc != F2V_OK) return rc;
+    *hits_out = counts[0];
+    *possible_out = counts[1];
+    return F2V_OK;
+}
 
 int f2v_push_export(f2v_handle c, void *handles_out) {
     if (!c || !handles_out) return fail(F2V_EINVAL, "f2v_push_export: null argument");

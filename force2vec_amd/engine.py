@@ -20,6 +20,9 @@ from ._lib import INIT_SYMMETRIC, INIT_UNIT, check
 Objective = namedtuple("Objective", "loss attraction repulsion positive_pairs negative_pairs")
 
 
+METRICS = {"dot": _lib.SIM_DOT, "l2": _lib.SIM_L2, "cos": _lib.SIM_COSINE, "cosine": _lib.SIM_COSINE}
+
+
 def _u32(a):
     return a.ctypes.data_as(_lib.u32p)
 
@@ -221,6 +224,44 @@ class Engine:
         values = np.zeros((max(n.value, 1), 3), dtype=np.float64)
         self._ck(self._L.f2v_train_losses(self._h, _u32(epochs), values.ctypes.data_as(C.POINTER(C.c_double)), n.value, C.byref(n)))
         return epochs[: n.value], values[: n.value]
+
+    # -- nearest neighbours (include/f2v.h: definition; a function of the matrix, the metric, k and the flags alone) --------------
+    def nearest(self, ids=None, vectors=None, k=10, metric="dot", exclude_self=True, exclude_neighbours=False):
+        """The k most similar rows of the matrix for each query -> (ids uint32 [nq, k], scores float32 [nq, k]).  Queries are
+        the rows `ids` (default: all vertices) or the float32 `vectors` [nq, dim]; the two exclusions apply to rows only.
+        metric: "dot" | "l2" | "cos".  Slots past the last candidate hold id 0xFFFFFFFF and score -inf.  `last_nearest_seconds`
+        keeps the device time."""
+        m = METRICS[metric] if isinstance(metric, str) else int(metric)
+        sec = C.c_double()
+        if vectors is not None:
+            if ids is not None:
+                raise ValueError("nearest: give ids or vectors, not both")
+            q = np.ascontiguousarray(vectors, dtype=np.float32)
+            if q.ndim != 2 or q.shape[1] != self.dim:
+                raise ValueError("nearest: vectors must be [nq, %d]" % self.dim)
+            nq = q.shape[0]
+            out_ids, out_scores = np.empty((nq, k), dtype=np.uint32), np.empty((nq, k), dtype=np.float32)
+            self._ck(self._L.f2v_nearest_vectors(self._h, _f32(q), nq, k, m, _u32(out_ids), _f32(out_scores), C.byref(sec)))
+        else:
+            q = np.arange(self.n, dtype=np.uint32) if ids is None else np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+            flags = (_lib.NEAREST_EXCLUDE_SELF if exclude_self else 0) | (_lib.NEAREST_EXCLUDE_NEIGHBOURS if exclude_neighbours else 0)
+            out_ids, out_scores = np.empty((len(q), k), dtype=np.uint32), np.empty((len(q), k), dtype=np.float32)
+            self._ck(self._L.f2v_nearest_rows(self._h, _u32(q), len(q), k, m, flags, _u32(out_ids), _f32(out_scores), C.byref(sec)))
+        self.last_nearest_seconds = sec.value
+        return out_ids, out_scores
+
+    def neighbour_recall(self, k=10, metric="dot", ids=None):
+        """Graph-reconstruction precision@k, counted on the device -> (hits, possible): how many of the vertices' top-k (self
+        excluded) are their CSR neighbours, out of sum min(k, distinct neighbours).  ids=None: all vertices."""
+        m = METRICS[metric] if isinstance(metric, str) else int(metric)
+        hits, possible, sec = C.c_uint64(), C.c_uint64(), C.c_double()
+        if ids is None:
+            self._ck(self._L.f2v_neighbour_recall(self._h, None, 0, k, m, C.byref(hits), C.byref(possible), C.byref(sec)))
+        else:
+            q = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+            self._ck(self._L.f2v_neighbour_recall(self._h, _u32(q), len(q), k, m, C.byref(hits), C.byref(possible), C.byref(sec)))
+        self.last_nearest_seconds = sec.value
+        return hits.value, possible.value
 
     def stats(self):
         s = _lib.Stats()

@@ -301,6 +301,49 @@ F2V_API int f2v_objective(f2v_handle h, int option, uint32_t ns, f2v_objective_t
  * of scope). */
 F2V_API int f2v_train_losses(f2v_handle h, uint32_t *epochs_out, double *values_out, uint32_t cap, uint32_t *count_out);
 
+/* ---- nearest neighbours ---------------------------------------------------------------------------------------------------
+ * Which rows of the matrix are most similar to a query?  Three similarities between a query vector q and row c of the matrix, all
+ * fp32, all "larger is nearer".  fma(a, b, acc) is one correctly rounded fp32 fused multiply-add; a chain starts from +0 and runs
+ * over d = 0 .. D-1 in ascending order:
+ *   F2V_SIM_DOT     s = chain_d fma(q_d, c_d, acc);
+ *   F2V_SIM_L2      s = -chain_d fma(t_d, t_d, acc), t_d = q_d - c_d (one rounded subtraction) -- always from differences, never
+ *                   |q|^2 + |c|^2 - 2 q.c: that form cancels for exactly the pairs a nearest-neighbour query is about;
+ *   F2V_SIM_COSINE  s = (dot * r_q) * r_c (two rounded multiplications), dot as above, r_v = 1 / sqrt(n_v), n_v = chain_d fma(v_d, v_d,
+ *                   acc), square root and division correctly rounded, r_v = 0 where n_v == 0.
+ * Subnormals are kept.  Ranking is a strict total order: score descending (-0 and +0 are one score), equal scores by ascending
+ * vertex id, a NaN score below every number (NaNs among themselves by ascending id).  A query's result is the first k candidates of
+ * that order after the exclusions; where fewer than k are left the tail holds id 0xFFFFFFFF and score -inf.  The result is a function
+ * of the matrix, the metric, k and the flags alone: never of how many queries share a call, of "nearest_splits" / "nearest_block" /
+ * "nearest_chunk" (f2v_set_param), of the handle or of the order in which workgroups run.  dot and cosine are computed by the fp32
+ * matrix instruction v_mfma_f32_32x32x2_f32, whose accumulator is that very chain; L2 by the vector ALU.
+ * All three work on the matrix as f2v_get_embeddings would return it (pending minibatches are committed first), run on the
+ * handle's stream behind whatever training was enqueued, and change neither the matrices nor the rand() stream nor any later
+ * training result.  Any nq: queries run in chunks of "nearest_chunk" (default 8192); the N x nq scores are never stored, the
+ * workspace is chunk x splits x k keys, allocated on first use and freed by f2v_destroy.  seconds_out (may be NULL): device time
+ * between events around the query's own launches, uploads and downloads excluded.  On a handle attached to a push exchange it reads
+ * this rank's replica; nothing is exchanged.
+ * F2V_ESTATE without valid embeddings; F2V_EINVAL for null pointers, k = 0 or k > F2V_NEAREST_MAX_K, an unknown metric or flag, a query
+ * id >= n, and -- for F2V_NEAREST_EXCLUDE_NEIGHBOURS and f2v_neighbour_recall, which search CSR rows -- a CSR whose column ids
+ * are not ascending inside every row (the order f2v_create documents; checked once per handle).  nq = 0 is F2V_OK and touches
+ * nothing: no launch, no commit of pending minibatches. */
+#define F2V_SIM_DOT 0
+#define F2V_SIM_L2 1
+#define F2V_SIM_COSINE 2
+#define F2V_NEAREST_MAX_K 128
+#define F2V_NEAREST_EXCLUDE_SELF 1u       /* drop the query vertex itself */
+#define F2V_NEAREST_EXCLUDE_NEIGHBOURS 2u /* drop the query vertex's CSR neighbours ("similar, but not linked yet") */
+/* Queries are rows of the matrix.  ids_out: nq x k; scores_out: nq x k, may be NULL. */
+F2V_API int f2v_nearest_rows(f2v_handle h, const uint32_t *query_ids, uint32_t nq, uint32_t k, int metric, uint32_t flags, uint32_t *ids_out,
+                     float *scores_out, double *seconds_out);
+/* Queries are caller-supplied vectors, nq x D fp32 on the host (there is no query vertex, hence no flags). */
+F2V_API int f2v_nearest_vectors(f2v_handle h, const float *queries, uint32_t nq, uint32_t k, int metric, uint32_t *ids_out, float *scores_out,
+                        double *seconds_out);
+/* Graph-reconstruction precision@k over the given vertices (query_ids NULL: all n, nq ignored), counted on the device:
+ * hits = sum_v |top-k(v) n N(v)| with v itself excluded from its top-k, possible = sum_v min(k, d(v)), d(v) the number of DISTINCT
+ * neighbours of v other than v (duplicate nonzeros and self-loops of the CSR count once / not at all). */
+F2V_API int f2v_neighbour_recall(f2v_handle h, const uint32_t *query_ids, uint32_t nq, uint32_t k, int metric, uint64_t *hits_out,
+                         uint64_t *possible_out, double *seconds_out);
+
 /* ---- host-side I/O of the drop-in boundary (no device needed) ----------------------------
  * f2v_read_mtx replaces SetInputMatricesAsCSR (sample/commonutility.h:44-54 -> ReadASCII
  * sample/IO.h:59-156, CSC sample/CSC.h:146-188, CSR sample/CSR.h:154-186): MatrixMarket
