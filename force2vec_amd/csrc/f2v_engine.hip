@@ -325,11 +325,61 @@ uint32_t subwave_width(const f2v_ctx *c) {
     return w;
 }
 
+// The sub-wave layouts: an item's row lies in LPI lanes of NB dwordx4 each, U neighbour rows are in flight per item, and a
+// wavefront holds `per_wave` items.  Everything that depends on a layout -- the planners' items per workgroup, the kernel
+// instantiations a launch chooses from (dispatch_subwave) -- reads this table.
+struct SubwaveLayout {
+    uint32_t width;
+    int lpi, nb, u;
+    uint32_t per_wave;
+};
+constexpr SubwaveLayout kSubwave[] = {{16, 4, 1, 8, 16}, {32, 8, 1, 8, 8}, {64, 16, 1, 8, 4}, {128, 16, 2, 4, 4}, {256, 16, 4, 4, 4}};
+
+// items per wavefront on the layout of this width (0: the generic layout, one item per wavefront)
+constexpr uint32_t items_per_wave(uint32_t width) {
+    for (const SubwaveLayout &l : kSubwave)
+        if (l.width == width) return l.per_wave;
+    return 1u;
+}
+
 // items one workgroup of the step kernel covers, and tree nodes one workgroup covers (= its wavefronts)
-uint32_t items_per_block(const f2v_ctx *c) {
-    const uint32_t w = subwave_width(c);
-    const uint32_t per_wave = !w ? 1u : (w == 16 ? 16u : w == 32 ? 8u : 4u);
-    return per_wave * (uint32_t)c->waves_per_block;
+uint32_t items_per_block(const f2v_ctx *c) { return items_per_wave(subwave_width(c)) * (uint32_t)c->waves_per_block; }
+
+template <int V> using Int = std::integral_constant<int, V>;
+
+// f(OPT, LPI, NB, U, FULL) on layout I of the table with U rows in flight
+template <int I, int U, typename F>
+int subwave_case(int math, bool full, F &f) {
+    auto run = [&](auto O) {
+        if (full) f(O, Int<kSubwave[I].lpi>{}, Int<kSubwave[I].nb>{}, Int<U>{}, std::true_type{});
+        else f(O, Int<kSubwave[I].lpi>{}, Int<kSubwave[I].nb>{}, Int<U>{}, std::false_type{});
+    };
+    if (math == 5) run(Int<5>{});
+    else run(Int<6>{});
+    return F2V_OK;
+}
+
+// Call f(OPT, LPI, NB, U, FULL) -- std::integral_constants -- for the sub-wave kernel that runs `math` on the layout `width`.
+// OPT: 5 or 6 (math 7 runs 6); FULL: the rows fill the layout (D == width).  The launch forms do not instantiate the same
+// kernels, and f is only instantiated for what its form runs: NARROWEST is the form's narrowest layout, U8_AT_128 says whether
+// "rows_in_flight" = 8 selects U = 8 at width 128 (elsewhere U is the table's).
+template <uint32_t NARROWEST, bool U8_AT_128, typename F>
+int dispatch_subwave(const f2v_ctx *c, int math, uint32_t width, F &&f) {
+    static_assert(NARROWEST == kSubwave[0].width || NARROWEST == kSubwave[1].width, "a form may leave out the narrowest layout only");
+    const bool full = width == c->D;
+    switch (width) {
+        case kSubwave[0].width:
+            if constexpr (NARROWEST <= kSubwave[0].width) return subwave_case<0, kSubwave[0].u>(math, full, f);
+            break;
+        case kSubwave[1].width: return subwave_case<1, kSubwave[1].u>(math, full, f);
+        case kSubwave[2].width: return subwave_case<2, kSubwave[2].u>(math, full, f);
+        case kSubwave[3].width:
+            if constexpr (U8_AT_128)
+                if (c->rows_in_flight == 8) return subwave_case<3, 8>(math, full, f);
+            return subwave_case<3, kSubwave[3].u>(math, full, f);
+        case kSubwave[4].width: return subwave_case<4, kSubwave[4].u>(math, full, f);
+    }
+    return fail(F2V_ESTATE, "no sub-wave kernel of this launch form runs rows of width %u", width);
 }
 
 // Where a split row (degree > chunk) is cut into pieces: after every `chunk` neighbours, and -- "class_cut", the default --
@@ -588,7 +638,7 @@ uint32_t wide_width(const f2v_ctx *c, uint32_t batch) {
     const uint32_t floor_w = c->wide_min_width ? c->wide_min_width : (c->nnz <= (2ull << 20) ? 64u : batch <= 1024u ? 32u : 16u);
     return std::max(subwave_width(c), floor_w);
 }
-uint32_t wide_items_per_block(uint32_t width) { return 4u * (width == 16 ? 16u : width == 32 ? 8u : 4u); }
+uint32_t wide_items_per_block(uint32_t width) { return 4u * items_per_wave(width); }
 
 // the wide form of a chained launch: jobs add at most 32 LDS slots, so the fan-in groups must fit
 bool wide_usable(const f2v_ctx *c) { return c->wide && c->fanin >= 2 && c->fanin <= 32 && c->waves_per_block == 4; }
@@ -1270,6 +1320,15 @@ int dispatch_layout(f2v_ctx *c, F &&f) {
     return fail(F2V_EINVAL, "unsupported dimension %u", c->D);
 }
 
+// ... and f(OPT, VEC, EXACT) for the kernels of the generic layout that differ by the option's math (5, or 6: math 7 runs 6)
+template <typename F>
+int dispatch_math_layout(f2v_ctx *c, int math, F &&f) {
+    return dispatch_layout(c, [&](auto V, auto E) {
+        if (math == 5) f(Int<5>{}, V, E);
+        else f(Int<6>{}, V, E);
+    });
+}
+
 // Make d_X[cur] the whole, up-to-date matrix: a completed epoch (all N rows updated) just swaps the two
 // matrices; a partial range is folded back with a copy.
 int flush_pending(f2v_ctx *c) {
@@ -1421,40 +1480,109 @@ int math_of_option(int option) {
 // Launch one minibatch step (+ hub finalisation) on the handle's stream.  d_ids: device sample ids.
 void fill_targets(const f2v_ctx *c, PushTargets &t, int which, uint32_t batch_lo, const uint32_t *d_masks);
 
-// bound of a combine-tree node's wait in ticks of the 100 MHz wall clock ("tree_timeout_ms", default 5 s; the
-// environment variable F2V_TREE_TIMEOUT_MS sets the default of new handles)
-unsigned long long tree_timeout_ticks(const f2v_ctx *c) { return (unsigned long long)c->tree_timeout_ms * 100000ull; }
+// a bound given in milliseconds in ticks of the 100 MHz wall clock (wall_clock64)
+unsigned long long ms_to_ticks(int64_t ms) { return (unsigned long long)ms * 100000ull; }
+
+// bound of a combine-tree node's wait ("tree_timeout_ms", default 5 s; the environment variable F2V_TREE_TIMEOUT_MS sets the
+// default of new handles)
+unsigned long long tree_timeout_ticks(const f2v_ctx *c) { return ms_to_ticks(c->tree_timeout_ms); }
+
+// the sequence number of a launch with in-grid waits (never 0: that is what fresh flags hold)
+uint32_t next_launch_seq(f2v_ctx *c) {
+    if (++c->launch_seq == 0) ++c->launch_seq;
+    return c->launch_seq;
+}
+
+// a launch whose first row is `lo` does not continue the updated range (a new epoch, or batches out of order): swap / fold first
+int flush_unless_continued(f2v_ctx *c, uint32_t lo) { return (c->upd_hi != c->upd_lo && lo != c->upd_hi) ? flush_pending(c) : F2V_OK; }
+
+// the first row a chained launch starting at row `lo` reads from the second matrix
+uint32_t chain_upd_lo(const f2v_ctx *c, uint32_t lo) { return c->upd_hi == c->upd_lo ? lo : c->upd_lo; }
+
+// what every form of the step kernel is told: the matrices, the graph, the launch's items, the step's scalars
+void fill_step_args(const f2v_ctx *c, StepArgs &a, int math, size_t item_off, uint32_t upd_lo, uint32_t ns, float lr, int bs_mode) {
+    a.X = c->d_X[c->cur];
+    a.Xn = c->d_X[c->cur ^ 1];
+    a.rowptr = c->d_rowptr;
+    a.nbr_ids = math == 7 ? c->d_walks : c->d_colids;
+    a.partials = c->d_partials;
+    a.items = c->d_items + item_off;
+    a.sm_table = c->d_table;
+    a.D = c->D;
+    a.upd_lo = upd_lo;
+    a.ns = ns;
+    a.bs_mode = bs_mode ? 1u : 0u;
+    a.unit_degi = c->unit_degi ? 1u : 0u;
+    a.lr = lr;
+}
+
+// Arm the in-grid waits of a launch: the flags, where a wait that gives up reports, its bound and a fresh sequence number.
+// A chained launch lasts a millisecond or two: its waits are bounded by "chain_timeout_ms" as well.
+void arm_waits(f2v_ctx *c, StepArgs &a, bool chained) {
+    a.ready = c->d_ready;
+    a.err = c->d_kerr;
+    a.timeout_ticks = chained ? ms_to_ticks(std::min(c->tree_timeout_ms, c->chain_timeout_ms)) : tree_timeout_ticks(c);
+    a.seq = next_launch_seq(c);
+#ifdef F2V_TEST_HOOKS
+    a.test_withhold_slot = c->test_withhold_slot;
+    a.test_withhold_row = chained ? c->test_withhold_row : kNoSlot;  // (chained launches only)
+#endif
+}
+
+// Record a launch over rows [lo, hi) that computed `rows` rows against `samples` negative samples, `epochs` times over: the
+// statistics and -- unless nothing is left pending (the ring of the wide form) -- the updated range, with [p_lo, hi) the last minibatch
+template <class P>
+void record_launch(f2v_ctx *c, const P &plan, uint32_t lo, uint32_t hi, uint32_t p_lo, uint64_t rows, uint64_t samples, uint64_t epochs = 1,
+                   bool pending = true) {
+    if (pending) {
+        if (c->upd_hi == c->upd_lo) c->upd_lo = lo;
+        c->upd_hi = hi;
+        c->pending = true;
+        c->p_lo = p_lo;
+        c->p_hi = hi;
+    }
+    // statistics: algorithmic bytes of SURVEY 8d -- nnz*(4D+4) + rows*(8D+4) + ns*(4D+4) per minibatch
+    c->stats.hub_rows += (uint64_t)plan.n_hubs * epochs;
+    c->stats.hub_chunks += (uint64_t)plan.n_chunks * epochs;
+    c->stats.step_launches += 1;
+    c->stats.rows += rows * epochs;
+    c->stats.nnz += plan.nnz * epochs;
+    c->stats.algorithmic_bytes += (plan.nnz * (4ull * c->D + 4) + rows * (8ull * c->D + 4) + samples * (4ull * c->D + 4)) * epochs;
+    c->stats.compulsory_bytes += plan.compulsory * epochs;
+}
+
+// `epochs` epochs of seven counters as `per` of them counted (f2v_train's hipGraph form counts two while it captures)
+void scale_stats(f2v_stats &s, uint64_t epochs, uint64_t per) {
+    for (uint64_t *v : {&s.step_launches, &s.rows, &s.nnz, &s.algorithmic_bytes, &s.hub_rows, &s.hub_chunks, &s.compulsory_bytes}) *v = *v / per * epochs;
+}
+
+// combine-tree launch of `n` nodes at `items`, reading and writing what the step launch `a` did
+FinalizeArgs finalize_args(const f2v_ctx *c, const StepArgs &a, const FinItem *items, uint32_t n) {
+    FinalizeArgs f{};
+    f.X = a.X;
+    f.partials = c->d_partials;
+    f.Xn = a.Xn;
+    f.items = items;
+    f.n_items = n;
+    f.D = c->D;
+    f.push = a.push;
+    return f;
+}
 
 // push_masks / push: a sharded run's step -- the kernels also store every finished row into the second matrix of
 // the peers that read it (push_masks == nullptr: of every peer).
 int launch_step(f2v_ctx *c, int math, uint32_t batch_lo, uint32_t batch_hi, uint32_t row_lo, uint32_t row_hi,
                 const uint32_t *d_ids, uint32_t ns, float lr, int bs_mode, bool push = false, const uint32_t *push_masks = nullptr) {
     int rc;
-    if (c->upd_hi != c->upd_lo && batch_lo != c->upd_hi) {
-        // not the continuation of the updated range (a new epoch, or batches out of order): swap / fold first
-        if ((rc = flush_pending(c)) != F2V_OK) return rc;
-    }
-    const bool walk = (math == 7);
-    const Plan plan = plan_for(c, row_lo, row_hi, walk);  // by value: upload_plans may not move it, but keep it simple
+    if ((rc = flush_unless_continued(c, batch_lo)) != F2V_OK) return rc;
+    const Plan plan = plan_for(c, row_lo, row_hi, math == 7);  // by value: upload_plans may not move it, but keep it simple
     if ((rc = upload_plans(c)) != F2V_OK) return rc;
     StepArgs a{};
-    a.X = c->d_X[c->cur];
-    a.Xn = c->d_X[c->cur ^ 1];
-    a.rowptr = c->d_rowptr;
-    a.nbr_ids = walk ? c->d_walks : c->d_colids;
-    a.partials = c->d_partials;
+    fill_step_args(c, a, math, plan.item_off, c->upd_lo, ns, lr, bs_mode);
     a.sample_ids = d_ids;
-    a.items = c->d_items + plan.item_off;
-    a.sm_table = c->d_table;
-    a.D = c->D;
     a.batch_lo = batch_lo;
     a.n_items = plan.n_items;
-    a.upd_lo = c->upd_lo;
     a.upd_rows = c->upd_hi - c->upd_lo;
-    a.ns = ns;
-    a.bs_mode = bs_mode ? 1u : 0u;
-    a.unit_degi = c->unit_degi ? 1u : 0u;
-    a.lr = lr;
 #ifdef F2V_TEST_HOOKS
     a.xcd_times = c->d_xcd;
 #endif
@@ -1464,61 +1592,36 @@ int launch_step(f2v_ctx *c, int math, uint32_t batch_lo, uint32_t batch_hi, uint
     const uint32_t wpb = (uint32_t)c->waves_per_block;
     // sub-wave layout when D is a multiple of 4 up to 256: 16, 8 or 4 work items per wavefront
     const uint32_t width = subwave_width(c);
-    const bool quarter = width != 0, full = width == c->D;
-    const uint32_t per_wave = !quarter ? 1u : (width == 16 ? 16u : width == 32 ? 8u : 4u);
+    const bool quarter = width != 0;
+    const uint32_t per_wave = items_per_wave(width);
     const uint32_t waves = (plan.n_items + per_wave - 1) / per_wave;
     uint32_t blocks = (waves + wpb - 1) / wpb;  // 0 when this rank has no row of the batch
     a.step_blocks = blocks;
+    uint32_t tree_nodes = 0;
+    for (int lev = 0; lev < plan.n_levels; lev++) tree_nodes += plan.fin_cnt[lev];  // the levels are stored back to back
     // sub-wave kernel: the combine trees ride in the same grid (one launch per minibatch)
     const bool fused_tree = quarter && c->merge_fin && !c->capturing && plan.n_levels >= 1 && blocks > 0;
     if (fused_tree) {
         a.fin_items = c->d_hubs + plan.fin_off[0];
-        a.fin_n = 0;
-        for (int lev = 0; lev < plan.n_levels; lev++) a.fin_n += plan.fin_cnt[lev];  // the levels are stored back to back
-        a.ready = c->d_ready;
-        a.err = c->d_kerr;
-        a.timeout_ticks = tree_timeout_ticks(c);
-        a.seq = ++c->launch_seq;
-        if (a.seq == 0) a.seq = ++c->launch_seq;  // 0 is what fresh flags hold
-#ifdef F2V_TEST_HOOKS
-        a.test_withhold_slot = c->test_withhold_slot;
-        a.test_withhold_row = kNoSlot;  // (chained launches only)
-#endif
+        a.fin_n = tree_nodes;
+        arm_waits(c, a, false);
         blocks += (a.fin_n + wpb - 1) / wpb;
     }
     if (blocks == 0) {
         // nothing to compute here; the range bookkeeping below still advances
     } else if (quarter) {
-#define F2V_Q2(OPT, LPI, NB, U, PUSH, FULL) hipLaunchKernelGGL((qstep_kernel<OPT, LPI, NB, U, PUSH, FULL>), dim3(blocks), dim3(64 * wpb), 0, c->stream, a)
-#define F2V_Q(OPT, LPI, NB, U)                                                              \
-    do {                                                                                    \
-        if (push) { if (full) F2V_Q2(OPT, LPI, NB, U, true, true); else F2V_Q2(OPT, LPI, NB, U, true, false); }    \
-        else { if (full) F2V_Q2(OPT, LPI, NB, U, false, true); else F2V_Q2(OPT, LPI, NB, U, false, false); }       \
-    } while (0)
         // rows in flight per item: 4 at D = 128 (90 VGPRs, 5 waves/SIMD; 8 is selectable and measured 3-9 % slower
         // on RMAT-20: 116 VGPRs, 4 waves/SIMD) and at D = 256; 8 where a row is a single dwordx4 per lane (D <= 64)
-        const bool u8 = (c->rows_in_flight == 8);
-        const int o = (math == 5) ? 5 : 6;
-        switch (width) {
-            case 16: if (o == 5) F2V_Q(5, 4, 1, 8); else F2V_Q(6, 4, 1, 8); break;
-            case 32: if (o == 5) F2V_Q(5, 8, 1, 8); else F2V_Q(6, 8, 1, 8); break;
-            case 64: if (o == 5) F2V_Q(5, 16, 1, 8); else F2V_Q(6, 16, 1, 8); break;
-            case 128:
-                if (u8) { if (o == 5) F2V_Q(5, 16, 2, 8); else F2V_Q(6, 16, 2, 8); }
-                else { if (o == 5) F2V_Q(5, 16, 2, 4); else F2V_Q(6, 16, 2, 4); }
-                break;
-            default: if (o == 5) F2V_Q(5, 16, 4, 4); else F2V_Q(6, 16, 4, 4); break;
-        }
-#undef F2V_Q
-#undef F2V_Q2
+        rc = dispatch_subwave<16, true>(c, math, width, [&](auto O, auto L, auto N, auto U, auto FL) {
+            constexpr int OPT = decltype(O)::value, LPI = decltype(L)::value, NB = decltype(N)::value, UR = decltype(U)::value;
+            constexpr bool FULL = decltype(FL)::value;
+            if (push) hipLaunchKernelGGL((qstep_kernel<OPT, LPI, NB, UR, true, FULL>), dim3(blocks), dim3(64 * wpb), 0, c->stream, a);
+            else hipLaunchKernelGGL((qstep_kernel<OPT, LPI, NB, UR, false, FULL>), dim3(blocks), dim3(64 * wpb), 0, c->stream, a);
+        });
+        if (rc != F2V_OK) return rc;
     } else {
-        rc = dispatch_layout(c, [&](auto V, auto E) {
-            constexpr int VEC = decltype(V)::value;
-            constexpr bool EX = decltype(E)::value;
-            if (math == 5)
-                hipLaunchKernelGGL((step_kernel<5, VEC, EX>), dim3(blocks), dim3(64 * wpb), 0, c->stream, a);
-            else
-                hipLaunchKernelGGL((step_kernel<6, VEC, EX>), dim3(blocks), dim3(64 * wpb), 0, c->stream, a);
+        rc = dispatch_math_layout(c, math, [&](auto O, auto V, auto E) {
+            hipLaunchKernelGGL((step_kernel<decltype(O)::value, decltype(V)::value, decltype(E)::value>), dim3(blocks), dim3(64 * wpb), 0, c->stream, a);
         });
         if (rc != F2V_OK) return rc;
     }
@@ -1526,145 +1629,77 @@ int launch_step(f2v_ctx *c, int math, uint32_t batch_lo, uint32_t batch_hi, uint
     const bool tree = !fused_tree && c->merge_fin && !c->capturing && plan.n_levels >= 2;
     if (tree) {
         FinalizeTreeArgs t{};
-        t.f.X = a.X;
-        t.f.partials = c->d_partials;
-        t.f.Xn = a.Xn;
-        t.f.items = c->d_hubs + plan.fin_off[0];
-        t.f.n_items = 0;
-        for (int lev = 0; lev < plan.n_levels; lev++) t.f.n_items += plan.fin_cnt[lev];  // the levels are stored back to back
-        t.f.D = c->D;
-        t.f.push = a.push;
+        t.f = finalize_args(c, a, c->d_hubs + plan.fin_off[0], tree_nodes);
         t.ready = c->d_ready;
         t.err = c->d_kerr;
         t.timeout_ticks = tree_timeout_ticks(c);
-        t.seq = ++c->launch_seq;
-        if (t.seq == 0) t.seq = ++c->launch_seq;  // 0 is what fresh flags hold
+        t.seq = next_launch_seq(c);
         t.first_dep = plan.fin_cnt[0];
         const uint32_t fb = (t.f.n_items + wpb - 1) / wpb;  // the node layout counts on `wpb` nodes per workgroup
-        rc = dispatch_layout(c, [&](auto V, auto E) {
-            constexpr int VEC = decltype(V)::value;
-            constexpr bool EX = decltype(E)::value;
-            if (math == 5)
-                hipLaunchKernelGGL((hub_finalize_tree_kernel<5, VEC, EX>), dim3(fb), dim3(64 * wpb), 0, c->stream, t);
-            else
-                hipLaunchKernelGGL((hub_finalize_tree_kernel<6, VEC, EX>), dim3(fb), dim3(64 * wpb), 0, c->stream, t);
+        rc = dispatch_math_layout(c, math, [&](auto O, auto V, auto E) {
+            hipLaunchKernelGGL((hub_finalize_tree_kernel<decltype(O)::value, decltype(V)::value, decltype(E)::value>), dim3(fb), dim3(64 * wpb), 0, c->stream, t);
         });
         if (rc != F2V_OK) return rc;
         HIPC(hipGetLastError());
     }
     for (int lev = 0; lev < plan.n_levels && !tree && !fused_tree; lev++) {
-        FinalizeArgs f{};
-        f.X = a.X;
-        f.partials = c->d_partials;
-        f.Xn = a.Xn;
-        f.items = c->d_hubs + plan.fin_off[lev];
-        f.n_items = plan.fin_cnt[lev];
-        f.D = c->D;
-        f.push = a.push;
+        const FinalizeArgs f = finalize_args(c, a, c->d_hubs + plan.fin_off[lev], plan.fin_cnt[lev]);
         const uint32_t fb = (f.n_items + 3) / 4;
-        rc = dispatch_layout(c, [&](auto V, auto E) {
-            constexpr int VEC = decltype(V)::value;
-            constexpr bool EX = decltype(E)::value;
-            if (math == 5)
-                hipLaunchKernelGGL((hub_finalize_kernel<5, VEC, EX>), dim3(fb), dim3(256), 0, c->stream, f);
-            else
-                hipLaunchKernelGGL((hub_finalize_kernel<6, VEC, EX>), dim3(fb), dim3(256), 0, c->stream, f);
+        rc = dispatch_math_layout(c, math, [&](auto O, auto V, auto E) {
+            hipLaunchKernelGGL((hub_finalize_kernel<decltype(O)::value, decltype(V)::value, decltype(E)::value>), dim3(fb), dim3(256), 0, c->stream, f);
         });
         if (rc != F2V_OK) return rc;
         HIPC(hipGetLastError());
     }
-    c->stats.hub_rows += plan.n_hubs;
-    c->stats.hub_chunks += plan.n_chunks;
-    if (c->upd_hi == c->upd_lo) c->upd_lo = batch_lo;
-    c->upd_hi = batch_hi;
-    c->pending = true;
-    c->p_lo = batch_lo;
-    c->p_hi = batch_hi;
-
-    // statistics: algorithmic bytes of SURVEY 8d -- nnz*(4D+4) + rows*(8D+4) + ns*(4D+4) per minibatch
-    const uint64_t rows = row_hi - row_lo;
-    c->stats.step_launches += 1;
-    c->stats.rows += rows;
-    c->stats.nnz += plan.nnz;
-    c->stats.algorithmic_bytes += plan.nnz * (4ull * c->D + 4) + rows * (8ull * c->D + 4) + (uint64_t)ns * (4ull * c->D + 4);
-    c->stats.compulsory_bytes += plan.compulsory;
+    record_launch(c, plan, batch_lo, batch_hi, batch_lo, row_hi - row_lo, ns);
     return F2V_OK;
+}
+
+// the fields the two chained forms share: the tree nodes, the armed waits, the rows handed on inside the launch
+template <class P>
+void fill_chain_args(f2v_ctx *c, StepArgs &a, int math, const P &plan, uint32_t ns, float lr, int bs_mode) {
+    fill_step_args(c, a, math, plan.item_off, chain_upd_lo(c, plan.lo), ns, lr, bs_mode);
+    a.fin_items = c->d_hubs + plan.fin_off;
+    arm_waits(c, a, true);
+    a.rowflag = c->d_rowflag;
+    a.chain_lo = plan.lo;
+#ifdef F2V_TEST_HOOKS
+    a.stamps = c->d_stamps;
+#endif
 }
 
 // One chained launch: minibatches [plan.first_batch, +plan.n_batches) of an epoch whose sample ids (ids_stride per minibatch)
 // lie at d_ids_epoch.
 int launch_chain(f2v_ctx *c, int math, const ChainPlan &plan, const uint32_t *d_ids_epoch, uint32_t ids_stride, uint32_t ns, float lr, int bs_mode) {
     int rc;
-    if (c->upd_hi != c->upd_lo && plan.lo != c->upd_hi) {
-        if ((rc = flush_pending(c)) != F2V_OK) return rc;
-    }
+    if ((rc = flush_unless_continued(c, plan.lo)) != F2V_OK) return rc;
     ChainArgs ca{};
-    StepArgs &a = ca.base;
-    a.X = c->d_X[c->cur];
-    a.Xn = c->d_X[c->cur ^ 1];
-    a.rowptr = c->d_rowptr;
-    a.nbr_ids = math == 7 ? c->d_walks : c->d_colids;
-    a.partials = c->d_partials;
-    a.items = c->d_items + plan.item_off;
-    a.sm_table = c->d_table;
-    a.D = c->D;
-    a.upd_lo = (c->upd_hi == c->upd_lo) ? plan.lo : c->upd_lo;
-    a.ns = ns;
-    a.bs_mode = bs_mode ? 1u : 0u;
-    a.unit_degi = c->unit_degi ? 1u : 0u;
-    a.lr = lr;
-    a.fin_items = c->d_hubs + plan.fin_off;
-    a.ready = c->d_ready;
-    a.err = c->d_kerr;
-    a.timeout_ticks = (unsigned long long)std::min(c->tree_timeout_ms, c->chain_timeout_ms) * 100000ull;
-    a.seq = ++c->launch_seq;
-    if (a.seq == 0) a.seq = ++c->launch_seq;
+    fill_chain_args(c, ca.base, math, plan, ns, lr, bs_mode);
 #ifdef F2V_TEST_HOOKS
-    a.test_withhold_slot = c->test_withhold_slot;
-    a.test_withhold_row = c->test_withhold_row;
-#endif
-    a.rowflag = c->d_rowflag;
-    a.chain_lo = plan.lo;
-#ifdef F2V_TEST_HOOKS
-    if (c->test_chain_nowait) a.chain_lo = 0xFFFFFFFFu;  // the kernel then treats no row as "written by an earlier minibatch"
-    a.stamps = c->d_stamps;
+    if (c->test_chain_nowait) ca.base.chain_lo = 0xFFFFFFFFu;  // the kernel then treats no row as "written by an earlier minibatch"
 #endif
     ca.wg = c->d_wg + plan.wg_off;
     ca.ids = d_ids_epoch;
     ca.ids_stride = ids_stride;
-    const uint32_t width = subwave_width(c), wpb = (uint32_t)c->waves_per_block;
-    const bool full = width == c->D;
-    const int o = (math == 5) ? 5 : 6;
-#define F2V_C2(OPT, LPI, NB, U, FULL) hipLaunchKernelGGL((qstep_chain_kernel<OPT, LPI, NB, U, FULL>), dim3(plan.n_wgs), dim3(64 * wpb), 0, c->stream, ca)
-#define F2V_C(OPT, LPI, NB, U) do { if (full) F2V_C2(OPT, LPI, NB, U, true); else F2V_C2(OPT, LPI, NB, U, false); } while (0)
-    switch (width) {
-        case 32: if (o == 5) F2V_C(5, 8, 1, 8); else F2V_C(6, 8, 1, 8); break;
-        case 64: if (o == 5) F2V_C(5, 16, 1, 8); else F2V_C(6, 16, 1, 8); break;
-        case 128:
-            if (c->rows_in_flight == 8) { if (o == 5) F2V_C(5, 16, 2, 8); else F2V_C(6, 16, 2, 8); }
-            else { if (o == 5) F2V_C(5, 16, 2, 4); else F2V_C(6, 16, 2, 4); }
-            break;
-        default: if (o == 5) F2V_C(5, 16, 4, 4); else F2V_C(6, 16, 4, 4); break;
-    }
-#undef F2V_C
-#undef F2V_C2
+    const uint32_t wpb = (uint32_t)c->waves_per_block;
+    // (no 16-wide instance: rows narrower than a 128-byte line chain in the wide form only, chain_usable)
+    rc = dispatch_subwave<32, true>(c, math, subwave_width(c), [&](auto O, auto L, auto N, auto U, auto FL) {
+        hipLaunchKernelGGL((qstep_chain_kernel<decltype(O)::value, decltype(L)::value, decltype(N)::value, decltype(U)::value, decltype(FL)::value>),
+                           dim3(plan.n_wgs), dim3(64 * wpb), 0, c->stream, ca);
+    });
+    if (rc != F2V_OK) return rc;
     HIPC(hipGetLastError());
     c->last_train_form = 1;
-    if (c->upd_hi == c->upd_lo) c->upd_lo = plan.lo;
-    c->upd_hi = plan.hi;
-    c->pending = true;
-    c->p_lo = plan.last_lo;
-    c->p_hi = plan.hi;
-    c->stats.hub_rows += plan.n_hubs;
-    c->stats.hub_chunks += plan.n_chunks;
-    c->stats.step_launches += 1;
-    c->stats.rows += plan.hi - plan.lo;
-    c->stats.nnz += plan.nnz;
-    c->stats.algorithmic_bytes += plan.nnz * (4ull * c->D + 4) + (uint64_t)(plan.hi - plan.lo) * (8ull * c->D + 4) + (uint64_t)plan.n_batches * ns * (4ull * c->D + 4);
-    c->stats.compulsory_bytes += plan.compulsory;
+    record_launch(c, plan, plan.lo, plan.hi, plan.last_lo, plan.hi - plan.lo, (uint64_t)plan.n_batches * ns);
     return F2V_OK;
 }
 
+void free_ring(f2v_ctx *c) {
+    for (void *p : {(void *)c->d_ring, (void *)c->d_ring_partials, (void *)c->d_ring_flags, (void *)c->d_ring_ready})
+        if (p) (void)hipFree(p);
+    c->d_ring = c->d_ring_partials = nullptr;
+    c->d_ring_flags = c->d_ring_ready = nullptr;
+}
 
 // One launch of the wide form (qwide_chain_kernel): minibatches [plan.first_batch, +plan.n_batches)
 // `epochs` > 1 (the plan covers the whole graph): that many epochs chained in the one launch -- the current matrix is copied into a ring
@@ -1677,10 +1712,7 @@ int launch_wide(f2v_ctx *c, int math, const WidePlan &plan, const uint32_t *d_id
     if (epochs > 1 && (c->ring_epochs < epochs || c->ring_slots < std::max<size_t>(plan.n_slots, 1))) {
         // the ring of matrices (and the per-epoch flags and partial sums): where the device has no room for it, one epoch per launch
         HIPC(hipStreamSynchronize(c->stream));
-        for (void *p : {(void *)c->d_ring, (void *)c->d_ring_partials, (void *)c->d_ring_flags, (void *)c->d_ring_ready})
-            if (p) (void)hipFree(p);
-        c->d_ring = c->d_ring_partials = nullptr;
-        c->d_ring_flags = c->d_ring_ready = nullptr;
+        free_ring(c);
         const uint32_t cap = std::max(epochs, c->ring_epochs);
         const size_t slots = std::max<size_t>(std::max<size_t>(plan.n_slots, c->ring_slots), 1), mat = (size_t)c->n * c->D;
         c->ring_epochs = 0;
@@ -1694,10 +1726,7 @@ int launch_wide(f2v_ctx *c, int math, const WidePlan &plan, const uint32_t *d_id
             hipMalloc((void **)&c->d_ring_flags, (size_t)cap * c->n * sizeof(uint32_t)) != hipSuccess ||
             hipMalloc((void **)&c->d_ring_ready, (size_t)cap * slots * sizeof(uint32_t)) != hipSuccess) {
             (void)hipGetLastError();
-            for (void *p : {(void *)c->d_ring, (void *)c->d_ring_partials, (void *)c->d_ring_flags, (void *)c->d_ring_ready})
-                if (p) (void)hipFree(p);
-            c->d_ring = c->d_ring_partials = nullptr;
-            c->d_ring_flags = c->d_ring_ready = nullptr;
+            free_ring(c);
             c->ring_refused = true;  // (f2v_train stops asking)
             epochs = 1;
         } else {
@@ -1709,9 +1738,7 @@ int launch_wide(f2v_ctx *c, int math, const WidePlan &plan, const uint32_t *d_id
     }
     if (epochs_io) *epochs_io = epochs;
     const bool ring = epochs > 1;
-    if (ring || (c->upd_hi != c->upd_lo && plan.lo != c->upd_hi)) {
-        if ((rc = flush_pending(c)) != F2V_OK) return rc;
-    }
+    if ((rc = ring ? flush_pending(c) : flush_unless_continued(c, plan.lo)) != F2V_OK) return rc;
     const size_t matrix = (size_t)c->n * c->D;
     if (ring) {
         if (plan.lo != 0 || plan.hi != c->n || plan.n_node_wgs != 0) return fail(F2V_ESTATE, "launch_wide: epochs can only be chained where one launch covers the graph");
@@ -1719,32 +1746,13 @@ int launch_wide(f2v_ctx *c, int math, const WidePlan &plan, const uint32_t *d_id
     }
     WideArgs wa{};
     StepArgs &a = wa.base;
-    a.X = ring ? c->d_ring : c->d_X[c->cur];
-    a.Xn = ring ? c->d_ring + matrix : c->d_X[c->cur ^ 1];
-    a.rowptr = c->d_rowptr;
-    a.nbr_ids = math == 7 ? c->d_walks : c->d_colids;
-    a.partials = ring ? c->d_ring_partials : c->d_partials;
-    a.items = c->d_items + plan.item_off;
-    a.sm_table = c->d_table;
-    a.D = c->D;
-    a.upd_lo = (c->upd_hi == c->upd_lo) ? plan.lo : c->upd_lo;
-    a.ns = ns;
-    a.bs_mode = bs_mode ? 1u : 0u;
-    a.unit_degi = c->unit_degi ? 1u : 0u;
-    a.lr = lr;
-    a.fin_items = c->d_hubs + plan.fin_off;
-    a.ready = ring ? c->d_ring_ready : c->d_ready;
-    a.err = c->d_kerr;
-    a.timeout_ticks = (unsigned long long)std::min(c->tree_timeout_ms, c->chain_timeout_ms) * 100000ull;
-    a.seq = ++c->launch_seq;
-    if (a.seq == 0) a.seq = ++c->launch_seq;
-#ifdef F2V_TEST_HOOKS
-    a.test_withhold_slot = c->test_withhold_slot;
-    a.test_withhold_row = c->test_withhold_row;
-#endif
-    a.rowflag = ring ? c->d_ring_flags : c->d_rowflag;
-    a.chain_lo = plan.lo;
-    if (ring) {
+    fill_chain_args(c, a, math, plan, ns, lr, bs_mode);
+    if (ring) {  // the ring's matrices, and every epoch its own partial sums and flags
+        a.X = c->d_ring;
+        a.Xn = c->d_ring + matrix;
+        a.partials = c->d_ring_partials;
+        a.ready = c->d_ring_ready;
+        a.rowflag = c->d_ring_flags;
         wa.wgs_per_epoch = plan.n_wgs;
         wa.n_rows = c->n;
         wa.slots_per_epoch = (uint32_t)c->ring_slots;
@@ -1753,52 +1761,31 @@ int launch_wide(f2v_ctx *c, int math, const WidePlan &plan, const uint32_t *d_id
     }
 #ifdef F2V_TEST_HOOKS
     a.test_nowait = c->test_chain_mode;
-    a.stamps = c->d_stamps;
 #endif
     wa.wg = c->d_wide + plan.wg_off;
     wa.jobs = c->d_jobs + plan.job_off;
     wa.ids = d_ids_epoch;
     wa.ids_stride = ids_stride;
-    const uint32_t width = plan.width;
-    const bool full = width == c->D;
-    const int o = (math == 5) ? 5 : 6;
     // "wide_samples_early" (-1 = automatic): on for graphs of up to 2 M nonzeros, whose launches are one dependency chain
     const bool early = ring || (c->wide_samples_early >= 0 ? c->wide_samples_early != 0 : c->nnz <= (2ull << 20));
     c->last_wide_early = early;
-    c->last_wide_width = width;
+    c->last_wide_width = plan.width;
     c->last_train_form = 2;
     c->last_wide_epochs = std::max(c->last_wide_epochs, epochs);  // (the most epochs one launch of this f2v_train has carried)
     const uint32_t grid = plan.n_wgs * epochs;
-#define F2V_W3(OPT, LPI, NB, U, FULL, MODE) hipLaunchKernelGGL((qwide_chain_kernel<OPT, LPI, NB, U, FULL, MODE>), dim3(grid), dim3(256), 0, c->stream, wa)
-#define F2V_W2(OPT, LPI, NB, U, FULL) do { if (ring) F2V_W3(OPT, LPI, NB, U, FULL, 2); else if (early) F2V_W3(OPT, LPI, NB, U, FULL, 1); else F2V_W3(OPT, LPI, NB, U, FULL, 0); } while (0)
-#define F2V_W(OPT, LPI, NB, U) do { if (full) F2V_W2(OPT, LPI, NB, U, true); else F2V_W2(OPT, LPI, NB, U, false); } while (0)
-    switch (width) {
-        case 16: if (o == 5) F2V_W(5, 4, 1, 8); else F2V_W(6, 4, 1, 8); break;
-        case 32: if (o == 5) F2V_W(5, 8, 1, 8); else F2V_W(6, 8, 1, 8); break;
-        case 64: if (o == 5) F2V_W(5, 16, 1, 8); else F2V_W(6, 16, 1, 8); break;
-        case 128: if (o == 5) F2V_W(5, 16, 2, 4); else F2V_W(6, 16, 2, 4); break;
-        default: if (o == 5) F2V_W(5, 16, 4, 4); else F2V_W(6, 16, 4, 4); break;
-    }
-#undef F2V_W
-#undef F2V_W2
-#undef F2V_W3
+    // MODE 2: epochs chained through the ring; 1: the EARLY form; 0: the plain one.  Always the table's rows in flight.
+    rc = dispatch_subwave<16, false>(c, math, plan.width, [&](auto O, auto L, auto N, auto U, auto FL) {
+        constexpr int OPT = decltype(O)::value, LPI = decltype(L)::value, NB = decltype(N)::value, UR = decltype(U)::value;
+        constexpr bool FULL = decltype(FL)::value;
+        if (ring) hipLaunchKernelGGL((qwide_chain_kernel<OPT, LPI, NB, UR, FULL, 2>), dim3(grid), dim3(256), 0, c->stream, wa);
+        else if (early) hipLaunchKernelGGL((qwide_chain_kernel<OPT, LPI, NB, UR, FULL, 1>), dim3(grid), dim3(256), 0, c->stream, wa);
+        else hipLaunchKernelGGL((qwide_chain_kernel<OPT, LPI, NB, UR, FULL, 0>), dim3(grid), dim3(256), 0, c->stream, wa);
+    });
+    if (rc != F2V_OK) return rc;
     HIPC(hipGetLastError());
-    if (ring) {  // the last epoch's matrix becomes the current one: nothing is pending
+    if (ring)  // the last epoch's matrix becomes the current one: nothing is pending
         HIPC(hipMemcpyAsync(c->d_X[c->cur], c->d_ring + (size_t)epochs * matrix, matrix * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-    } else {
-        if (c->upd_hi == c->upd_lo) c->upd_lo = plan.lo;
-        c->upd_hi = plan.hi;
-        c->pending = true;
-        c->p_lo = plan.last_lo;
-        c->p_hi = plan.hi;
-    }
-    c->stats.hub_rows += (uint64_t)plan.n_hubs * epochs;
-    c->stats.hub_chunks += (uint64_t)plan.n_chunks * epochs;
-    c->stats.step_launches += 1;
-    c->stats.rows += (uint64_t)(plan.hi - plan.lo) * epochs;
-    c->stats.nnz += plan.nnz * epochs;
-    c->stats.algorithmic_bytes += (plan.nnz * (4ull * c->D + 4) + (uint64_t)(plan.hi - plan.lo) * (8ull * c->D + 4) + (uint64_t)plan.n_batches * ns * (4ull * c->D + 4)) * epochs;
-    c->stats.compulsory_bytes += plan.compulsory * epochs;
+    record_launch(c, plan, plan.lo, plan.hi, plan.last_lo, plan.hi - plan.lo, (uint64_t)plan.n_batches * ns, epochs, !ring);
     return F2V_OK;
 }
 
@@ -1892,7 +1879,7 @@ int launch_barrier(f2v_ctx *c) {
     for (uint32_t r = 0; r < c->push.world; r++) b.peer_flags[r] = c->push.peer_flags[r];
     b.err = c->push.d_err;
     b.seq = ++c->push.seq;
-    b.timeout_ticks = (unsigned long long)c->push.timeout_ms * 100000ull;  // wall_clock64 ticks at 100 MHz
+    b.timeout_ticks = ms_to_ticks(c->push.timeout_ms);
     b.self = c->push.rank;
     b.world = c->push.world;
     hipLaunchKernelGGL(xgmi_barrier_kernel, dim3(1), dim3(64), 0, c->stream, b);
@@ -1975,6 +1962,155 @@ int prepare_masks(f2v_ctx *c, uint32_t batch, const std::vector<uint32_t> &ids) 
     HIPC(hipGetLastError());
     P.patched_ids.swap(uniq);
     return F2V_OK;
+}
+
+// ---- parameters (include/f2v.h: f2v_set_param / f2v_get_param) ----------------------------------------------------------------
+// before anything the launch plans were built from changes: nothing pending, nothing in flight
+int quiesce(f2v_ctx *c) {
+    HIPC(hipSetDevice(c->device));
+    int rc = flush_pending(c);
+    if (rc != F2V_OK) return rc;
+    HIPC(hipStreamSynchronize(c->stream));
+    return F2V_OK;
+}
+
+enum ParamKind { kValue, kFlag };            // kFlag: a switch -- every value is accepted, non-zero is on
+enum Replan { kKeep, kAlways, kOnChange };   // setting it quiesces the handle and drops its launch plans: never, always, where the value changes
+
+struct Param {
+    const char *name;
+    int64_t (*get)(const f2v_ctx *);       // nullptr: cannot be read
+    void (*put)(f2v_ctx *, int64_t);       // stores the value and does nothing else; nullptr (and no `set`): cannot be set
+    ParamKind kind = kValue;
+    Replan replan = kKeep;
+    bool (*valid)(int64_t) = nullptr;      // the accepted values (nullptr: all of them) ...
+    const char *error = nullptr;           // ... and what any other one is answered with (F2V_EINVAL)
+    int (*set)(f2v_ctx *, int64_t) = nullptr;  // after `valid`: runs instead of the plain rule (`replan` then says what it does)
+};
+
+template <int64_t LO, int64_t HI> bool in(int64_t v) { return v >= LO && v <= HI; }
+template <int64_t... S> bool one_of(int64_t v) { return ((v == S) || ...); }
+bool fanin_ok(int64_t v) { return v == 0 || in<2, 0x7FFFFFFF>(v); }
+
+int set_hub_chunk(f2v_ctx *c, int64_t value) {
+    int rc = quiesce(c);
+    if (rc != F2V_OK) return rc;
+    if (value > (int64_t)kItemSlotMask) return fail(F2V_EINVAL, "hub_chunk out of range");
+    // partial-sum slots are 28-bit: pieces plus the nodes of their combine trees must stay below 2^28
+    if (value > 0 && c->nnz / (uint64_t)value >= (1ull << 27)) return fail(F2V_EINVAL, "hub_chunk %lld is too small for %llu nonzeros", (long long)value, (unsigned long long)c->nnz);
+    c->chunk = (uint32_t)value;
+    c->chunk_auto = false;
+    drop_plans(c);
+    return F2V_OK;
+}
+
+int set_hub_chunk_for_batch(f2v_ctx *c, int64_t value) {  // resolve the automatic chunk for this batch size now
+    int rc = quiesce(c);
+    if (rc != F2V_OK) return rc;
+    const uint32_t ch = auto_chunk(c, (uint32_t)value);
+    if (ch != c->chunk) { c->chunk = ch; drop_plans(c); }
+    c->chunk_auto = true;
+    return F2V_OK;
+}
+
+int set_nearest_block(f2v_ctx *c, int64_t value) {
+    if (value == 128 && c->D > 128) return fail(F2V_EINVAL, "nearest_block = 128 needs dim <= 128 (the query block lives in LDS)");
+    c->nn.block = (uint32_t)value;
+    return F2V_OK;
+}
+
+int set_recover(f2v_ctx *c, int64_t value) {
+    c->recover = value != 0;
+    if (!c->recover && c->d_snap) {  // the snapshot matrix goes with the net
+        HIPC(hipSetDevice(c->device));
+        HIPC(hipStreamSynchronize(c->stream));
+        (void)hipFree(c->d_snap);
+        c->d_snap = nullptr;
+    }
+    return F2V_OK;
+}
+
+// a row's `get` and `put` where the parameter is one field of the handle
+#define F2V_READ(field) [](const f2v_ctx *c) -> int64_t { return (int64_t)c->field; }
+#define F2V_GET(field) F2V_READ(field), nullptr
+#define F2V_PUT(field) nullptr, [](f2v_ctx *c, int64_t v) { c->field = (decltype(c->field))v; }
+#define F2V_FIELD(field) F2V_READ(field), [](f2v_ctx *c, int64_t v) { c->field = (decltype(c->field))v; }
+const Param kParams[] = {
+    {"hub_chunk", F2V_FIELD(chunk), kValue, kAlways, in<0, 0x7FFFFFFF>, "hub_chunk out of range", set_hub_chunk},
+    {"hub_chunk_for_batch", nullptr, nullptr, kValue, kOnChange, in<1, 0xFFFFFFFFll>, "hub_chunk_for_batch: bad batch size", set_hub_chunk_for_batch},
+    {"hub_chunk_auto", F2V_GET(chunk_auto)},
+    {"hub_fanin", F2V_FIELD(fanin), kValue, kAlways, fanin_ok, "hub_fanin must be 0 (one sequential pass) or >= 2"},
+    {"quarter_wave", F2V_FIELD(use_quarter), kFlag, kOnChange},  // the item layout follows the kernel's items per workgroup
+    {"waves_per_block", F2V_FIELD(waves_per_block), kValue, kOnChange, one_of<1, 2, 4>, "waves_per_block must be 1, 2 or 4"},
+    {"rows_in_flight", F2V_PUT(rows_in_flight), kValue, kKeep, one_of<0, 4, 8>, "rows_in_flight must be 0 (default), 4 or 8"},
+    {"fast_rng", F2V_FIELD(fast_rng), kFlag},
+    {"use_graph", F2V_FIELD(use_graph), kFlag},
+    {"class_cut", F2V_FIELD(class_cut), kFlag, kAlways},
+    {"piece_affinity", F2V_FIELD(piece_affinity), kFlag, kOnChange},
+    {"count_compulsory", F2V_FIELD(count_compulsory), kFlag, kOnChange},
+    {"shared_card", F2V_GET(shared_card)},
+    {"merge_finalize", F2V_READ(merge_fin), [](f2v_ctx *c, int64_t v) { c->merge_fin = v != 0; c->waits_suspended = false; /* the caller's own choice stands */ }, kFlag},
+    {"tree_timeout_ms", F2V_FIELD(tree_timeout_ms), kValue, kKeep, in<1, 600000>, "tree_timeout_ms must be 1..600000"},
+    {"chain_timeout_ms", F2V_FIELD(chain_timeout_ms), kValue, kKeep, in<1, 600000>, "chain_timeout_ms must be 1..600000"},
+    {"recover", F2V_FIELD(recover), kFlag, kKeep, nullptr, nullptr, set_recover},
+    {"recoveries", F2V_GET(recoveries)},
+    {"chain_batches", F2V_FIELD(chain), kFlag},
+    {"chain_max_batch", F2V_FIELD(chain_max_batch), kValue, kKeep, in<0, 0xFFFFFFFFll>, "chain_max_batch out of range"},
+    // rows one chained launch covers: an explicit value holds for both forms ("wide_rows" alone: the wide form's)
+    {"chain_rows", F2V_READ(chain_rows), [](f2v_ctx *c, int64_t v) { c->chain_rows = c->wide_rows = (uint32_t)v; }, kValue, kAlways, in<2, 0x7FFFFFFF>, "chain_rows out of range"},
+    {"chain_wide", F2V_FIELD(wide), kFlag, kAlways},
+    {"wide_rows", F2V_FIELD(wide_rows), kValue, kAlways, in<2, 0x7FFFFFFF>, "wide_rows out of range"},
+    {"wide_max_batch", F2V_FIELD(wide_max_batch), kValue, kKeep, in<0, 0xFFFFFFFFll>, "wide_max_batch out of range"},
+    {"wide_min_width", F2V_FIELD(wide_min_width), kValue, kAlways, one_of<0, 16, 32, 64, 128>, "wide_min_width must be 0 (automatic), 16, 32, 64 or 128"},
+    {"wide_phases", F2V_FIELD(wide_phases), kValue, kAlways, in<1, 64>, "wide_phases must be 1..64"},
+    {"wide_span", F2V_FIELD(wide_span), kValue, kAlways, in<1, 64>, "wide_span must be 1..64"},
+    {"wide_finish", F2V_FIELD(wide_finish), kValue, kAlways, in<1, 64>, "wide_finish must be 1..64"},
+    {"wide_order", F2V_FIELD(wide_order), kValue, kAlways, in<0, 2>, "wide_order must be 0, 1 or 2"},
+    {"wide_rounds", F2V_FIELD(wide_rounds), kValue, kAlways, in<0, 64>, "wide_rounds must be 0..64"},
+    {"wide_epochs", F2V_FIELD(wide_epochs), kValue, kKeep, in<0, 1024>, "wide_epochs must be 0 (automatic) ... 1024"},
+    {"wide_single", F2V_FIELD(wide_single), kFlag},
+    {"wide_samples_early", F2V_FIELD(wide_samples_early), kValue, kKeep, in<-1, 1>, "wide_samples_early must be -1 (automatic), 0 or 1"},
+    {"replicate_small", F2V_FIELD(replicate_small), kValue, kKeep, in<0, 2>, "replicate_small must be 0 (never), 1 (where no peer shares the GPU) or 2 (always)"},
+    {"epoch_marks", F2V_FIELD(mark_every), kValue, kKeep, in<0, 0x7FFFFFFF>, "epoch_marks out of range"},
+    {"loss_every", F2V_FIELD(loss_every), kValue, kKeep, in<0, 0x7FFFFFFF>, "loss_every out of range"},
+    {"loss_seed", F2V_FIELD(loss_seed)},
+    {"last_loss_us", [](const f2v_ctx *c) { return (int64_t)(c->last_loss_us + 0.5); }, nullptr},
+    // candidate ranges a query block's work is cut into (0: chosen from nq and N); results do not depend on it
+    {"nearest_splits", F2V_FIELD(nn.splits), kValue, kKeep, in<0, 256>, "nearest_splits must be 0..256"},
+    // queries per workgroup (0: 128 where D <= 128 and more than 32 queries share a launch, else 32)
+    {"nearest_block", F2V_FIELD(nn.block), kValue, kKeep, one_of<0, 32, 128>, "nearest_block must be 0, 32 or 128", set_nearest_block},
+    // queries per launch: bounds the workspace (chunk x splits x k keys)
+    {"nearest_chunk", F2V_FIELD(nn.chunk), kValue, kKeep, in<1, 65536>, "nearest_chunk must be 1..65536"},
+    {"push_fused", F2V_FIELD(push.fused), kFlag},
+    {"push_timeout_ms", F2V_FIELD(push.timeout_ms), kValue, kKeep, in<1, 600000>, "push_timeout_ms must be 1..600000"},
+    // takes effect at the next f2v_push_export; read: what the exchange in place runs with
+    {"push_landing", [](const f2v_ctx *c) -> int64_t { return (c->push.attached || c->push.exported) ? c->push.landing : c->push.force_landing; },
+     [](f2v_ctx *c, int64_t v) { c->push.force_landing = v != 0; }, kFlag},
+    {"push_world", [](const f2v_ctx *c) -> int64_t { return c->push.attached ? c->push.world : 0; }, nullptr},
+    {"push_rank", F2V_GET(push.rank)},
+    {"last_train_replicated", F2V_GET(last_replicated)},
+    {"last_train_form", F2V_GET(last_train_form)},
+    {"last_wide_width", F2V_GET(last_wide_width)},
+    {"last_wide_early", F2V_GET(last_wide_early)},
+    {"last_wide_epochs", F2V_GET(last_wide_epochs)},
+    // launch plans resident on the host (and, uploaded, in HBM): items, jobs, workgroup descriptors, tree nodes
+    {"plan_resident_bytes", [](const f2v_ctx *c) { return (int64_t)(c->h_items.size() * sizeof(Item) + c->h_jobs.size() * sizeof(WJob) + c->h_wide.size() * sizeof(WideDesc) +
+                                                                    c->h_wg.size() * sizeof(WgDesc) + c->h_hubs.size() * sizeof(FinItem)); }, nullptr},
+    {"xcc_count", F2V_GET(xcc_count)},
+    {"xcc_round_robin", F2V_GET(xcc_round_robin)},
+    {"dim", F2V_GET(D)},
+    {"n", F2V_GET(n)},
+    {"nnz", F2V_GET(nnz)},
+};
+#undef F2V_READ
+#undef F2V_GET
+#undef F2V_PUT
+#undef F2V_FIELD
+
+const Param *find_param(const char *name) {
+    for (const Param &p : kParams)
+        if (!strcmp(p.name, name)) return &p;
+    return nullptr;
 }
 
 int train_impl(f2v_ctx *c, int option, uint32_t iters, uint32_t batch, uint32_t ns, float lr, int bs_mode, double *seconds_out, bool sharded);
@@ -2185,331 +2321,36 @@ int f2v_get_embeddings(f2v_handle c, float *x_out) {
     if (!c->have_x)
         return fail(F2V_ESTATE, c->x_invalid ? "f2v_get_embeddings: the embeddings are invalid since a launch gave up a bounded wait: set or initialise them again"
                                              : "f2v_get_embeddings: embeddings were never initialised");
-    HIPC(hipSetDevice(c->device));
-    int rc = flush_pending(c);
-    if (rc != F2V_OK) return rc;
-    HIPC(hipStreamSynchronize(c->stream));
-    if ((rc = check_kernel_err(c, "f2v_get_embeddings")) != F2V_OK) return rc;
+    int rc = quiesce(c);
+    if (rc != F2V_OK || (rc = check_kernel_err(c, "f2v_get_embeddings")) != F2V_OK) return rc;
     HIPC(hipMemcpy(x_out, c->d_X[c->cur], (size_t)c->n * c->D * sizeof(float), hipMemcpyDeviceToHost));
     return F2V_OK;
 }
 
 int f2v_set_param(f2v_handle c, const char *name, int64_t value) {
     if (!c || !name) return fail(F2V_EINVAL, "f2v_set_param: null argument");
-    if (!strcmp(name, "hub_chunk")) {
-        if (value < 0 || value > 0x7FFFFFFF) return fail(F2V_EINVAL, "hub_chunk out of range");
-        HIPC(hipSetDevice(c->device));
-        int rc = flush_pending(c);
+    const Param *p = find_param(name);
+    if (!p || (!p->put && !p->set)) return fail(F2V_EINVAL, "f2v_set_param: unknown parameter '%s'", name);
+    if (p->valid && !p->valid(value)) return fail(F2V_EINVAL, "%s", p->error);
+    if (p->kind == kFlag) value = value != 0;
+    if (p->set) return p->set(c, value);
+    if (p->replan == kAlways || (p->replan == kOnChange && p->get(c) != value)) {
+        int rc = quiesce(c);
         if (rc != F2V_OK) return rc;
-        HIPC(hipStreamSynchronize(c->stream));
-        if (value > (int64_t)kItemSlotMask) return fail(F2V_EINVAL, "hub_chunk out of range");
-        // partial-sum slots are 28-bit: pieces plus the nodes of their combine trees must stay below 2^28
-        if (value > 0 && c->nnz / (uint64_t)value >= (1ull << 27)) return fail(F2V_EINVAL, "hub_chunk %lld is too small for %llu nonzeros", (long long)value, (unsigned long long)c->nnz);
-        c->chunk = (uint32_t)value;
-        c->chunk_auto = false;
+        p->put(c, value);
         drop_plans(c);
-        return F2V_OK;
+    } else {
+        p->put(c, value);
     }
-    if (!strcmp(name, "hub_chunk_for_batch")) {  // resolve the automatic chunk for this batch size now
-        if (value <= 0 || value > 0xFFFFFFFFll) return fail(F2V_EINVAL, "hub_chunk_for_batch: bad batch size");
-        HIPC(hipSetDevice(c->device));
-        int rc = flush_pending(c);
-        if (rc != F2V_OK) return rc;
-        HIPC(hipStreamSynchronize(c->stream));
-        const uint32_t ch = auto_chunk(c, (uint32_t)value);
-        if (ch != c->chunk) { c->chunk = ch; drop_plans(c); }
-        c->chunk_auto = true;
-        return F2V_OK;
-    }
-    if (!strcmp(name, "hub_fanin")) {
-        if (value < 0 || value == 1 || value > 0x7FFFFFFF) return fail(F2V_EINVAL, "hub_fanin must be 0 (one sequential pass) or >= 2");
-        HIPC(hipSetDevice(c->device));
-        int rc = flush_pending(c);
-        if (rc != F2V_OK) return rc;
-        HIPC(hipStreamSynchronize(c->stream));
-        c->fanin = (uint32_t)value;
-        drop_plans(c);
-        return F2V_OK;
-    }
-    if (!strcmp(name, "quarter_wave")) {
-        if (c->use_quarter != (value != 0)) {  // the item layout follows the kernel's items per workgroup
-            HIPC(hipSetDevice(c->device));
-            int rc = flush_pending(c);
-            if (rc != F2V_OK) return rc;
-            HIPC(hipStreamSynchronize(c->stream));
-            c->use_quarter = value != 0;
-            drop_plans(c);
-        }
-        return F2V_OK;
-    }
-    if (!strcmp(name, "fast_rng")) {
-        c->fast_rng = value != 0;
-        return F2V_OK;
-    }
-    if (!strcmp(name, "use_graph")) {
-        c->use_graph = value != 0;
-        return F2V_OK;
-    }
-    if (!strcmp(name, "class_cut")) {
-        HIPC(hipSetDevice(c->device));
-        int rc = flush_pending(c);
-        if (rc != F2V_OK) return rc;
-        HIPC(hipStreamSynchronize(c->stream));
-        c->class_cut = value != 0;
-        drop_plans(c);
-        return F2V_OK;
-    }
-    if (!strcmp(name, "piece_affinity")) {
-        if (c->piece_affinity != (value != 0)) {
-            HIPC(hipSetDevice(c->device));
-            int rc = flush_pending(c);
-            if (rc != F2V_OK) return rc;
-            HIPC(hipStreamSynchronize(c->stream));
-            c->piece_affinity = value != 0;
-            drop_plans(c);
-        }
-        return F2V_OK;
-    }
-    if (!strcmp(name, "count_compulsory")) {
-        if (c->count_compulsory != (value != 0)) {
-            HIPC(hipSetDevice(c->device));
-            int rc = flush_pending(c);
-            if (rc != F2V_OK) return rc;
-            HIPC(hipStreamSynchronize(c->stream));
-            c->count_compulsory = value != 0;
-            drop_plans(c);
-        }
-        return F2V_OK;
-    }
-    if (!strcmp(name, "rows_in_flight")) {
-        if (value != 0 && value != 4 && value != 8) return fail(F2V_EINVAL, "rows_in_flight must be 0 (default), 4 or 8");
-        c->rows_in_flight = (int)value;
-        return F2V_OK;
-    }
-    if (!strcmp(name, "push_fused")) {
-        c->push.fused = value != 0;
-        return F2V_OK;
-    }
-    if (!strcmp(name, "merge_finalize")) {
-        c->merge_fin = value != 0;
-        c->waits_suspended = false;  // the caller's own choice stands
-        return F2V_OK;
-    }
-    if (!strcmp(name, "chain_batches")) {
-        c->chain = value != 0;
-        return F2V_OK;
-    }
-    if (!strcmp(name, "chain_max_batch")) {
-        if (value < 0 || value > 0xFFFFFFFFll) return fail(F2V_EINVAL, "chain_max_batch out of range");
-        c->chain_max_batch = (uint32_t)value;
-        return F2V_OK;
-    }
-    if (!strcmp(name, "wide_epochs")) {
-        if (value < 0 || value > 1024) return fail(F2V_EINVAL, "wide_epochs must be 0 (automatic) ... 1024");
-        c->wide_epochs = (uint32_t)value;
-        return F2V_OK;
-    }
-    if (!strcmp(name, "wide_single")) {
-        c->wide_single = value != 0;
-        return F2V_OK;
-    }
-    if (!strcmp(name, "replicate_small")) {
-        if (value < 0 || value > 2) return fail(F2V_EINVAL, "replicate_small must be 0 (never), 1 (where no peer shares the GPU) or 2 (always)");
-        c->replicate_small = (int)value;
-        return F2V_OK;
-    }
-    if (!strcmp(name, "wide_samples_early")) {
-        if (value < -1 || value > 1) return fail(F2V_EINVAL, "wide_samples_early must be -1 (automatic), 0 or 1");
-        c->wide_samples_early = (int)value;
-        return F2V_OK;
-    }
-    if (!strcmp(name, "wide_min_width")) {
-        if (value != 0 && value != 16 && value != 32 && value != 64 && value != 128) return fail(F2V_EINVAL, "wide_min_width must be 0 (automatic), 16, 32, 64 or 128");
-        HIPC(hipSetDevice(c->device));
-        int rc = flush_pending(c);
-        if (rc != F2V_OK) return rc;
-        HIPC(hipStreamSynchronize(c->stream));
-        c->wide_min_width = (uint32_t)value;
-        drop_plans(c);
-        return F2V_OK;
-    }
-    if (!strcmp(name, "wide_max_batch")) {
-        if (value < 0 || value > 0xFFFFFFFFll) return fail(F2V_EINVAL, "wide_max_batch out of range");
-        c->wide_max_batch = (uint32_t)value;
-        return F2V_OK;
-    }
-    if (!strcmp(name, "wide_rows")) {
-        if (value < 2 || value > 0x7FFFFFFFll) return fail(F2V_EINVAL, "wide_rows out of range");
-        HIPC(hipSetDevice(c->device));
-        int rc = flush_pending(c);
-        if (rc != F2V_OK) return rc;
-        HIPC(hipStreamSynchronize(c->stream));
-        c->wide_rows = (uint32_t)value;
-        drop_plans(c);
-        return F2V_OK;
-    }
-    if (!strcmp(name, "chain_rows")) {  // rows one chained launch covers
-        if (value < 2 || value > 0x7FFFFFFFll) return fail(F2V_EINVAL, "chain_rows out of range");
-        HIPC(hipSetDevice(c->device));
-        int rc = flush_pending(c);
-        if (rc != F2V_OK) return rc;
-        HIPC(hipStreamSynchronize(c->stream));
-        c->chain_rows = c->wide_rows = (uint32_t)value;  // an explicit value holds for both forms ("wide_rows" alone: the wide form's)
-        drop_plans(c);
-        return F2V_OK;
-    }
-    if (!strcmp(name, "tree_timeout_ms")) {
-        if (value < 1 || value > 600000) return fail(F2V_EINVAL, "tree_timeout_ms must be 1..600000");
-        c->tree_timeout_ms = value;
-        return F2V_OK;
-    }
-    if (!strcmp(name, "epoch_marks")) {
-        if (value < 0 || value > 0x7FFFFFFF) return fail(F2V_EINVAL, "epoch_marks out of range");
-        c->mark_every = (uint32_t)value;
-        return F2V_OK;
-    }
-    if (!strcmp(name, "chain_wide") || !strcmp(name, "wide_phases") || !strcmp(name, "wide_span") || !strcmp(name, "wide_finish") || !strcmp(name, "wide_order") || !strcmp(name, "wide_rounds")) {
-        if (name[0] == 'w' && strcmp(name, "wide_order") && strcmp(name, "wide_rounds") && (value < 1 || value > 64)) return fail(F2V_EINVAL, "%s must be 1..64", name);
-        if (!strcmp(name, "wide_rounds") && (value < 0 || value > 64)) return fail(F2V_EINVAL, "wide_rounds must be 0..64");
-        if (!strcmp(name, "wide_order") && (value < 0 || value > 2)) return fail(F2V_EINVAL, "wide_order must be 0, 1 or 2");
-        HIPC(hipSetDevice(c->device));
-        int rc = flush_pending(c);
-        if (rc != F2V_OK) return rc;
-        HIPC(hipStreamSynchronize(c->stream));
-        if (!strcmp(name, "chain_wide")) c->wide = value != 0;
-        else if (!strcmp(name, "wide_phases")) c->wide_phases = (uint32_t)value;
-        else if (!strcmp(name, "wide_span")) c->wide_span = (uint32_t)value;
-        else if (!strcmp(name, "wide_order")) c->wide_order = (uint32_t)value;
-        else if (!strcmp(name, "wide_rounds")) c->wide_rounds = (uint32_t)value;
-        else c->wide_finish = (uint32_t)value;
-        drop_plans(c);
-        return F2V_OK;
-    }
-    if (!strcmp(name, "loss_every")) {
-        if (value < 0 || value > 0x7FFFFFFF) return fail(F2V_EINVAL, "loss_every out of range");
-        c->loss_every = (uint32_t)value;
-        return F2V_OK;
-    }
-    if (!strcmp(name, "loss_seed")) {
-        c->loss_seed = (uint64_t)value;
-        return F2V_OK;
-    }
-    if (!strcmp(name, "nearest_splits")) {  // candidate ranges a query block's work is cut into (0: chosen from nq and N); results do not depend on it
-        if (value < 0 || value > 256) return fail(F2V_EINVAL, "nearest_splits must be 0..256");
-        c->nn.splits = (uint32_t)value;
-        return F2V_OK;
-    }
-    if (!strcmp(name, "nearest_block")) {  // queries per workgroup (0: 128 where D <= 128 and more than 32 queries share a launch, else 32)
-        if (value != 0 && value != 32 && value != 128) return fail(F2V_EINVAL, "nearest_block must be 0, 32 or 128");
-        if (value == 128 && c->D > 128) return fail(F2V_EINVAL, "nearest_block = 128 needs dim <= 128 (the query block lives in LDS)");
-        c->nn.block = (uint32_t)value;
-        return F2V_OK;
-    }
-    if (!strcmp(name, "nearest_chunk")) {  // queries per launch: bounds the workspace (chunk x splits x k keys)
-        if (value < 1 || value > 65536) return fail(F2V_EINVAL, "nearest_chunk must be 1..65536");
-        c->nn.chunk = (uint32_t)value;
-        return F2V_OK;
-    }
-    if (!strcmp(name, "chain_timeout_ms")) {
-        if (value < 1 || value > 600000) return fail(F2V_EINVAL, "chain_timeout_ms must be 1..600000");
-        c->chain_timeout_ms = value;
-        return F2V_OK;
-    }
-    if (!strcmp(name, "recover")) {
-        c->recover = value != 0;
-        if (!c->recover && c->d_snap) {  // the snapshot matrix goes with the net
-            HIPC(hipSetDevice(c->device));
-            HIPC(hipStreamSynchronize(c->stream));
-            (void)hipFree(c->d_snap);
-            c->d_snap = nullptr;
-        }
-        return F2V_OK;
-    }
-    if (!strcmp(name, "push_landing")) {  // takes effect at the next f2v_push_export
-        c->push.force_landing = value != 0;
-        return F2V_OK;
-    }
-    if (!strcmp(name, "push_timeout_ms")) {
-        if (value < 1 || value > 600000) return fail(F2V_EINVAL, "push_timeout_ms must be 1..600000");
-        c->push.timeout_ms = value;
-        return F2V_OK;
-    }
-    if (!strcmp(name, "waves_per_block")) {
-        if (value != 1 && value != 2 && value != 4) return fail(F2V_EINVAL, "waves_per_block must be 1, 2 or 4");
-        if (c->waves_per_block != (int)value) {
-            HIPC(hipSetDevice(c->device));
-            int rc = flush_pending(c);
-            if (rc != F2V_OK) return rc;
-            HIPC(hipStreamSynchronize(c->stream));
-            c->waves_per_block = (int)value;
-            drop_plans(c);
-        }
-        return F2V_OK;
-    }
-    return fail(F2V_EINVAL, "f2v_set_param: unknown parameter '%s'", name);
+    return F2V_OK;
 }
 
 int f2v_get_param(f2v_handle c, const char *name, int64_t *out) {
     if (!c || !name || !out) return fail(F2V_EINVAL, "f2v_get_param: null argument");
-    if (!strcmp(name, "hub_chunk")) { *out = c->chunk; return F2V_OK; }
-    if (!strcmp(name, "waves_per_block")) { *out = c->waves_per_block; return F2V_OK; }
-    if (!strcmp(name, "quarter_wave")) { *out = c->use_quarter ? 1 : 0; return F2V_OK; }
-    if (!strcmp(name, "hub_fanin")) { *out = c->fanin; return F2V_OK; }
-    if (!strcmp(name, "fast_rng")) { *out = c->fast_rng ? 1 : 0; return F2V_OK; }
-    if (!strcmp(name, "use_graph")) { *out = c->use_graph ? 1 : 0; return F2V_OK; }
-    if (!strcmp(name, "count_compulsory")) { *out = c->count_compulsory ? 1 : 0; return F2V_OK; }
-    if (!strcmp(name, "piece_affinity")) { *out = c->piece_affinity ? 1 : 0; return F2V_OK; }
-    if (!strcmp(name, "class_cut")) { *out = c->class_cut ? 1 : 0; return F2V_OK; }
-    if (!strcmp(name, "shared_card")) { *out = c->shared_card ? 1 : 0; return F2V_OK; }
-    if (!strcmp(name, "hub_chunk_auto")) { *out = c->chunk_auto ? 1 : 0; return F2V_OK; }
-    if (!strcmp(name, "push_timeout_ms")) { *out = c->push.timeout_ms; return F2V_OK; }
-    if (!strcmp(name, "push_fused")) { *out = c->push.fused ? 1 : 0; return F2V_OK; }
-    if (!strcmp(name, "merge_finalize")) { *out = c->merge_fin ? 1 : 0; return F2V_OK; }
-    if (!strcmp(name, "tree_timeout_ms")) { *out = c->tree_timeout_ms; return F2V_OK; }
-    if (!strcmp(name, "chain_batches")) { *out = c->chain ? 1 : 0; return F2V_OK; }
-    if (!strcmp(name, "chain_timeout_ms")) { *out = c->chain_timeout_ms; return F2V_OK; }
-    if (!strcmp(name, "chain_wide")) { *out = c->wide ? 1 : 0; return F2V_OK; }
-    if (!strcmp(name, "epoch_marks")) { *out = c->mark_every; return F2V_OK; }
-    if (!strcmp(name, "loss_every")) { *out = c->loss_every; return F2V_OK; }
-    if (!strcmp(name, "loss_seed")) { *out = (int64_t)c->loss_seed; return F2V_OK; }
-    if (!strcmp(name, "nearest_splits")) { *out = c->nn.splits; return F2V_OK; }
-    if (!strcmp(name, "nearest_block")) { *out = c->nn.block; return F2V_OK; }
-    if (!strcmp(name, "nearest_chunk")) { *out = c->nn.chunk; return F2V_OK; }
-    if (!strcmp(name, "last_loss_us")) { *out = (int64_t)(c->last_loss_us + 0.5); return F2V_OK; }
-    if (!strcmp(name, "wide_phases")) { *out = c->wide_phases; return F2V_OK; }
-    if (!strcmp(name, "wide_max_batch")) { *out = c->wide_max_batch; return F2V_OK; }
-    if (!strcmp(name, "wide_min_width")) { *out = c->wide_min_width; return F2V_OK; }
-    if (!strcmp(name, "wide_single")) { *out = c->wide_single ? 1 : 0; return F2V_OK; }
-    if (!strcmp(name, "replicate_small")) { *out = c->replicate_small; return F2V_OK; }
-    if (!strcmp(name, "last_train_replicated")) { *out = c->last_replicated ? 1 : 0; return F2V_OK; }
-    if (!strcmp(name, "plan_resident_bytes")) {  // launch plans resident on the host (and, uploaded, in HBM): items, jobs, workgroup descriptors, tree nodes
-        *out = (int64_t)(c->h_items.size() * sizeof(Item) + c->h_jobs.size() * sizeof(WJob) + c->h_wide.size() * sizeof(WideDesc) + c->h_wg.size() * sizeof(WgDesc) + c->h_hubs.size() * sizeof(FinItem));
-        return F2V_OK;
-    }
-    if (!strcmp(name, "wide_samples_early")) { *out = c->wide_samples_early; return F2V_OK; }
-    if (!strcmp(name, "wide_epochs")) { *out = c->wide_epochs; return F2V_OK; }
-    if (!strcmp(name, "last_wide_epochs")) { *out = c->last_wide_epochs; return F2V_OK; }
-    if (!strcmp(name, "wide_rows")) { *out = c->wide_rows; return F2V_OK; }
-    if (!strcmp(name, "wide_span")) { *out = c->wide_span; return F2V_OK; }
-    if (!strcmp(name, "wide_order")) { *out = c->wide_order; return F2V_OK; }
-    if (!strcmp(name, "wide_rounds")) { *out = c->wide_rounds; return F2V_OK; }
-    if (!strcmp(name, "wide_finish")) { *out = c->wide_finish; return F2V_OK; }
-    if (!strcmp(name, "last_train_form")) { *out = c->last_train_form; return F2V_OK; }
-    if (!strcmp(name, "last_wide_width")) { *out = c->last_wide_width; return F2V_OK; }
-    if (!strcmp(name, "last_wide_early")) { *out = c->last_wide_early ? 1 : 0; return F2V_OK; }
-    if (!strcmp(name, "recover")) { *out = c->recover ? 1 : 0; return F2V_OK; }
-    if (!strcmp(name, "recoveries")) { *out = c->recoveries; return F2V_OK; }
-    if (!strcmp(name, "chain_max_batch")) { *out = c->chain_max_batch; return F2V_OK; }
-    if (!strcmp(name, "chain_rows")) { *out = c->chain_rows; return F2V_OK; }
-    if (!strcmp(name, "xcc_count")) { *out = c->xcc_count; return F2V_OK; }
-    if (!strcmp(name, "xcc_round_robin")) { *out = c->xcc_round_robin ? 1 : 0; return F2V_OK; }
-    if (!strcmp(name, "push_landing")) { *out = (c->push.attached || c->push.exported) ? (c->push.landing ? 1 : 0) : (c->push.force_landing ? 1 : 0); return F2V_OK; }
-    if (!strcmp(name, "push_world")) { *out = c->push.attached ? c->push.world : 0; return F2V_OK; }
-    if (!strcmp(name, "push_rank")) { *out = c->push.rank; return F2V_OK; }
-    if (!strcmp(name, "dim")) { *out = c->D; return F2V_OK; }
-    if (!strcmp(name, "n")) { *out = c->n; return F2V_OK; }
-    if (!strcmp(name, "nnz")) { *out = (int64_t)c->nnz; return F2V_OK; }
-    return fail(F2V_EINVAL, "f2v_get_param: unknown parameter '%s'", name);
+    const Param *p = find_param(name);
+    if (!p || !p->get) return fail(F2V_EINVAL, "f2v_get_param: unknown parameter '%s'", name);
+    *out = p->get(c);
+    return F2V_OK;
 }
 
 int f2v_set_walks(f2v_handle c, const uint32_t *walks) {
@@ -2615,11 +2456,8 @@ int f2v_minibatch_step_at(f2v_handle c, int option, uint32_t batch_lo, uint32_t 
 
 int f2v_flush(f2v_handle c) {
     if (!c) return fail(F2V_EINVAL, "null handle");
-    HIPC(hipSetDevice(c->device));
-    int rc = flush_pending(c);
-    if (rc != F2V_OK) return rc;
-    HIPC(hipStreamSynchronize(c->stream));
-    return check_kernel_err(c, "f2v_flush");
+    int rc = quiesce(c);
+    return rc != F2V_OK ? rc : check_kernel_err(c, "f2v_flush");
 }
 
 int f2v_synchronize(f2v_handle c) {
@@ -2872,8 +2710,7 @@ int train_impl(f2v_ctx *c, int option, uint32_t iters, uint32_t batch, uint32_t 
         // order: results are bit-identical for any world size GIVEN the chunk ("hub_chunk" pins it).
         const uint32_t ch = auto_chunk(c, sharded ? (batch + c->push.world - 1) / c->push.world : batch);
         if (ch != c->chunk) {
-            if ((rc = flush_pending(c)) != F2V_OK) return rc;
-            HIPC(hipStreamSynchronize(c->stream));
+            if ((rc = quiesce(c)) != F2V_OK) return rc;
             c->chunk = ch;
             drop_plans(c);
         }
@@ -3044,7 +2881,7 @@ int train_impl(f2v_ctx *c, int option, uint32_t iters, uint32_t batch, uint32_t 
         }
         // the host-side bookkeeping now stands where two executed epochs leave it; one epoch's statistics were counted twice
         f2v_stats one = c->stats;
-        one.step_launches /= 2; one.rows /= 2; one.nnz /= 2; one.algorithmic_bytes /= 2; one.hub_rows /= 2; one.hub_chunks /= 2; one.compulsory_bytes /= 2;
+        scale_stats(one, 1, 2);
         HIPC(hipEventRecord(ev0, c->stream));
         for (uint32_t it = 0; it < iters; it++) {
             if (it >= 2)
@@ -3055,8 +2892,7 @@ int train_impl(f2v_ctx *c, int option, uint32_t iters, uint32_t batch, uint32_t 
         }
         if (iters & 1) c->cur ^= 1;  // an odd number of epochs ends on the other matrix than the two captured ones did
         c->stats = one;
-        c->stats.step_launches *= iters; c->stats.rows *= iters; c->stats.nnz *= iters; c->stats.algorithmic_bytes *= iters; c->stats.compulsory_bytes *= iters;
-        c->stats.hub_rows *= iters; c->stats.hub_chunks *= iters;
+        scale_stats(c->stats, iters, 1);
         HIPC(hipStreamSynchronize(c->stream));
         for (int par = 0; par < 2; par++) { (void)hipGraphExecDestroy(exec[par]); (void)hipGraphDestroy(graph[par]); }
     }
@@ -3655,21 +3491,13 @@ int f2v_test_wide_plan_check(const uint32_t *rowptr, const uint32_t *colids, uin
     c->rowptr.assign(rowptr, rowptr + n + 1);
     c->colids.assign(colids, colids + nnz);
     c->chunk = auto_chunk(c, batch);
+    // overrides go into the handle's fields as f2v_set_param would store them (no device is there to quiesce); only what the planner reads
+    static const char *const planner_reads[] = {"hub_chunk", "hub_fanin", "class_cut", "wide_phases", "wide_rounds", "wide_span", "wide_finish", "wide_order", "wide_rows", "wide_min_width"};
     for (uint32_t k = 0; k < n_params; k++) {
-        const std::string nm = names[k];
-        const int64_t v = values[k];
-        if (nm == "hub_chunk") c->chunk = (uint32_t)v;
-        else if (nm == "hub_fanin") c->fanin = (uint32_t)v;
-        else if (nm == "class_cut") c->class_cut = v != 0;
-        else if (nm == "wide_phases") c->wide_phases = (uint32_t)v;
-        else if (nm == "wide_rounds") c->wide_rounds = (uint32_t)v;
-        else if (nm == "wide_span") c->wide_span = (uint32_t)v;
-        else if (nm == "wide_finish") c->wide_finish = (uint32_t)v;
-        else if (nm == "wide_order") c->wide_order = (uint32_t)v;
-        else if (nm == "wide_rows") c->wide_rows = (uint32_t)v;
-        else if (nm == "wide_min_width") c->wide_min_width = (uint32_t)v;
-        else if (nm == "plan_threads") plan_threads = (unsigned)v;  // build the epoch's plans on this many host threads (wide_plans_for_epoch)
-        else return fail(F2V_EINVAL, "f2v_test_wide_plan_check: unknown parameter '%s'", nm.c_str());
+        const char *nm = names[k];
+        if (!strcmp(nm, "plan_threads")) plan_threads = (unsigned)values[k];  // build the epoch's plans on this many host threads (wide_plans_for_epoch)
+        else if (std::any_of(std::begin(planner_reads), std::end(planner_reads), [&](const char *r) { return !strcmp(r, nm); })) find_param(nm)->put(c, values[k]);
+        else return fail(F2V_EINVAL, "f2v_test_wide_plan_check: unknown parameter '%s'", nm);
     }
     if (!wide_usable(c) || subwave_width(c) == 0) return fail(F2V_EINVAL, "f2v_test_wide_plan_check: the wide form does not run this shape");
     const uint32_t nb = (uint32_t)(((uint64_t)n + batch - 1) / batch), K = chain_len(c, batch, true);
