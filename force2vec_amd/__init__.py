@@ -11,11 +11,15 @@ its last, read back with `Engine.train_losses()`.
 
 Queries: `Engine.nearest(ids=..., k=10, metric="dot" | "l2" | "cos")` returns the k most similar rows of
 the matrix for each query (rows or caller-supplied vectors) without the matrix leaving the GPU;
-`Engine.neighbour_recall(k, metric)` is the graph-reconstruction precision@k."""
+`Engine.neighbour_recall(k, metric)` is the graph-reconstruction precision@k.
+
+Clustering: `Engine.kmeans(k, max_iters=300, seed=1, restarts=1)` runs Lloyd's k-means on the rows of the matrix on the GPU
+(deterministic: include/f2v.h), `Engine.modularity(labels)` scores a labelling on the input graph."""
 from . import _lib  # noqa: F401
 from ._lib import F2VError  # noqa: F401
+from ._lib import KMEANS_MAX_K, KMEANS_PIECE  # noqa: F401
 from ._lib import NEAREST_EXCLUDE_NEIGHBOURS, NEAREST_EXCLUDE_SELF, NEAREST_MAX_K, NEAREST_PAD_ID, SIM_COSINE, SIM_DOT, SIM_L2  # noqa: F401
-from .engine import Engine, algorithms, output_name, push_masks, read_embd, read_embd_bin, sm_table, write_embd, write_embd_bin  # noqa: F401
+from .engine import Engine, KMeans, Modularity, algorithms, output_name, push_masks, read_embd, read_embd_bin, sm_table, write_embd, write_embd_bin  # noqa: F401
 from .graph import read_csr_bin, read_mtx, rmat_csr, write_csr_bin  # noqa: F401
 
-__all__ = ["Engine", "F2VError", "algorithms", "read_mtx", "rmat_csr", "write_embd", "output_name", "sm_table"]
+__all__ = ["Engine", "F2VError", "KMeans", "Modularity", "algorithms", "read_mtx", "rmat_csr", "write_embd", "output_name", "sm_table"]

@@ -14,6 +14,7 @@ SIM_DOT, SIM_L2, SIM_COSINE = 0, 1, 2
 NEAREST_MAX_K = 128
 NEAREST_EXCLUDE_SELF, NEAREST_EXCLUDE_NEIGHBOURS = 1, 2
 NEAREST_PAD_ID = 0xFFFFFFFF  # id of a slot past the last candidate (its score is -inf)
+KMEANS_MAX_K, KMEANS_PIECE = 1024, 64
 
 u32p = C.POINTER(C.c_uint32)
 f32p = C.POINTER(C.c_float)
@@ -29,6 +30,11 @@ class Stats(C.Structure):
 class Objective(C.Structure):  # f2v_objective_t
     _fields_ = [("loss", C.c_double), ("attraction", C.c_double), ("repulsion", C.c_double),
                 ("positive_pairs", C.c_uint64), ("negative_pairs", C.c_uint64)]
+
+
+class KMeansInfo(C.Structure):  # f2v_kmeans_t
+    _fields_ = [("inertia", C.c_double), ("seconds", C.c_double), ("iterations", C.c_uint32), ("converged", C.c_uint32),
+                ("restart", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 # every entry point declared in include/f2v.h: name -> (restype, argtypes)
@@ -68,6 +74,8 @@ SIGNATURES = {
     "f2v_nearest_rows": (C.c_int, [C.c_void_p, u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, u32p, f32p, C.POINTER(C.c_double)]),
     "f2v_nearest_vectors": (C.c_int, [C.c_void_p, f32p, C.c_uint32, C.c_uint32, C.c_int, u32p, f32p, C.POINTER(C.c_double)]),
     "f2v_neighbour_recall": (C.c_int, [C.c_void_p, u32p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "f2v_kmeans": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, f32p, u32p, f32p, C.POINTER(C.c_uint64), C.POINTER(KMeansInfo)]),
+    "f2v_modularity": (C.c_int, [C.c_void_p, u32p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "f2v_push_export": (C.c_int, [C.c_void_p, C.c_void_p]),
     "f2v_push_attach": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "f2v_push_selftest": (C.c_int, [C.c_void_p]),

@@ -168,6 +168,22 @@ class algorithms {
         printf("Nearest: k=%u metric=%s %.6f s, precision@k %llu/%llu\n", k, metric_name, seconds, (unsigned long long)hits, (unsigned long long)possible);
     }
 
+    // -cluster <k>: k-means on the trained matrix (f2v_kmeans: `restarts` seeded runs from `seed`, the one of lowest inertia) as
+    // "<embd output name>.clu", one line "v label" per vertex (0-based ids), then the modularity of that labelling on the graph.
+    void writeClusters(uint32_t k, uint32_t iters, uint32_t restarts, uint64_t seed) {
+        std::vector<uint32_t> labels(rows);
+        f2v_kmeans_t info{};
+        check(f2v_kmeans(h, k, iters, restarts, seed, nullptr, labels.data(), nullptr, nullptr, &info));
+        double q = 0.0;
+        check(f2v_modularity(h, labels.data(), k, &q, nullptr, nullptr, nullptr));
+        const std::string name = last_output + ".clu";
+        FILE *f = fopen(name.c_str(), "w");
+        if (!f) throw std::runtime_error("cannot write " + name);
+        for (uint32_t v = 0; v < rows; v++) fprintf(f, "%u %u\n", v, labels[v]);
+        if (fclose(f) != 0) throw std::runtime_error("cannot write " + name);
+        printf("Clusters:%u :MODULARITY: %.17g :INERTIA: %.17g :ITERATIONS: %u :RESTART: %u\n", k, q, info.inertia, info.iterations, info.restart);
+    }
+
     // writeToFile, sample/algorithms.h:118-136 (file name rule in f2v_output_name)
     void writeToFile(int option, int bs, INDEXTYPE B, INDEXTYPE IT, INDEXTYPE ns) {
         char name[4096];

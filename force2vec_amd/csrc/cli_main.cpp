@@ -9,7 +9,8 @@
 // f2v_train_sharded; the ranks meet through files in a private temporary directory; same output, written by rank 0),
 // -loss <k> (print the training objective after every k-th epoch and the last, in the line the reference has commented out),
 // -nearest <k> [-metric dot|l2|cos] (after training: every vertex's k nearest rows as "<embd output name>.nn" and the
-// graph-reconstruction precision@k; default metric: the option's own similarity).
+// graph-reconstruction precision@k; default metric: the option's own similarity), -cluster <k> [-cluster-iters <n>]
+// [-cluster-restarts <r>] (after training: k-means on the embedding as "<embd output name>.clu" and its modularity on the graph).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -30,7 +31,7 @@ namespace {
 struct Settings {
     std::string input, output, init;
     long batch = 384, iter = 1200, threads = (long)std::thread::hardware_concurrency(), dim = 128, nsamples = 5, option = 5, bs = 0;
-    long device = 0, seed = 1, cache = 0, binout = 0, fastrng = 0, notext = 0, gpus = 1, samegpu = 0, loss = 0, nearest = 0;
+    long device = 0, seed = 1, cache = 0, binout = 0, fastrng = 0, notext = 0, gpus = 1, samegpu = 0, loss = 0, nearest = 0, cluster = 0, cluster_iters = 300, cluster_restarts = 10;
     std::string metric;
     double gamma = 1.0, lr = 0.02;
 };
@@ -95,6 +96,9 @@ int main(int argc, char *argv[]) {
         {"-fastrng", Kind::Integer, &s.fastrng, "<int>, 1 = NON-PARITY fast mode: initial embeddings and option-7 walks from a device-side RNG."},
         {"-loss", Kind::Integer, &s.loss, "<int>, k > 0: print \"Iteration:<epoch> :LOGLIKELIHOOD: <loss>\" after every k-th epoch and the last (the training objective, include/f2v.h; one GPU). (default:0)"},
         {"-nearest", Kind::Integer, &s.nearest, "<int>, k in 1..128: after training write <output file>.nn, one line per vertex \"v j1 s1 ... jk sk\" (its k nearest rows, self excluded), and print the precision@k against the graph (one GPU). (default:0)"},
+        {"-cluster", Kind::Integer, &s.cluster, "<int>, k in 1..1024: after training cluster the embedding with k-means on the GPU, write <output file>.clu, one line per vertex \"v label\" (0-based), and print the clustering's modularity on the graph (one GPU; seeded by -seed). (default:0)"},
+        {"-cluster-iters", Kind::Integer, &s.cluster_iters, "<int>, most Lloyd iterations of a -cluster run. (default:300)"},
+        {"-cluster-restarts", Kind::Integer, &s.cluster_restarts, "<int>, seeded runs of -cluster, the one of lowest inertia is kept (the scorer's n_init). (default:10)"},
         {"-metric", Kind::Text, &s.metric, "<string>, similarity of -nearest: dot | l2 | cos. (default: l2 for options 5, 8, 11, dot for the sigmoid options)"},
     };
     const size_t nflags = sizeof flags / sizeof flags[0];
@@ -153,6 +157,22 @@ int main(int argc, char *argv[]) {
         printf("-nearest is not available with -gpus > 1 (it queries one GPU's matrix).\n");
         return 1;
     }
+    if (s.cluster < 0 || s.cluster > F2V_KMEANS_MAX_K) {
+        printf("-cluster must be 0..%d.\n", F2V_KMEANS_MAX_K);
+        return 1;
+    }
+    if (s.cluster > 0 && (s.cluster_restarts < 1 || s.cluster_restarts > 0x7FFFFFFF)) {
+        printf("-cluster-restarts must be at least 1.\n");
+        return 1;
+    }
+    if (s.cluster > 0 && (s.cluster_iters < 0 || s.cluster_iters > 0x7FFFFFFF)) {
+        printf("-cluster-iters must be a non-negative number of iterations.\n");
+        return 1;
+    }
+    if (s.cluster > 0 && s.gpus > 1) {
+        printf("-cluster is not available with -gpus > 1 (it clusters one GPU's matrix).\n");
+        return 1;
+    }
     std::vector<VALUETYPE> seconds;
     int rank = 0;
     std::string meet;  // directory the ranks of a -gpus run meet in
@@ -195,6 +215,7 @@ int main(int argc, char *argv[]) {
                 for (uint32_t m = 0; m < count; m++) std::cout << "Iteration:" << epochs[m] << " :LOGLIKELIHOOD: " << values[3 * m] << std::endl;
             }
             if (s.nearest > 0 && rank == 0) algo.writeNearest((uint32_t)s.nearest, metric, s.metric.c_str());
+            if (s.cluster > 0 && rank == 0) algo.writeClusters((uint32_t)s.cluster, (uint32_t)s.cluster_iters, (uint32_t)s.cluster_restarts, (uint64_t)s.seed);
             const double t = algo.gpu_train_seconds;
             if (rank == 0 && s.gpus == 1)
                 printf("GPU epoch loop: %.6f s, %.4g nnz/s, %.1f GB/s algorithmic\n", t, t > 0 ? algo.stats.nnz / t : 0.0,

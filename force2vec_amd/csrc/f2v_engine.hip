@@ -33,6 +33,7 @@
 #include "f2v_internal.h"
 #include "f2v_kernels.hip.h"
 #include "f2v_nearest.hip.h"
+#include "f2v_kmeans.hip.h"
 
 using namespace f2v;
 
@@ -160,8 +161,21 @@ struct f2v_ctx {
         hipEvent_t ev[2] = {nullptr, nullptr};
         uint32_t splits = 0, block = 0, chunk = 8192;
         uint32_t lds_allowed = 0;  // nearest_kernel instantiations whose dynamic-LDS limit has been raised (launch_nearest_t)
-        int rows_sorted = -1;      // the CSR's ids ascend inside every row: -1 not checked yet (nearest_enter)
     } nn;
+    int rows_sorted = -1;  // the CSR's ids ascend inside every row (rows are searched by the nearest queries and f2v_modularity): -1 not checked yet (rows_ascending)
+    // clustering (f2v_kmeans, f2v_modularity): the workspace f2v.h states, allocated on first use for the call's k and grown for a
+    // larger one; "kmeans_block" (0 = from k | 64 | 128 | 256): rows per workgroup of kmeans_assign_kernel
+    struct Kmeans {
+        float *d_C = nullptr, *d_bestC = nullptr, *d_dist = nullptr;
+        uint32_t *d_labels = nullptr, *d_bestL = nullptr, *d_order = nullptr, *d_hist = nullptr, *d_counts = nullptr, *d_start = nullptr,
+                 *d_pstart = nullptr, *d_changed = nullptr, *d_seed = nullptr, *d_mlabels = nullptr;
+        double *d_psum = nullptr, *d_ipart = nullptr, *d_inertia = nullptr;
+        unsigned long long *d_tallies = nullptr;
+        uint32_t cap_k = 0, cap_nc = 0;  // the k the buffers hold, the communities d_tallies holds
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        uint32_t block = 0;
+        uint32_t lds_allowed = 0;  // kmeans_assign_kernel instantiations whose dynamic-LDS limit has been raised
+    } km;
     uint32_t last_wide_width = 0;  // the layout width of the last wide-form f2v_train ("last_wide_width")
     bool last_wide_early = false;  // ... and whether it ran the kernel's EARLY form ("last_wide_early")
     int last_train_form = 0;  // how the last f2v_train launched: 0 one launch per minibatch, 1 chained, 2 chained in the wide form ("last_train_form")
@@ -2081,6 +2095,8 @@ const Param kParams[] = {
     {"nearest_block", F2V_FIELD(nn.block), kValue, kKeep, one_of<0, 32, 128>, "nearest_block must be 0, 32 or 128", set_nearest_block},
     // queries per launch: bounds the workspace (chunk x splits x k keys)
     {"nearest_chunk", F2V_FIELD(nn.chunk), kValue, kKeep, in<1, 65536>, "nearest_chunk must be 1..65536"},
+    // rows per workgroup of the k-means assignment kernel (0: 256 for k <= 2, 128 for k <= 4, else 64); results do not depend on it
+    {"kmeans_block", F2V_FIELD(km.block), kValue, kKeep, one_of<0, 64, 128, 256>, "kmeans_block must be 0, 64, 128 or 256"},
     {"push_fused", F2V_FIELD(push.fused), kFlag},
     {"push_timeout_ms", F2V_FIELD(push.timeout_ms), kValue, kKeep, in<1, 600000>, "push_timeout_ms must be 1..600000"},
     // takes effect at the next f2v_push_export; read: what the exchange in place runs with
@@ -2212,7 +2228,9 @@ int f2v_destroy(f2v_handle c) {
     (void)push_detach(c);
     void *ptrs[] = {c->d_rowptr, c->d_colids, c->d_walks, c->d_walks_alt, c->d_ids, c->d_X[0], c->d_X[1],
                     c->d_partials, c->d_table, c->d_items, c->d_hubs, c->d_ready, c->d_kerr, c->d_wg, c->d_rowflag, c->d_snap, c->d_wide, c->d_jobs, c->d_ring, c->d_ring_partials, c->d_ring_flags, c->d_ring_ready, c->d_obj_items, c->d_obj_part, c->d_obj_out, c->push.flags, c->push.d_err, c->push.d_masks, c->push.d_patch, c->push.landing_buf,
-                    c->nn.d_Q, c->nn.d_rq, c->nn.d_rc, c->nn.d_scores, c->nn.d_qids, c->nn.d_ids, c->nn.d_ws, c->nn.d_counts};
+                    c->nn.d_Q, c->nn.d_rq, c->nn.d_rc, c->nn.d_scores, c->nn.d_qids, c->nn.d_ids, c->nn.d_ws, c->nn.d_counts,
+                    c->km.d_C, c->km.d_bestC, c->km.d_dist, c->km.d_labels, c->km.d_bestL, c->km.d_order, c->km.d_hist, c->km.d_counts, c->km.d_start, c->km.d_pstart,
+                    c->km.d_changed, c->km.d_seed, c->km.d_mlabels, c->km.d_psum, c->km.d_ipart, c->km.d_inertia, c->km.d_tallies};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
 #ifdef F2V_TEST_HOOKS
@@ -2223,6 +2241,8 @@ int f2v_destroy(f2v_handle c) {
     for (hipEvent_t e : c->ev_snap)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->nn.ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->km.ev)
         if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -3236,6 +3256,17 @@ int nearest_run(f2v_ctx *c, const uint32_t *qids, bool all, const float *vecs, u
     return F2V_OK;
 }
 
+// Do the CSR's column ids ascend inside every row?  Checked once per handle, on the host copy.
+bool rows_ascending(f2v_ctx *c) {
+    if (c->rows_sorted < 0) {
+        c->rows_sorted = 1;
+        for (uint32_t r = 0; r < c->n && c->rows_sorted; r++)
+            for (uint32_t p = c->rowptr[r] + 1; p < c->rowptr[r + 1]; p++)
+                if (c->colids[p] < c->colids[p - 1]) { c->rows_sorted = 0; break; }
+    }
+    return c->rows_sorted == 1;
+}
+
 // The entry points' common argument and state checks (f2v_objective's preamble).  -> 1: nq == 0, nothing to do and nothing touched.
 // `by_row`: the call searches CSR rows (EXCLUDE_NEIGHBOURS, the recall count), which needs their ids ascending -- f2v_create documents
 // that order but no earlier kernel depended on it, so it is verified here, once per handle, on the host copy.
@@ -3245,13 +3276,7 @@ int nearest_enter(f2v_ctx *c, const char *who, uint32_t nq, uint32_t k, int metr
     if (metric != F2V_SIM_DOT && metric != F2V_SIM_L2 && metric != F2V_SIM_COSINE) return fail(F2V_EINVAL, "%s: unknown metric %d", who, metric);
     if (flags & ~(F2V_NEAREST_EXCLUDE_SELF | F2V_NEAREST_EXCLUDE_NEIGHBOURS)) return fail(F2V_EINVAL, "%s: unknown flag in 0x%x", who, flags);
     if (by_row) {
-        if (c->nn.rows_sorted < 0) {
-            c->nn.rows_sorted = 1;
-            for (uint32_t r = 0; r < c->n && c->nn.rows_sorted; r++)
-                for (uint32_t p = c->rowptr[r] + 1; p < c->rowptr[r + 1]; p++)
-                    if (c->colids[p] < c->colids[p - 1]) { c->nn.rows_sorted = 0; break; }
-        }
-        if (!c->nn.rows_sorted) return fail(F2V_EINVAL, "%s: the CSR's column ids are not ascending inside every row (needed to search a row)", who);
+        if (!rows_ascending(c)) return fail(F2V_EINVAL, "%s: the CSR's column ids are not ascending inside every row (needed to search a row)", who);
     }
     if (!c->have_x)
         return fail(F2V_ESTATE, c->x_invalid ? "%s: the embeddings are invalid since a launch gave up a bounded wait: set or initialise them again"
@@ -3261,9 +3286,265 @@ int nearest_enter(f2v_ctx *c, const char *who, uint32_t nq, uint32_t k, int metr
     return flush_pending(c);
 }
 
+// ---- clustering (f2v_kmeans.hip.h; definition in include/f2v.h) ------------------------------------------------------------------
+template <int RB>
+int launch_assign_t(f2v_ctx *c, const KmAssignArgs &a) {
+    const size_t lds = km_lds_bytes(RB, a.D, a.tile);
+    const uint32_t form = RB == 64 ? 1u : RB == 128 ? 2u : 4u;
+    if (lds > 65536 && !(c->km.lds_allowed & form)) {  // D is fixed per handle and the tile never outgrows kKmTileFloats or one sweep
+        HIPC(hipFuncSetAttribute(reinterpret_cast<const void *>(&kmeans_assign_kernel<RB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        c->km.lds_allowed |= form;
+    }
+    hipLaunchKernelGGL((kmeans_assign_kernel<RB>), dim3((a.n + RB - 1) / RB), dim3(kKmThreads), lds, c->stream, a);
+    HIPC(hipGetLastError());
+    return F2V_OK;
+}
+
+template <class T>
+int km_alloc(T *&p, size_t count) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    hipError_t e = hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T));
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? F2V_ENOMEM : F2V_ENODEV, "clustering workspace: %s", hipGetErrorString(e));
+    return F2V_OK;
+}
+
+// the workspace of f2v_kmeans for `k` clusters (f2v.h states its size)
+int kmeans_workspace(f2v_ctx *c, uint32_t k) {
+    f2v_ctx::Kmeans &w = c->km;
+    for (hipEvent_t &e : w.ev)
+        if (!e) HIPC(hipEventCreate(&e));
+    if (w.cap_k >= k) return F2V_OK;
+    HIPC(hipStreamSynchronize(c->stream));
+    const size_t n = c->n, D = c->D, blocks = (n + kKmSortBlock - 1) / kKmSortBlock;
+    int rc;
+    if (!w.d_labels) {
+        if ((rc = km_alloc(w.d_labels, n)) != F2V_OK || (rc = km_alloc(w.d_bestL, n)) != F2V_OK || (rc = km_alloc(w.d_order, n)) != F2V_OK ||
+            (rc = km_alloc(w.d_dist, n)) != F2V_OK || (rc = km_alloc(w.d_ipart, (n + kKmPiece - 1) / kKmPiece)) != F2V_OK ||
+            (rc = km_alloc(w.d_inertia, 1)) != F2V_OK || (rc = km_alloc(w.d_changed, 1)) != F2V_OK)
+            return rc;
+    }
+    w.cap_k = 0;
+    if ((rc = km_alloc(w.d_C, k * D)) != F2V_OK || (rc = km_alloc(w.d_bestC, k * D)) != F2V_OK || (rc = km_alloc(w.d_hist, blocks * k)) != F2V_OK ||
+        (rc = km_alloc(w.d_counts, k)) != F2V_OK || (rc = km_alloc(w.d_start, (size_t)k + 1)) != F2V_OK || (rc = km_alloc(w.d_pstart, (size_t)k + 1)) != F2V_OK ||
+        (rc = km_alloc(w.d_seed, k)) != F2V_OK || (rc = km_alloc(w.d_psum, (n / kKmPiece + k) * D)) != F2V_OK)
+        return rc;
+    w.cap_k = k;
+    return F2V_OK;
+}
+
+// the k vertices of smallest key(v) = mix64(mix64(seed) ^ v), ties by id, in that order: a bounded heap over one pass
+void kmeans_seed_rows(uint32_t n, uint32_t k, uint64_t seed, std::vector<uint32_t> &ids) {
+    typedef std::pair<uint64_t, uint32_t> Entry;
+    const uint64_t sm = mix64_host(seed);
+    std::vector<Entry> heap;
+    heap.reserve(k);
+    for (uint32_t v = 0; v < n; v++) {
+        const Entry e(mix64_host(sm ^ (uint64_t)v), v);
+        if (heap.size() < k) {
+            heap.push_back(e);
+            std::push_heap(heap.begin(), heap.end());
+        } else if (e < heap.front()) {
+            std::pop_heap(heap.begin(), heap.end());
+            heap.back() = e;
+            std::push_heap(heap.begin(), heap.end());
+        }
+    }
+    std::sort_heap(heap.begin(), heap.end());
+    ids.resize(k);
+    for (uint32_t i = 0; i < k; i++) ids[i] = heap[i].second;
+}
+
+// histogram, scan: d_counts / d_start / d_pstart of `labels` and the per-block offsets the scatter needs
+void kmeans_count(f2v_ctx *c, const uint32_t *labels, uint32_t k) {
+    f2v_ctx::Kmeans &w = c->km;
+    const uint32_t blocks = (c->n + kKmSortBlock - 1) / kKmSortBlock;
+    hipLaunchKernelGGL(kmeans_hist_kernel, dim3(blocks), dim3(256), 0, c->stream, labels, c->n, k, w.d_hist);
+    hipLaunchKernelGGL(kmeans_offsets_kernel, dim3(k), dim3(256), 0, c->stream, w.d_hist, blocks, k, w.d_counts);
+    hipLaunchKernelGGL(kmeans_starts_kernel, dim3(1), dim3(256), 0, c->stream, (const uint32_t *)w.d_counts, k, w.d_start, w.d_pstart);
+}
+
+// One run of the iteration of f2v.h from the centroids in d_C: leaves L_t in d_labels, C_(t-1) in d_C, the distances in d_dist.
+int kmeans_run(f2v_ctx *c, uint32_t k, uint32_t max_iters, uint32_t *iterations, uint32_t *converged) {
+    f2v_ctx::Kmeans &w = c->km;
+    const uint32_t n = c->n, D = c->D;
+    const uint32_t rb = w.block ? w.block : k <= 2 ? 256u : k <= 4 ? 128u : 64u;
+    KmAssignArgs a{};
+    a.X = c->d_X[c->cur];
+    a.C = w.d_C;
+    a.labels = w.d_labels;
+    a.dist = w.d_dist;
+    a.changed = w.d_changed;
+    a.n = n;
+    a.D = D;
+    a.k = k;
+    a.tile = km_tile(rb, D, k);
+    KmSumArgs s{};
+    s.X = a.X;
+    s.order = w.d_order;
+    s.start = w.d_start;
+    s.counts = w.d_counts;
+    s.pstart = w.d_pstart;
+    s.psum = w.d_psum;
+    s.n = n;
+    s.D = D;
+    s.k = k;
+    s.lanes = 1;
+    while (s.lanes < 64 && 4 * s.lanes < D) s.lanes *= 2;
+    const uint32_t blocks = (n + kKmSortBlock - 1) / kKmSortBlock;
+    const size_t max_pieces = (size_t)n / kKmPiece + k;
+    HIPC(hipMemsetAsync(w.d_labels, 0xFF, (size_t)n * sizeof(uint32_t), c->stream));  // no label yet: the first assignment changes every row
+    for (uint32_t t = 1;; t++) {
+        HIPC(hipMemsetAsync(w.d_changed, 0, sizeof(uint32_t), c->stream));
+        int rc = rb == 256 ? launch_assign_t<256>(c, a) : rb == 128 ? launch_assign_t<128>(c, a) : launch_assign_t<64>(c, a);
+        if (rc != F2V_OK) return rc;
+        uint32_t changed = 0;
+        HIPC(hipMemcpyAsync(&changed, w.d_changed, sizeof changed, hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+        if (t > 1 && changed == 0) {
+            *iterations = t - 1;
+            *converged = 1;
+            return F2V_OK;
+        }
+        if (t - 1 == max_iters) {
+            *iterations = max_iters;
+            *converged = 0;
+            return F2V_OK;
+        }
+        kmeans_count(c, w.d_labels, k);
+        hipLaunchKernelGGL(kmeans_scatter_kernel, dim3(blocks), dim3(64), 0, c->stream, (const uint32_t *)w.d_labels, n, k, (const uint32_t *)w.d_hist,
+                           (const uint32_t *)w.d_start, w.d_order);
+        hipLaunchKernelGGL(kmeans_piece_sum_kernel, dim3((uint32_t)((max_pieces * s.lanes + kKmThreads - 1) / kKmThreads)), dim3(kKmThreads), 0, c->stream, s);
+        hipLaunchKernelGGL(kmeans_centroid_kernel, dim3(k, (D + 31) / 32), dim3(kKmThreads), 0, c->stream, (const double *)w.d_psum, (const uint32_t *)w.d_counts,
+                           (const uint32_t *)w.d_pstart, D, w.d_C);
+        HIPC(hipGetLastError());
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int f2v_kmeans(f2v_handle c, uint32_t k, uint32_t max_iters, uint32_t restarts, uint64_t seed, const float *init_centroids, uint32_t *labels_out,
+               float *centroids_out, uint64_t *counts_out, f2v_kmeans_t *info_out) {
+    if (!c || !labels_out || !info_out) return fail(F2V_EINVAL, "f2v_kmeans: null argument");
+    if (k == 0 || k > F2V_KMEANS_MAX_K || k > c->n) return fail(F2V_EINVAL, "f2v_kmeans: k = %u is outside 1..min(%d, n = %u)", k, F2V_KMEANS_MAX_K, c->n);
+    if (restarts == 0) return fail(F2V_EINVAL, "f2v_kmeans: restarts must be at least 1");
+    if (restarts > 1 && init_centroids) return fail(F2V_EINVAL, "f2v_kmeans: restarts > 1 need seeded centroids (init_centroids must be NULL)");
+    if (c->n >= 0xFFFFFFFFu - 256u) return fail(F2V_EINVAL, "f2v_kmeans: too many vertices for 32-bit row blocks");
+    if (!c->have_x)
+        return fail(F2V_ESTATE, c->x_invalid ? "f2v_kmeans: the embeddings are invalid since a launch gave up a bounded wait: set or initialise them again"
+                                             : "f2v_kmeans: embeddings were never initialised");
+    HIPC(hipSetDevice(c->device));
+    int rc = flush_pending(c);
+    if (rc != F2V_OK) return rc;
+    if ((rc = kmeans_workspace(c, k)) != F2V_OK) return rc;
+    f2v_ctx::Kmeans &w = c->km;
+    const uint32_t n = c->n, D = c->D;
+    const size_t cbytes = (size_t)k * D * sizeof(float), lbytes = (size_t)n * sizeof(uint32_t);
+    f2v_kmeans_t best{};
+    std::vector<uint32_t> ids, all_ids;  // every restart's seeded rows, chosen on the host before the timed part
+    for (uint32_t r = 0; !init_centroids && r < restarts; r++) {
+        kmeans_seed_rows(n, k, seed + r, ids);
+        all_ids.insert(all_ids.end(), ids.begin(), ids.end());
+    }
+    HIPC(hipEventRecord(w.ev[0], c->stream));
+    for (uint32_t r = 0; r < restarts; r++) {
+        if (init_centroids) {
+            HIPC(hipMemcpyAsync(w.d_C, init_centroids, cbytes, hipMemcpyHostToDevice, c->stream));
+        } else {
+            HIPC(hipMemcpyAsync(w.d_seed, all_ids.data() + (size_t)r * k, (size_t)k * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(nearest_gather_kernel, dim3(std::min<size_t>(((size_t)k * D + 255) / 256, 4096)), dim3(256), 0, c->stream, (const float *)c->d_X[c->cur],
+                               (const uint32_t *)w.d_seed, k, D, w.d_C);
+            HIPC(hipGetLastError());
+        }
+        uint32_t iterations = 0, converged = 0;
+        if ((rc = kmeans_run(c, k, max_iters, &iterations, &converged)) != F2V_OK) return rc;
+        const uint32_t parts = (n + kKmPiece - 1) / kKmPiece;
+        hipLaunchKernelGGL(kmeans_inertia_piece_kernel, dim3((parts + 255) / 256), dim3(256), 0, c->stream, (const float *)w.d_dist, n, w.d_ipart);
+        hipLaunchKernelGGL(kmeans_inertia_reduce_kernel, dim3(1), dim3(256), 0, c->stream, (const double *)w.d_ipart, parts, w.d_inertia);
+        HIPC(hipGetLastError());
+        double inertia = 0.0;
+        HIPC(hipMemcpyAsync(&inertia, w.d_inertia, sizeof inertia, hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+        if (r == 0 || inertia < best.inertia) {  // (a NaN inertia never replaces a run: ties and NaNs go to the lowest r)
+            best.inertia = inertia;
+            best.iterations = iterations;
+            best.converged = converged;
+            best.restart = r;
+            if (restarts > 1) {
+                HIPC(hipMemcpyAsync(w.d_bestL, w.d_labels, lbytes, hipMemcpyDeviceToDevice, c->stream));
+                HIPC(hipMemcpyAsync(w.d_bestC, w.d_C, cbytes, hipMemcpyDeviceToDevice, c->stream));
+            }
+        }
+    }
+    const uint32_t *L = restarts > 1 ? w.d_bestL : w.d_labels;
+    const float *Cb = restarts > 1 ? w.d_bestC : w.d_C;
+    kmeans_count(c, L, k);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(w.ev[1], c->stream));
+    std::vector<uint32_t> counts(k);
+    HIPC(hipMemcpyAsync(labels_out, L, lbytes, hipMemcpyDeviceToHost, c->stream));
+    if (centroids_out) HIPC(hipMemcpyAsync(centroids_out, Cb, cbytes, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipMemcpyAsync(counts.data(), w.d_counts, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    if ((rc = check_kernel_err(c, "f2v_kmeans")) != F2V_OK) return rc;
+    for (uint32_t i = 0; counts_out && i < k; i++) counts_out[i] = counts[i];
+    float ms = 0.f;
+    HIPC(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
+    best.seconds = ms * 1e-3;
+    *info_out = best;
+    return F2V_OK;
+}
+
+int f2v_modularity(f2v_handle c, const uint32_t *labels, uint32_t n_clusters, double *q_out, uint64_t *edges_out, uint64_t *inside_out,
+                   uint64_t *degree_out) {
+    if (!c || !labels || !q_out) return fail(F2V_EINVAL, "f2v_modularity: null argument");
+    if (n_clusters == 0) return fail(F2V_EINVAL, "f2v_modularity: n_clusters must be at least 1");
+    for (uint32_t v = 0; v < c->n; v++)
+        if (labels[v] >= n_clusters) return fail(F2V_EINVAL, "f2v_modularity: labels[%u] = %u is not below n_clusters = %u", v, labels[v], n_clusters);
+    if (!rows_ascending(c)) return fail(F2V_EINVAL, "f2v_modularity: the CSR's column ids are not ascending inside every row (needed to search a row)");
+    HIPC(hipSetDevice(c->device));
+    f2v_ctx::Kmeans &w = c->km;
+    int rc;
+    if (!w.d_mlabels && (rc = km_alloc(w.d_mlabels, c->n)) != F2V_OK) return rc;
+    const size_t words = 1 + 2 * (size_t)n_clusters;
+    if (w.cap_nc < n_clusters) {
+        HIPC(hipStreamSynchronize(c->stream));
+        w.cap_nc = 0;
+        if ((rc = km_alloc(w.d_tallies, words)) != F2V_OK) return rc;
+        w.cap_nc = n_clusters;
+    }
+    HIPC(hipMemcpyAsync(w.d_mlabels, labels, (size_t)c->n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemsetAsync(w.d_tallies, 0, words * sizeof(unsigned long long), c->stream));
+    ModArgs a{};
+    a.rowptr = c->d_rowptr;
+    a.colids = c->d_colids;
+    a.labels = w.d_mlabels;
+    a.tallies = w.d_tallies;
+    a.n = c->n;
+    a.nc = n_clusters;
+    a.lds = n_clusters <= kModLdsClusters && c->nnz < (1ull << 31) ? 1u : 0u;  // a workgroup's 32-bit tallies cannot overflow
+    const uint32_t wgs = std::max(1u, std::min((c->n + 3) / 4, 4096u));
+    hipLaunchKernelGGL(modularity_kernel, dim3(wgs), dim3(256), a.lds ? 2 * (size_t)n_clusters * sizeof(uint32_t) : 0, c->stream, a);
+    HIPC(hipGetLastError());
+    std::vector<uint64_t> t(words);
+    HIPC(hipMemcpyAsync(t.data(), w.d_tallies, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    const uint64_t m = t[0];
+    double q = 0.0;
+    for (uint32_t i = 0; m && i < n_clusters; i++) {
+        const double x = (double)t[1 + n_clusters + i] / (2.0 * (double)m);
+        q += (double)t[1 + i] / (double)m - x * x;
+    }
+    *q_out = q;
+    if (edges_out) *edges_out = m;
+    for (uint32_t i = 0; i < n_clusters; i++) {
+        if (inside_out) inside_out[i] = t[1 + i];
+        if (degree_out) degree_out[i] = t[1 + n_clusters + i];
+    }
+    return F2V_OK;
+}
 
 int f2v_nearest_rows(f2v_handle c, const uint32_t *query_ids, uint32_t nq, uint32_t k, int metric, uint32_t flags, uint32_t *ids_out,
                      float *scores_out, double *seconds_out) {

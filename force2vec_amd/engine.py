@@ -20,6 +20,11 @@ from ._lib import INIT_SYMMETRIC, INIT_UNIT, check
 Objective = namedtuple("Objective", "loss attraction repulsion positive_pairs negative_pairs")
 
 
+# Engine.kmeans / Engine.modularity (include/f2v.h: clustering)
+KMeans = namedtuple("KMeans", "labels centroids inertia iterations converged restart counts")
+Modularity = namedtuple("Modularity", "q edges inside degree")
+
+
 METRICS = {"dot": _lib.SIM_DOT, "l2": _lib.SIM_L2, "cos": _lib.SIM_COSINE, "cosine": _lib.SIM_COSINE}
 
 
@@ -46,6 +51,7 @@ class Engine:
         h = C.c_void_p()
         self._ck(self._L.f2v_create(_u32(rowptr), _u32(colids), self.n, self.nnz, self.dim, device, C.byref(h)))
         self._h = h
+        self.last_nearest_seconds = self.last_kmeans_seconds = 0.0  # device time of the last query / clustering
 
     def _ck(self, rc):
         check(rc, self._L)  # the error text lives in the library that returned the code
@@ -262,6 +268,39 @@ class Engine:
             self._ck(self._L.f2v_neighbour_recall(self._h, _u32(q), len(q), k, m, C.byref(hits), C.byref(possible), C.byref(sec)))
         self.last_nearest_seconds = sec.value
         return hits.value, possible.value
+
+    # -- clustering (include/f2v.h: definition; a function of the matrix, k, max_iters, restarts and the seed alone) -------------
+    def kmeans(self, k, max_iters=300, seed=1, restarts=1, init=None):
+        """Lloyd's k-means on the rows of the matrix, on the GPU -> KMeans(labels uint32[n], centroids float32[k, dim], inertia,
+        iterations, converged, restart, counts uint64[k]).  Initial centroids: `init` (float32 [k, dim]) or rows drawn from `seed`;
+        of `restarts` seeded runs (seed, seed + 1, ...) the one of lowest inertia is returned.  `last_kmeans_seconds` keeps the
+        device time."""
+        labels = np.empty(self.n, dtype=np.uint32)
+        centroids = np.empty((k, self.dim), dtype=np.float32)
+        counts = np.empty(k, dtype=np.uint64)
+        c0 = None
+        if init is not None:
+            c0 = np.ascontiguousarray(init, dtype=np.float32)
+            if c0.shape != (k, self.dim):
+                raise ValueError("kmeans: init must be [%d, %d]" % (k, self.dim))
+        info = _lib.KMeansInfo()
+        self._ck(self._L.f2v_kmeans(self._h, k, max_iters, restarts, seed, _f32(c0) if c0 is not None else None, _u32(labels), _f32(centroids),
+                                    counts.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(info)))
+        self.last_kmeans_seconds = info.seconds
+        return KMeans(labels, centroids, info.inertia, info.iterations, bool(info.converged), info.restart, counts)
+
+    def modularity(self, labels, n_clusters=None):
+        """Newman modularity of `labels` on the simple undirected graph of the CSR, tallied on the GPU -> Modularity(q, edges,
+        inside uint64[n_clusters], degree uint64[n_clusters]).  n_clusters=None: max(labels) + 1."""
+        lab = np.ascontiguousarray(labels, dtype=np.uint32).reshape(-1)
+        if len(lab) != self.n:
+            raise ValueError("modularity: one label per vertex")
+        nc = (int(lab.max()) + 1 if len(lab) else 1) if n_clusters is None else int(n_clusters)
+        q, edges = C.c_double(), C.c_uint64()
+        inside, degree = np.zeros(max(nc, 1), dtype=np.uint64), np.zeros(max(nc, 1), dtype=np.uint64)
+        self._ck(self._L.f2v_modularity(self._h, _u32(lab), nc, C.byref(q), C.byref(edges), inside.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                        degree.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return Modularity(q.value, edges.value, inside[:nc], degree[:nc])
 
     def stats(self):
         s = _lib.Stats()

@@ -344,6 +344,58 @@ F2V_API int f2v_nearest_vectors(f2v_handle h, const float *queries, uint32_t nq,
 F2V_API int f2v_neighbour_recall(f2v_handle h, const uint32_t *query_ids, uint32_t nq, uint32_t k, int metric, uint64_t *hits_out,
                          uint64_t *possible_out, double *seconds_out);
 
+/* ---- clustering ------------------------------------------------------------------------------------------------------------
+ * The third score the reference judges an embedding by (performancescores/runnodeclassclust.py:311-331): k-means on the rows of the
+ * matrix, then the modularity of that clustering on the input graph -- the one score that needs no labels.  Lloyd's iteration,
+ * defined so that it is deterministic; fma(a, b, acc) is one correctly rounded fp32 fused multiply-add:
+ *   distance    dist(x, c) = chain_d fma(t_d, t_d, acc) from +0 over ascending d, t_d = x_d - c_d (one rounded subtraction): -F2V_SIM_L2
+ *               of the nearest-neighbour definition above, always from differences, subnormals kept;
+ *   assignment  label(v) = the centroid of smallest dist, ties to the lowest centroid index, a NaN distance after every number
+ *               (all NaN: label 0): the ranking of f2v_nearest_* over the K centroids with k = 1;
+ *   update      the members of cluster c in ascending vertex id, cut into pieces of F2V_KMEANS_PIECE consecutive members; a piece is
+ *               summed per dimension in fp64, sequentially from +0; the piece sums are added sequentially in ascending piece order
+ *               in fp64; centroid_d = (float)(sum_d / (double)count); a cluster without members keeps its previous centroid;
+ *   inertia     the fp64 sum of the fp32 distances dist(v, centroid[label(v)]): vertices in ascending id in pieces of 64 consecutive
+ *               vertices summed sequentially from +0, the piece sums added sequentially in ascending order;
+ *   iteration   with C_0 the initial centroids, for t = 1, 2, ...: L_t = assign(X, C_(t-1)); if t > 1 and L_t == L_(t-1) stop with
+ *               converged = 1, iterations = t - 1; if t - 1 == max_iters stop with converged = 0, iterations = max_iters;
+ *               C_t = update(X, L_t, C_(t-1)).  Returned are L_t, C_(t-1), the inertia of that pair and the member counts of L_t,
+ *               so labels == assign(X, centroids) always holds; max_iters = 0 is a pure assignment to the given centroids;
+ *   initial centroids   k x D floats from the caller, or seeded rows: key(v) = mix64(mix64(seed) ^ v) (mix64: the splitmix64
+ *               finaliser of the objective above), vertices sorted by key ascending, ties by id, centroid c = the row of the c-th
+ *               vertex of that order (k distinct vertices).  Restart r of `restarts` (0-based) uses seed + r; the result is the
+ *               restart of lowest inertia (fp64 compare), ties to the lowest r.
+ * The result is a function of (X, k, max_iters, restarts, seed or the given centroids) alone: never of launch shapes, of
+ * "kmeans_block" (f2v_set_param: rows per workgroup of the assignment kernel, 0 = automatic | 64 | 128 | 256) or any other tunable,
+ * of the handle or of the order in which workgroups run; no float atomics.
+ * f2v_kmeans works on the matrix as f2v_get_embeddings would return it (pending minibatches are committed first), runs on the
+ * handle's stream and changes neither the matrices nor the rand() stream nor any later training result; on a handle attached to a
+ * push exchange it reads this rank's replica.  Workspace, allocated on first use (grown for a larger k) and freed by f2v_destroy:
+ * 4 n-word arrays (labels, the best restart's labels, the members in cluster order, distances), 2 k x D floats, ceil(n / 1024) x k
+ * words of block histograms, (n / 64 + k) x D doubles of piece sums and ceil(n / 64) doubles of inertia pieces.  The convergence
+ * test reads 4 bytes back per iteration.  info_out->seconds: device time between events around the call's own launches.
+ * F2V_ESTATE without valid embeddings; F2V_EINVAL for null pointers, k = 0, k > F2V_KMEANS_MAX_K, k > n, restarts = 0, and
+ * restarts > 1 together with init_centroids. */
+#define F2V_KMEANS_MAX_K 1024
+#define F2V_KMEANS_PIECE 64
+typedef struct {
+    double inertia;
+    double seconds;
+    uint32_t iterations, converged, restart, reserved;
+} f2v_kmeans_t;
+F2V_API int f2v_kmeans(f2v_handle h, uint32_t k, uint32_t max_iters, uint32_t restarts, uint64_t seed,
+               const float *init_centroids /* k x D or NULL */, uint32_t *labels_out /* n */, float *centroids_out /* k x D, may be NULL */,
+               uint64_t *counts_out /* k, may be NULL */, f2v_kmeans_t *info_out);
+/* Newman modularity of a labelling (labels[v] < n_clusters) on the SIMPLE undirected graph of the CSR: every unordered pair {u, v}
+ * that occurs as a nonzero in either direction counts once (duplicates are collapsed), a self-loop is one edge and adds 2 to its
+ * vertex's degree; m = edges, inside[c] = edges with both ends in c, degree[c] = sum of the simple-graph degrees of c's vertices;
+ * Q = sum over c ascending of (inside[c] / m - (degree[c] / (2 m))^2) in fp64, sequentially, 0 when m = 0.  The tallies are integers
+ * counted on the device with integer atomics (exact, independent of order), Q is formed on the host from them.  Needs no embeddings.
+ * The last three outputs may be NULL (inside_out, degree_out: n_clusters values each).  F2V_EINVAL for null pointers, n_clusters = 0,
+ * a label >= n_clusters and a CSR whose column ids are not ascending inside every row (rows are searched; checked once per handle). */
+F2V_API int f2v_modularity(f2v_handle h, const uint32_t *labels /* n */, uint32_t n_clusters, double *q_out, uint64_t *edges_out,
+                   uint64_t *inside_out, uint64_t *degree_out);
+
 /* ---- host-side I/O of the drop-in boundary (no device needed) ----------------------------
  * f2v_read_mtx replaces SetInputMatricesAsCSR (sample/commonutility.h:44-54 -> ReadASCII
  * sample/IO.h:59-156, CSC sample/CSC.h:146-188, CSR sample/CSR.h:154-186): MatrixMarket
