@@ -187,6 +187,7 @@ struct f2v_ctx {
     bool test_chain_nowait = false;  // timing experiment: chained launches without their row waits (results are then wrong)
     unsigned long long *d_xcd = nullptr;     // f2v_test_xcd_times (StepArgs::xcd_times)
     unsigned long long *d_stamps = nullptr;  // f2v_test_stamps: 4 wall-clock words per row (StepArgs::stamps)
+    uint32_t test_stub = 0;                  // f2v_test_interaction_stub (StepArgs::test_stub)
 #endif
     bool merge_fin = true, capturing = false;  // all combine-tree levels in one launch (not while a hipGraph is captured)
     int cur = 0;  // d_X[cur]: current matrix; d_X[cur^1]: receives the rows updated this epoch
@@ -1599,6 +1600,7 @@ int launch_step(f2v_ctx *c, int math, uint32_t batch_lo, uint32_t batch_hi, uint
     a.upd_rows = c->upd_hi - c->upd_lo;
 #ifdef F2V_TEST_HOOKS
     a.xcd_times = c->d_xcd;
+    a.test_stub = c->test_stub;
 #endif
     push = push && c->push.attached && c->push.world > 1;
     if (push) fill_targets(c, a.push, c->cur ^ 1, batch_lo, push_masks);
@@ -3750,6 +3752,12 @@ int f2v_test_chain_nowait(f2v_handle c, int on) {
     if (!c) return fail(F2V_EINVAL, "null handle");
     c->test_chain_nowait = (on & 1) != 0;
     c->test_chain_mode = (uint32_t)on;
+    return F2V_OK;
+}
+
+int f2v_test_interaction_stub(f2v_handle c, uint32_t mode) {
+    if (!c) return fail(F2V_EINVAL, "null handle");
+    c->test_stub = mode & 3u;
     return F2V_OK;
 }
 

@@ -125,6 +125,9 @@ struct StepArgs {
     // f2v_test_xcd_times (one launch per minibatch): per XCD k -- [k] latest end of a workgroup, [8 + k] earliest start, [16 + k] sum of the
     // workgroups' durations, [24 + k] workgroups (100-MHz wall clock); nullptr: off
     unsigned long long *xcd_times;
+    // f2v_test_interaction_stub (one launch per minibatch; timing only, results WRONG): bit 0 -- a gathered neighbour row costs one add per
+    // register instead of its interaction; bit 1 -- the same for the samples staged in LDS
+    uint32_t test_stub;
 #endif
 };
 constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
@@ -744,6 +747,148 @@ __device__ __forceinline__ void pair_update_q(const float (&xi)[NB][4], const fl
     pair_apply_q<OPT, LPI, NB, NEG>(xi, xj4, Y, lr, pair_coef_q<OPT, LPI, NB, NEG>(xi, xj4, lr, c0, table));
 }
 
+// ---- a group's interactions, written out for the ISA (option 5 in the plain-launch path: qprocess's all-in-flight walk, and the
+// samples of qstep_body staged in LDS) --------------------------------------------------------------------------------------------
+// The same floating-point operations on the same values in the same order as pair_update_q, in fewer issue slots:
+//   * pair_dist_q: the differences and their squares as explicit 2-vectors in the register order the 16-byte loads deliver (one
+//     v_pk_add_f32 / v_pk_mul_f32 per register pair, no transposing moves), the in-lane tree and the cross-lane steps scalar -- an
+//     add can take its DPP operand directly, a packed add cannot and costs a v_mov_b32_dpp per half in front of it; the value
+//     barrier behind a block's sum keeps the SLP vectoriser from pairing the two blocks' reductions all the same;
+//   * shared_coef5: after the reductions every lane of an item holds all N sums a[0..N), and d1 is a function of a alone -- lane t
+//     evaluates the fp64 sequence ONCE, for a[t & (N - 1)], and the N results go back to every lane by DPP.  The same instructions
+//     on the same input: the same bits, inf and NaN included;
+//   * pair_apply5_q: f = clamp(diff * d1), Y += lr * f on the differences kept from pair_dist_q.
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+
+template <bool NEG>
+__device__ __forceinline__ float coef5(float a) {
+    if constexpr (NEG) return (float)(2.0 / ((double)a * (1.0 + (double)a)));  // algorithms.cpp:622
+    else return (float)(-2.0 / (1.0 + (double)a));                              // algorithms.cpp:608
+}
+
+template <int LPI, int NB>
+__device__ __forceinline__ float pair_dist_q(const float (&xi)[NB][4], const float4 (&xj4)[NB], f32x2_t (&d)[NB][2]) {
+    float bs[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        d[b][0] = f32x2_t{xi[b][0], xi[b][1]} - f32x2_t{xj4[b].x, xj4[b].y};
+        d[b][1] = f32x2_t{xi[b][2], xi[b][3]} - f32x2_t{xj4[b].z, xj4[b].w};
+        const f32x2_t s0 = d[b][0] * d[b][0], s1 = d[b][1] * d[b][1];
+        float t01 = s0.x + s0.y;
+        asm("" : "+v"(t01));
+        bs[b] = item_allreduce_tree<LPI>(t01 + (s1.x + s1.y));
+        asm("" : "+v"(bs[b]));
+    }
+    if constexpr (NB == 1) return bs[0];
+    else if constexpr (NB == 2) return bs[0] + bs[1];
+    else return (bs[0] + bs[1]) + (bs[2] + bs[3]);
+}
+
+// Which of N = 4 or 8 pairs lane t of an item evaluates -- t & (N - 1) -- as bit masks for v_bfi_b32: m[k] is all ones where bit k of t is set.
+// The value barrier keeps the compiler from turning the masks back into a compare and a v_cndmask_b32 per select; volatile, so
+// that they are made where they are used (two instructions a group) and not once, early, and held through the kernel.
+template <int N>
+struct LaneSel { uint32_t m[N == 4 ? 2 : 3]; };
+template <int N>
+__device__ __forceinline__ LaneSel<N> lane_sel(uint32_t t) {
+    LaneSel<N> s;
+#pragma unroll
+    for (int k = 0; k < (N == 4 ? 2 : 3); ++k) {
+        s.m[k] = 0u - ((t >> k) & 1u);
+        asm volatile("" : "+v"(s.m[k]));
+    }
+    return s;
+}
+
+// N = 4 or 8 pairs of one item (LPI >= N lanes): a[] is uniform over the item's lanes going in, cf[] coming out.
+template <int N, bool NEG>
+__device__ __forceinline__ void shared_coef5(const float (&a)[N], const LaneSel<N> &sel, float (&cf)[N]) {
+    static_assert(N == 4 || N == 8, "a quad, or the two quads of a half row");
+    uint32_t m[N];  // the lane's own pair, by a tree of bit selects on its index's low bits
+#pragma unroll
+    for (int k = 0; k < N; ++k) m[k] = __builtin_bit_cast(uint32_t, a[k]);
+#pragma unroll
+    for (int s = 1, l = 0; s < N; s <<= 1, ++l) {
+#pragma unroll
+        for (int k = 0; k + s < N; k += 2 * s) m[k] = (m[k + s] & sel.m[l]) | (m[k] & ~sel.m[l]);
+    }
+    const int c = __builtin_bit_cast(int, coef5<NEG>(__builtin_bit_cast(float, m[0])));
+    // pair u's result sits on lane u of every N lanes.  quad_perm [k, k, k, k] hands lane k's to its quad; with N = 8 the quad that
+    // does not hold pair u takes it from the other one through row_half_mirror (the value is uniform in a quad by then), written
+    // under a bank mask: banks 1 and 3 are the upper quads of a row's two halves, banks 0 and 2 the lower ones.
+    int q[4];
+    q[0] = __builtin_amdgcn_update_dpp(0, c, 0x00, 0xF, 0xF, true);
+    q[1] = __builtin_amdgcn_update_dpp(0, c, 0x55, 0xF, 0xF, true);
+    q[2] = __builtin_amdgcn_update_dpp(0, c, 0xAA, 0xF, 0xF, true);
+    q[3] = __builtin_amdgcn_update_dpp(0, c, 0xFF, 0xF, 0xF, true);
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+        if constexpr (N == 4) cf[u] = __builtin_bit_cast(float, q[u]);
+        else cf[u] = __builtin_bit_cast(float, u < 4 ? __builtin_amdgcn_update_dpp(q[u & 3], q[u & 3], 0x141, 0xF, 0xA, false)
+                                                     : __builtin_amdgcn_update_dpp(q[u & 3], q[u & 3], 0x141, 0xF, 0x5, false));
+    }
+}
+
+template <int NB>
+__device__ __forceinline__ void pair_apply5_q(const f32x2_t (&d)[NB][2], float (&Y)[NB][4], float lr, float coef) {
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            f32x2_t f = d[b][h] * coef;
+            f.x = clamp_ref(f.x);
+            f.y = clamp_ref(f.y);
+            const f32x2_t s = lr * f;
+            Y[b][2 * h] = Y[b][2 * h] + s.x;
+            Y[b][2 * h + 1] = Y[b][2 * h + 1] + s.y;
+        }
+    }
+}
+
+// The negative samples a workgroup has staged in LDS (ns <= 8 of them, the same for every item), all their coefficients in one evaluation
+// (shared_coef5 on the lanes t & 7; a slot past ns stands in with a = 1), then the additions in order -- the differences are taken again
+// from LDS rather than kept in 8 x NB x 4 registers.
+template <int LPI, int NB>
+__device__ __forceinline__ void lds_samples5_q(const float4 (*smp)[LPI * NB], uint32_t ns, uint32_t t, const float (&xi)[NB][4], float (&Y)[NB][4], float lr) {
+    float sum[8], cf[8];
+#pragma unroll
+    for (uint32_t sidx = 0; sidx < 8u; ++sidx) {
+        sum[sidx] = 1.0f;
+        if (sidx < ns) {
+            float4 xs[NB];
+            f32x2_t d[NB][2];
+#pragma unroll
+            for (int b = 0; b < NB; ++b) xs[b] = smp[sidx][LPI * b + t];
+            sum[sidx] = pair_dist_q<LPI, NB>(xi, xs, d);
+        }
+    }
+    shared_coef5<8, true>(sum, lane_sel<8>(t), cf);
+#pragma unroll
+    for (uint32_t sidx = 0; sidx < 8u; ++sidx) {
+        if (sidx < ns) {
+            f32x2_t d[NB][2];
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                const float4 xs = smp[sidx][LPI * b + t];
+                d[b][0] = f32x2_t{xi[b][0], xi[b][1]} - f32x2_t{xs.x, xs.y};
+                d[b][1] = f32x2_t{xi[b][2], xi[b][3]} - f32x2_t{xs.z, xs.w};
+            }
+            pair_apply5_q<NB>(d, Y, lr, cf[sidx]);
+        }
+    }
+}
+
+#ifdef F2V_TEST_HOOKS
+// f2v_test_interaction_stub: a gathered row costs one add per register (results WRONG; what is left is the kernel's memory side and frame)
+template <int NB>
+__device__ __forceinline__ void stub_update_q(const float4 (&xj4)[NB], float (&Y)[NB][4]) {
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        Y[b][0] = Y[b][0] + xj4[b].x; Y[b][1] = Y[b][1] + xj4[b].y; Y[b][2] = Y[b][2] + xj4[b].z; Y[b][3] = Y[b][3] + xj4[b].w;
+    }
+}
+#endif
+
 // Chained minibatches: row j is written by an earlier minibatch of this launch -- wait until it has been announced
 // (rowflag[j] == seq, stored by its writer after the written-through row was acknowledged).  -> true: gave up (time-out, or
 // the launch is lost already); the caller then stores nothing.
@@ -827,9 +972,10 @@ __device__ __forceinline__ HandSrc hand_src_window(const StepArgs &a, uint32_t D
 // fetched one group ahead.
 // FULL: D == 4*LPI*NB.  Otherwise D is any smaller multiple of 4 (rows stay 16-byte aligned): lane t's block b is live
 // iff 4*LPI*b + 4t < D, dead pieces read as zero -- the zero padding of the canonical tree -- and are never stored.
-// `idle`: a valid row id in memory (the item's own, or its wavefront's first item's), read in place of the list when cnt == 0.
+// `idle`: the item of this launch (its own, or its wavefront's first one) whose row id -- a valid one, in memory -- is read in place of the list when
+// cnt == 0; an index, not the address: that would be a 64-bit value held through the neighbour walk for the sample walk behind it.
 template <int OPT, int LPI, int NB, bool NEG, int U, bool FULL, bool CHAIN>
-__device__ __forceinline__ void qprocess(const StepArgs &a, const HandSrc &hs, const uint32_t *ids, const uint32_t *idle, uint32_t cnt, uint32_t maxcnt,
+__device__ __forceinline__ void qprocess(const StepArgs &a, const HandSrc &hs, const uint32_t *ids, uint32_t idle, uint32_t cnt, uint32_t maxcnt,
                                          uint32_t t, uint32_t D, const float (&xi)[NB][4], float (&Y)[NB][4], double c0, const float *table, bool &bad) {
     // The unconditional gather below costs registers: most forms lose a wave per SIMD for it and gain more (D = 16 / 32 / 64:
     // -46 / -46 / -16 %; profiles/r05_gather_in_flight.txt), but options 6/7 at a D short of the U = 4 form's width (D = 100:
@@ -842,7 +988,8 @@ __device__ __forceinline__ void qprocess(const StepArgs &a, const HandSrc &hs, c
         // id (the row of an earlier slot: a cache hit), an empty list reads `idle`: nothing speculative leaves the item's list
         // or the matrix.  The interactions stay predicated: the same sums in the same order.
         const uint32_t last = cnt != 0u ? cnt - 1u : 0u;
-        const uint32_t *list = cnt != 0u ? ids : idle;
+        asm volatile("" : "+v"(idle));  // (or the two walks' addresses are made once, early)
+        const uint32_t *list = cnt != 0u ? ids : &a.items[idle].row;
         uint32_t j[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) j[u] = list[(uint32_t)u < last ? (uint32_t)u : last];
@@ -870,9 +1017,49 @@ __device__ __forceinline__ void qprocess(const StepArgs &a, const HandSrc &hs, c
             // (keeps every load above the predicated interactions: left free, the compiler sinks row 0's loads into the first one's
             // block, behind the others, and waits vmcnt(0) there -- for the next ids too)
             asm volatile("" ::: "memory");
+#ifdef F2V_TEST_HOOKS
+            if (a.test_stub & 1u) {
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (g + u < cnt) pair_update_q<OPT, LPI, NB, NEG>(xi, xj[u], Y, a.lr, c0, table);
+                for (int u = 0; u < U; ++u)
+                    if (g + u < cnt) stub_update_q<NB>(xj[u], Y);
+                continue;
+            }
+#endif
+            if constexpr (OPT == 5 && !NEG && NB * U <= 8) {
+                // four rows at a time (a quad of lanes evaluates their coefficients; U = 8: two rounds -- all eight at once are a dozen
+                // registers more, a wave per SIMD): the rows' sums first, each row consumed under its own counted wait as it arrives --
+                // for every slot: one past the item's end holds a real row, its sum is finite and its coefficient is dropped --, ONE
+                // evaluation of the four coefficients, then the additions onto Y in list order, predicated as ever (a zero coefficient
+                // would not do: 0 x inf is NaN, and NaN clamps to -5)
+                const LaneSel<4> sel = lane_sel<4>(t);
+#pragma unroll
+                for (int h = 0; h < U; h += 4) {
+                    f32x2_t d[4][NB][2];
+                    float sum[4], cf[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        // (the row passes through a barrier of its own, behind the one above: unpredicated, row 0's differences are
+                        // otherwise hoisted in among the loads -- they free its address registers -- behind a wait for it)
+#pragma unroll
+                        for (int b = 0; b < NB; ++b) {
+                            f32x4_t v = {xj[h + u][b].x, xj[h + u][b].y, xj[h + u][b].z, xj[h + u][b].w};
+                            asm volatile("" : "+v"(v));
+                            xj[h + u][b] = make_float4(v.x, v.y, v.z, v.w);
+                        }
+                        sum[u] = pair_dist_q<LPI, NB>(xi, xj[h + u], d[u]);
+                    }
+                    shared_coef5<4, NEG>(sum, sel, cf);
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        if (g + h + u < cnt) pair_apply5_q<NB>(d[u], Y, a.lr, cf[u]);
+                    }
+                }
+            } else {
+                // (options 6 / 7 apply in fp64, per row; the sample walk of -bs 1 / ns > 8 has no registers for it)
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (g + u < cnt) pair_update_q<OPT, LPI, NB, NEG>(xi, xj[u], Y, a.lr, c0, table);
+                }
             }
         }
         return;
@@ -1086,7 +1273,7 @@ __device__ __forceinline__ void qstep_body(const StepArgs &a, const uint32_t blk
     // stages them in LDS once -- each CU then fetches them from L2 once per workgroup instead of once per item, and
     // the repulsive interactions read them at LDS latency.  All lane groups of a wave read the same 16-byte
     // slots (broadcast), consecutive lanes consecutive slots: conflict-free.
-    constexpr uint32_t kLdsSamples = 8;
+    constexpr uint32_t kLdsSamples = 8;  // (lds_samples5_q counts on it)
     __shared__ float4 smp[kLdsSamples][DP / 4];
     const bool lds_samples = !a.bs_mode && a.ns <= kLdsSamples;
     const HandSrc hs = hand_src_window(a, D);  // (chained launches: where handed-on rows are read, 16 bytes at agent scope)
@@ -1158,14 +1345,28 @@ __device__ __forceinline__ void qstep_body(const StepArgs &a, const uint32_t blk
     }
 
     bool bad = false;  // chained minibatches: a wait for an earlier minibatch's row gave up -- this item stores nothing
-    const uint32_t *idle = &a.items[active ? idx : IPW * w].row;  // (an empty list's stand-in id: this item's row, or the wave's first item's)
+    const uint32_t idle = active ? idx : IPW * w;  // (an empty list's stand-in id: this item's row, or the wave's first item's)
     qprocess<OPT, LPI, NB, false, U, FULL, CHAIN>(a, hs, a.nbr_ids + it.nb, idle, it.cnt, wave_max_of_items<LPI>(it.cnt), t, D, xi, Y, c0, table, bad);
     if (lds_samples) {
         if (active && last_chunk) {
-            for (uint32_t sidx = 0; sidx < a.ns; ++sidx) {
+            // option 5 in the plain launch, where an item has the lanes for it: the samples' coefficients in one evaluation
+            bool together = OPT == 5 && !CHAIN && LPI >= kLdsSamples;
+#ifdef F2V_TEST_HOOKS
+            together = together && (a.test_stub & 2u) == 0u;
+#endif
+            if constexpr (OPT == 5 && !CHAIN && LPI >= kLdsSamples) {
+                if (together) lds_samples5_q<LPI, NB>(smp, a.ns, t, xi, Y, a.lr);
+            }
+            for (uint32_t sidx = 0; !together && sidx < a.ns; ++sidx) {
                 float4 xs[NB];
 #pragma unroll
                 for (int b = 0; b < NB; ++b) xs[b] = smp[sidx][LPI * b + t];
+#ifdef F2V_TEST_HOOKS
+                if (a.test_stub & 2u) {
+                    stub_update_q<NB>(xs, Y);
+                    continue;
+                }
+#endif
                 pair_update_q<OPT, LPI, NB, true>(xi, xs, Y, a.lr, c0, table);
             }
         }
@@ -1179,8 +1380,17 @@ __device__ __forceinline__ void qstep_body(const StepArgs &a, const uint32_t blk
         // (wave-uniform on purpose: the launch is lost anyway, and a wave either announces all its items or none)
         return;
     }
+    // Option 5, whose walks hold a group's sums and coefficients besides its rows: the lane's index in its item and the row's offset are
+    // taken afresh for the stores (shared with the own row's load at the top they are three registers held through both walks)
+    uint32_t ts = t, row_out = row;
+    if constexpr (OPT == 5) {
+        uint32_t tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        ts = tid & (LPI - 1u);
+        asm("" : "+v"(row_out));
+    }
     if (active) {
-        float *out = (partial ? a.partials + (size_t)(it.flags & kItemSlotMask) * D : a.Xn + (size_t)row * D) + t * 4;
+        float *out = (partial ? a.partials + (size_t)(it.flags & kItemSlotMask) * D : a.Xn + (size_t)row_out * D) + ts * 4;
         float4 v[NB];
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
@@ -1188,7 +1398,7 @@ __device__ __forceinline__ void qstep_body(const StepArgs &a, const uint32_t blk
                 v[b] = make_float4(xi[b][0] + Y[b][0], xi[b][1] + Y[b][1], xi[b][2] + Y[b][2], xi[b][3] + Y[b][3]);  // algorithms.cpp:636
             else
                 v[b] = make_float4(Y[b][0], Y[b][1], Y[b][2], Y[b][3]);
-            if (!FULL && !(4u * LPI * b + 4u * t < D)) continue;
+            if (!FULL && !(4u * LPI * b + 4u * ts < D)) continue;
             if ((partial && a.fin_items) || CHAIN) store16_agent(out + 4 * LPI * b, v[b]);  // a tree node (or a later minibatch) of this grid reads it
             else *reinterpret_cast<float4 *>(out + 4 * LPI * b) = v[b];
         }
@@ -1201,10 +1411,10 @@ __device__ __forceinline__ void qstep_body(const StepArgs &a, const uint32_t blk
 #pragma unroll
                 for (int q = 0; q < kMaxRanks; ++q) {
                     if (m & (1u << q)) {
-                        float *dst = a.push.peer[q] + (size_t)(row - a.push.row_base) * D + t * 4;
+                        float *dst = a.push.peer[q] + (size_t)(row - a.push.row_base) * D + ts * 4;
 #pragma unroll
                         for (int b = 0; b < NB; ++b)
-                            if (FULL || 4u * LPI * b + 4u * t < D) store16_system(dst + 4 * LPI * b, v[b]);
+                            if (FULL || 4u * LPI * b + 4u * ts < D) store16_system(dst + 4 * LPI * b, v[b]);
                     }
                 }
             }
@@ -1214,13 +1424,13 @@ __device__ __forceinline__ void qstep_body(const StepArgs &a, const uint32_t blk
     if constexpr (CHAIN) {
         __builtin_amdgcn_s_waitcnt(0);  // new rows are in memory before they are announced to the later minibatches of the launch
 #ifdef F2V_TEST_HOOKS
-        if (active && !partial && t == 0u && row != a.test_withhold_row)
+        if (active && !partial && ts == 0u && row != a.test_withhold_row)
 #else
-        if (active && !partial && t == 0u)
+        if (active && !partial && ts == 0u)
 #endif
             __hip_atomic_store(a.rowflag + row, a.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #ifdef F2V_TEST_HOOKS
-        if (a.stamps && active && !partial && t == 0u) a.stamps[4 * (size_t)row + 2] = wall_clock64();
+        if (a.stamps && active && !partial && ts == 0u) a.stamps[4 * (size_t)row + 2] = wall_clock64();
 #endif
     }
     if (a.fin_items) {
@@ -1228,15 +1438,25 @@ __device__ __forceinline__ void qstep_body(const StepArgs &a, const uint32_t blk
 #ifdef F2V_TEST_HOOKS
         if ((it.flags & kItemSlotMask) == a.test_withhold_slot) return;  // fault injection: this piece never announces its sum
 #endif
-        if (active && partial && t == 0u) __hip_atomic_store(a.ready + (it.flags & kItemSlotMask), a.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (active && partial && ts == 0u) __hip_atomic_store(a.ready + (it.flags & kItemSlotMask), a.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #ifdef F2V_TEST_HOOKS
-        if (a.stamps && active && partial && it.cnt != 0u && t == 0u) atomicMax(a.stamps + 4 * (size_t)row, wall_clock64());
+        if (a.stamps && active && partial && it.cnt != 0u && ts == 0u) atomicMax(a.stamps + 4 * (size_t)row, wall_clock64());
 #endif
     }
 }
 
+// 5 waves per SIMD where the group's interactions are evaluated together and a group is 8 loads per lane: left to itself the scheduler
+// spreads the independent reductions over 104-108 VGPRs -- 4 waves -- where 90 do.  (Not in the self-test build: with its hooks'
+// registers on top the bound spills.)
+#ifdef F2V_TEST_HOOKS
+template <int OPT, int NB, int U>
+constexpr int kStepWaves = 1;
+#else
+template <int OPT, int NB, int U>
+constexpr int kStepWaves = (OPT == 5 && NB * U <= 8) ? 5 : 1;
+#endif
 template <int OPT, int LPI, int NB, int U, bool PUSH = false, bool FULL = true>
-__global__ __launch_bounds__(256) void qstep_kernel(const StepArgs a) {
+__global__ __launch_bounds__(256, (kStepWaves<OPT, NB, U>)) void qstep_kernel(const StepArgs a) {
 #ifdef F2V_TEST_HOOKS
     const unsigned long long t0 = a.xcd_times ? wall_clock64() : 0ull;
 #endif
@@ -1806,7 +2026,7 @@ __global__ __launch_bounds__(256, (NB <= 2 && U <= 4) ? (MODE == 2 ? 2 : OPT == 
         } else {
             const uint32_t scnt = (!idle && last_chunk) ? a.ns : 0u;
             const uint32_t sbase = a.bs_mode ? (row - a.batch_lo) : 0u;
-            qprocess<OPT, LPI, NB, true, U, FULL, true>(a, hs, a.sample_ids + sbase, nullptr, scnt, wave_max_of_items<LPI>(scnt), t, D, xi, Y, c0, table, bad);
+            qprocess<OPT, LPI, NB, true, U, FULL, true>(a, hs, a.sample_ids + sbase, 0u, scnt, wave_max_of_items<LPI>(scnt), t, D, xi, Y, c0, table, bad);
         }
         const bool wave_bad = __builtin_amdgcn_ballot_w64(bad) != 0ull;  // (wave-uniform: a wave stores all its items or none)
         if (wave_bad) wg_bad = 1u;

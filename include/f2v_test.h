@@ -61,6 +61,12 @@ F2V_API int f2v_test_xcd_times(f2v_handle h, int on, unsigned long long *out);
  * afterwards).  Best of `reps` launches in microseconds.  tools/plan_gather_probe.py. */
 F2V_API int f2v_test_plan_gather(f2v_handle h, uint32_t row_lo, uint32_t row_hi, uint32_t mode, uint32_t reps, double *us_out);
 
+/* Timing experiment: what the interactions are worth in a launch.  The real launch plans through the real step kernel (the sub-wave kernel, one
+ * launch per minibatch) with the interactions reduced to a stub, "rows gathered, one add each" (the results are then WRONG) -- mode bit 0: every
+ * gathered neighbour row is added onto the force sum, register by register, in place of its interaction; bit 1: the same for the negative samples
+ * staged in LDS; 0: off.  tools/interaction_stub_probe.py. */
+F2V_API int f2v_test_interaction_stub(f2v_handle h, uint32_t mode);
+
 #ifdef __cplusplus
 }
 #endif
