@@ -14,12 +14,17 @@ the matrix for each query (rows or caller-supplied vectors) without the matrix l
 `Engine.neighbour_recall(k, metric)` is the graph-reconstruction precision@k.
 
 Clustering: `Engine.kmeans(k, max_iters=300, seed=1, restarts=1)` runs Lloyd's k-means on the rows of the matrix on the GPU
-(deterministic: include/f2v.h), `Engine.modularity(labels)` scores a labelling on the input graph."""
+(deterministic: include/f2v.h), `Engine.modularity(labels)` scores a labelling on the input graph.
+
+Scoring with labels: `Engine.classify(labels, train_ids, test_ids)` (node-classification F1) and `Engine.link_predict(u, v, y)` fit a
+one-vs-rest logistic regression on rows or pair features with every pass over the samples on the GPU (`Engine.logreg_fit`,
+`logreg_eval`, `logreg_decision`; definition in include/f2v.h)."""
 from . import _lib  # noqa: F401
 from ._lib import F2VError  # noqa: F401
 from ._lib import KMEANS_MAX_K, KMEANS_PIECE  # noqa: F401
+from ._lib import LOGREG_BLOCK, LOGREG_MAX_CLASSES, PAIR_AVERAGE, PAIR_HADAMARD, PAIR_L1, PAIR_L2  # noqa: F401
 from ._lib import NEAREST_EXCLUDE_NEIGHBOURS, NEAREST_EXCLUDE_SELF, NEAREST_MAX_K, NEAREST_PAD_ID, SIM_COSINE, SIM_DOT, SIM_L2  # noqa: F401
-from .engine import Engine, KMeans, Modularity, algorithms, output_name, push_masks, read_embd, read_embd_bin, sm_table, write_embd, write_embd_bin  # noqa: F401
+from .engine import Engine, KMeans, LogregModel, Modularity, algorithms, output_name, push_masks, read_embd, read_embd_bin, sm_table, write_embd, write_embd_bin  # noqa: F401
 from .graph import read_csr_bin, read_mtx, rmat_csr, write_csr_bin  # noqa: F401
 
-__all__ = ["Engine", "F2VError", "KMeans", "Modularity", "algorithms", "read_mtx", "rmat_csr", "write_embd", "output_name", "sm_table"]
+__all__ = ["Engine", "F2VError", "KMeans", "LogregModel", "Modularity", "algorithms", "read_mtx", "rmat_csr", "write_embd", "output_name", "sm_table"]

@@ -15,9 +15,13 @@ NEAREST_MAX_K = 128
 NEAREST_EXCLUDE_SELF, NEAREST_EXCLUDE_NEIGHBOURS = 1, 2
 NEAREST_PAD_ID = 0xFFFFFFFF  # id of a slot past the last candidate (its score is -inf)
 KMEANS_MAX_K, KMEANS_PIECE = 1024, 64
+LOGREG_MAX_CLASSES, LOGREG_BLOCK = 64, 1024
+PAIR_HADAMARD, PAIR_L1, PAIR_L2, PAIR_AVERAGE = 0, 1, 2, 3
 
 u32p = C.POINTER(C.c_uint32)
 f32p = C.POINTER(C.c_float)
+f64p = C.POINTER(C.c_double)
+u8p = C.POINTER(C.c_uint8)
 
 
 class Stats(C.Structure):
@@ -35,6 +39,11 @@ class Objective(C.Structure):  # f2v_objective_t
 class KMeansInfo(C.Structure):  # f2v_kmeans_t
     _fields_ = [("inertia", C.c_double), ("seconds", C.c_double), ("iterations", C.c_uint32), ("converged", C.c_uint32),
                 ("restart", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class LogregInfo(C.Structure):  # f2v_logreg_t
+    _fields_ = [("loss", C.c_double), ("gnorm_inf", C.c_double), ("seconds", C.c_double), ("iterations", C.c_uint32),
+                ("evaluations", C.c_uint32), ("converged", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 # every entry point declared in include/f2v.h: name -> (restype, argtypes)
@@ -76,6 +85,9 @@ SIGNATURES = {
     "f2v_neighbour_recall": (C.c_int, [C.c_void_p, u32p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "f2v_kmeans": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, f32p, u32p, f32p, C.POINTER(C.c_uint64), C.POINTER(KMeansInfo)]),
     "f2v_modularity": (C.c_int, [C.c_void_p, u32p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "f2v_logreg_eval": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32, C.c_int, u8p, C.c_uint32, f64p, C.c_double, f64p, f64p, f64p]),
+    "f2v_logreg_fit": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32, C.c_int, u8p, C.c_uint32, C.c_double, C.c_double, C.c_uint32, f64p, C.POINTER(LogregInfo)]),
+    "f2v_logreg_decision": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32, C.c_int, f64p, C.c_uint32, f64p, f64p]),
     "f2v_push_export": (C.c_int, [C.c_void_p, C.c_void_p]),
     "f2v_push_attach": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "f2v_push_selftest": (C.c_int, [C.c_void_p]),

@@ -184,6 +184,91 @@ class algorithms {
         printf("Clusters:%u :MODULARITY: %.17g :INERTIA: %.17g :ITERATIONS: %u :RESTART: %u\n", k, q, info.inertia, info.iterations, info.restart);
     }
 
+    // -classify <labels file>: node classification as the reference scores it (performancescores/runnodeclassclust.py).  The file holds
+    // lines "vertex label" with 1-based vertex ids; a vertex may have several lines; labels are 0 .. C - 1, C <= 64.  For split
+    // s = 0 .. splits - 1 the labelled vertices are ordered by key(v) = mix64(mix64(seed + s) ^ v) ascending (mix64: the splitmix64
+    // finaliser of include/f2v.h), ties by id; the first int(L * frac) of the L train f2v_logreg_fit (lambda 1, tol 1e-4, 100
+    // iterations), every other one is predicted as many labels as it has: its largest decision values, ties to the lower class.
+    // Prints the means of the splits' micro and macro F1 in percent.
+    static uint64_t mix64(uint64_t z) {
+        z += 0x9E3779B97F4A7C15ull;
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        return z ^ (z >> 31);
+    }
+    void classify(const std::string &path, double frac, uint32_t splits, uint64_t seed) {
+        FILE *f = fopen(path.c_str(), "r");
+        if (!f) throw std::runtime_error("cannot read " + path);
+        std::vector<std::vector<uint32_t>> labels(rows);
+        std::vector<bool> seen;
+        long v = 0, l = 0;
+        while (fscanf(f, "%ld %ld", &v, &l) == 2) {
+            if (v < 1 || v > (long)rows || l < 0 || l >= F2V_LOGREG_MAX_CLASSES) {
+                fclose(f);
+                throw std::runtime_error("-classify: \"" + std::to_string(v) + " " + std::to_string(l) + "\" is outside the graph's vertices or the 64 classes");
+            }
+            labels[v - 1].push_back((uint32_t)l);
+            if (seen.size() <= (size_t)l) seen.resize(l + 1, false);
+            seen[l] = true;
+        }
+        fclose(f);
+        const uint32_t C = (uint32_t)seen.size();
+        if (C == 0 || std::find(seen.begin(), seen.end(), false) != seen.end()) throw std::runtime_error("-classify: the labels must be 0 .. C - 1, each used");
+        std::vector<uint32_t> labelled;
+        for (uint32_t u = 0; u < rows; u++)
+            if (!labels[u].empty()) labelled.push_back(u);
+        const size_t L = labelled.size(), cv = (size_t)((double)L * frac);
+        if (cv == 0 || cv == L) throw std::runtime_error("-classify: the split leaves no training or no test vertex");
+        const uint32_t P = DIM + 1;
+        double micro_sum = 0.0, macro_sum = 0.0;
+        for (uint32_t s = 0; s < splits; s++) {
+            const uint64_t sm = mix64(seed + s);
+            std::vector<std::pair<uint64_t, uint32_t>> keyed(L);
+            for (size_t i = 0; i < L; i++) keyed[i] = {mix64(sm ^ (uint64_t)labelled[i]), labelled[i]};
+            std::sort(keyed.begin(), keyed.end());
+            std::vector<uint32_t> ids(L);
+            for (size_t i = 0; i < L; i++) ids[i] = keyed[i].second;
+            std::vector<uint8_t> y(L * C, 0);
+            for (size_t i = 0; i < L; i++)
+                for (uint32_t c : labels[ids[i]]) y[i * C + c] = 1;
+            std::vector<double> W((size_t)C * P), z((L - cv) * C);
+            std::vector<f2v_logreg_t> info(C);
+            check(f2v_logreg_fit(h, ids.data(), nullptr, (uint32_t)cv, F2V_PAIR_HADAMARD, y.data(), C, 1.0, 1e-4, 100, W.data(), info.data()));
+            check(f2v_logreg_decision(h, ids.data() + cv, nullptr, (uint32_t)(L - cv), F2V_PAIR_HADAMARD, W.data(), C, z.data(), nullptr));
+            std::vector<double> tp(C, 0.0), fp(C, 0.0), fn(C, 0.0);
+            std::vector<uint32_t> order(C);
+            for (size_t i = cv; i < L; i++) {
+                const double *zi = z.data() + (i - cv) * C;
+                const uint8_t *yi = y.data() + i * C;
+                uint32_t k = 0;
+                for (uint32_t c = 0; c < C; c++) {
+                    order[c] = c;
+                    k += yi[c];
+                }
+                std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return zi[a] > zi[b]; });
+                std::vector<uint8_t> pred(C, 0);
+                for (uint32_t j = 0; j < k; j++) pred[order[j]] = 1;
+                for (uint32_t c = 0; c < C; c++) {
+                    tp[c] += yi[c] && pred[c];
+                    fp[c] += !yi[c] && pred[c];
+                    fn[c] += yi[c] && !pred[c];
+                }
+            }
+            double tps = 0.0, fps = 0.0, fns = 0.0, per = 0.0;
+            for (uint32_t c = 0; c < C; c++) {
+                tps += tp[c];
+                fps += fp[c];
+                fns += fn[c];
+                const double den = 2 * tp[c] + fp[c] + fn[c];
+                per += den > 0 ? 2 * tp[c] / den : 0.0;
+            }
+            const double den = 2 * tps + fps + fns;
+            micro_sum += 100.0 * (den > 0 ? 2 * tps / den : 0.0);
+            macro_sum += 100.0 * (per / C);
+        }
+        printf("Classify: frac %g :F1-MICRO: %.17g :F1-MACRO: %.17g\n", frac, micro_sum / splits, macro_sum / splits);
+    }
+
     // writeToFile, sample/algorithms.h:118-136 (file name rule in f2v_output_name)
     void writeToFile(int option, int bs, INDEXTYPE B, INDEXTYPE IT, INDEXTYPE ns) {
         char name[4096];

@@ -10,7 +10,8 @@
 // -loss <k> (print the training objective after every k-th epoch and the last, in the line the reference has commented out),
 // -nearest <k> [-metric dot|l2|cos] (after training: every vertex's k nearest rows as "<embd output name>.nn" and the
 // graph-reconstruction precision@k; default metric: the option's own similarity), -cluster <k> [-cluster-iters <n>]
-// [-cluster-restarts <r>] (after training: k-means on the embedding as "<embd output name>.clu" and its modularity on the graph).
+// [-cluster-restarts <r>] (after training: k-means on the embedding as "<embd output name>.clu" and its modularity on the graph),
+// -classify <labels file> [-classify-frac <f>] [-classify-splits <s>] (after training: node-classification F1 of the embedding).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -32,8 +33,9 @@ struct Settings {
     std::string input, output, init;
     long batch = 384, iter = 1200, threads = (long)std::thread::hardware_concurrency(), dim = 128, nsamples = 5, option = 5, bs = 0;
     long device = 0, seed = 1, cache = 0, binout = 0, fastrng = 0, notext = 0, gpus = 1, samegpu = 0, loss = 0, nearest = 0, cluster = 0, cluster_iters = 300, cluster_restarts = 10;
-    std::string metric;
-    double gamma = 1.0, lr = 0.02;
+    std::string metric, classify;
+    long classify_splits = 10;
+    double gamma = 1.0, lr = 0.02, classify_frac = 0.1;
 };
 
 enum class Kind { Text, Integer, Real };
@@ -99,6 +101,9 @@ int main(int argc, char *argv[]) {
         {"-cluster", Kind::Integer, &s.cluster, "<int>, k in 1..1024: after training cluster the embedding with k-means on the GPU, write <output file>.clu, one line per vertex \"v label\" (0-based), and print the clustering's modularity on the graph (one GPU; seeded by -seed). (default:0)"},
         {"-cluster-iters", Kind::Integer, &s.cluster_iters, "<int>, most Lloyd iterations of a -cluster run. (default:300)"},
         {"-cluster-restarts", Kind::Integer, &s.cluster_restarts, "<int>, seeded runs of -cluster, the one of lowest inertia is kept (the scorer's n_init). (default:10)"},
+        {"-classify", Kind::Text, &s.classify, "<string>, a labels file of lines \"vertex label\" (1-based vertex ids, labels 0..C-1, C <= 64): after training fit a one-vs-rest logistic regression on a share of the labelled vertices on the GPU and print \"Classify: frac <f> :F1-MICRO: <x> :F1-MACRO: <y>\", the mean F1 of the others in percent (one GPU; splits seeded by -seed)."},
+        {"-classify-frac", Kind::Real, &s.classify_frac, "<float>, share of the labelled vertices a -classify split trains on, in (0, 1). (default:0.1)"},
+        {"-classify-splits", Kind::Integer, &s.classify_splits, "<int>, seeded splits of -classify whose F1 values are averaged. (default:10)"},
         {"-metric", Kind::Text, &s.metric, "<string>, similarity of -nearest: dot | l2 | cos. (default: l2 for options 5, 8, 11, dot for the sigmoid options)"},
     };
     const size_t nflags = sizeof flags / sizeof flags[0];
@@ -173,6 +178,18 @@ int main(int argc, char *argv[]) {
         printf("-cluster is not available with -gpus > 1 (it clusters one GPU's matrix).\n");
         return 1;
     }
+    if (!s.classify.empty() && !(s.classify_frac > 0.0 && s.classify_frac < 1.0)) {
+        printf("-classify-frac must be above 0 and below 1.\n");
+        return 1;
+    }
+    if (!s.classify.empty() && (s.classify_splits < 1 || s.classify_splits > 0x7FFFFFFF)) {
+        printf("-classify-splits must be at least 1.\n");
+        return 1;
+    }
+    if (!s.classify.empty() && s.gpus > 1) {
+        printf("-classify is not available with -gpus > 1 (it scores one GPU's matrix).\n");
+        return 1;
+    }
     std::vector<VALUETYPE> seconds;
     int rank = 0;
     std::string meet;  // directory the ranks of a -gpus run meet in
@@ -216,6 +233,7 @@ int main(int argc, char *argv[]) {
             }
             if (s.nearest > 0 && rank == 0) algo.writeNearest((uint32_t)s.nearest, metric, s.metric.c_str());
             if (s.cluster > 0 && rank == 0) algo.writeClusters((uint32_t)s.cluster, (uint32_t)s.cluster_iters, (uint32_t)s.cluster_restarts, (uint64_t)s.seed);
+            if (!s.classify.empty() && rank == 0) algo.classify(s.classify, s.classify_frac, (uint32_t)s.classify_splits, (uint64_t)s.seed);
             const double t = algo.gpu_train_seconds;
             if (rank == 0 && s.gpus == 1)
                 printf("GPU epoch loop: %.6f s, %.4g nnz/s, %.1f GB/s algorithmic\n", t, t > 0 ? algo.stats.nnz / t : 0.0,

@@ -34,6 +34,7 @@
 #include "f2v_kernels.hip.h"
 #include "f2v_nearest.hip.h"
 #include "f2v_kmeans.hip.h"
+#include "f2v_logreg.hip.h"
 
 using namespace f2v;
 
@@ -176,6 +177,15 @@ struct f2v_ctx {
         uint32_t block = 0;
         uint32_t lds_allowed = 0;  // kmeans_assign_kernel instantiations whose dynamic-LDS limit has been raised
     } km;
+    // logistic regression (f2v_logreg_*): the workspace f2v.h states, allocated on first use and grown for a larger call
+    struct Logreg {
+        uint32_t *d_a = nullptr, *d_b = nullptr, *d_cmap = nullptr;
+        uint8_t *d_y = nullptr;
+        double *d_W = nullptr, *d_sums = nullptr, *d_part = nullptr, *d_z = nullptr;
+        size_t cap_m = 0, cap_y = 0, cap_part = 0, cap_z = 0;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        uint32_t lds_allowed = 0;  // logreg_kernel instantiations whose dynamic-LDS limit has been raised
+    } lr;
     uint32_t last_wide_width = 0;  // the layout width of the last wide-form f2v_train ("last_wide_width")
     bool last_wide_early = false;  // ... and whether it ran the kernel's EARLY form ("last_wide_early")
     int last_train_form = 0;  // how the last f2v_train launched: 0 one launch per minibatch, 1 chained, 2 chained in the wide form ("last_train_form")
@@ -2232,7 +2242,8 @@ int f2v_destroy(f2v_handle c) {
                     c->d_partials, c->d_table, c->d_items, c->d_hubs, c->d_ready, c->d_kerr, c->d_wg, c->d_rowflag, c->d_snap, c->d_wide, c->d_jobs, c->d_ring, c->d_ring_partials, c->d_ring_flags, c->d_ring_ready, c->d_obj_items, c->d_obj_part, c->d_obj_out, c->push.flags, c->push.d_err, c->push.d_masks, c->push.d_patch, c->push.landing_buf,
                     c->nn.d_Q, c->nn.d_rq, c->nn.d_rc, c->nn.d_scores, c->nn.d_qids, c->nn.d_ids, c->nn.d_ws, c->nn.d_counts,
                     c->km.d_C, c->km.d_bestC, c->km.d_dist, c->km.d_labels, c->km.d_bestL, c->km.d_order, c->km.d_hist, c->km.d_counts, c->km.d_start, c->km.d_pstart,
-                    c->km.d_changed, c->km.d_seed, c->km.d_mlabels, c->km.d_psum, c->km.d_ipart, c->km.d_inertia, c->km.d_tallies};
+                    c->km.d_changed, c->km.d_seed, c->km.d_mlabels, c->km.d_psum, c->km.d_ipart, c->km.d_inertia, c->km.d_tallies,
+                    c->lr.d_a, c->lr.d_b, c->lr.d_cmap, c->lr.d_y, c->lr.d_W, c->lr.d_sums, c->lr.d_part, c->lr.d_z};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
 #ifdef F2V_TEST_HOOKS
@@ -2245,6 +2256,8 @@ int f2v_destroy(f2v_handle c) {
     for (hipEvent_t e : c->nn.ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->km.ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->lr.ev)
         if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -3423,6 +3436,203 @@ int kmeans_run(f2v_ctx *c, uint32_t k, uint32_t max_iters, uint32_t *iterations,
     }
 }
 
+// ---- logistic regression (f2v_logreg.hip.h; definition in include/f2v.h) ----------------------------------------------------------
+constexpr uint32_t kLrDecisionChunk = 262144;  // samples per launch of f2v_logreg_decision: bounds its z buffer
+
+template <class T>
+int lr_grow(f2v_ctx *c, T *&p, size_t &cap, size_t count) {
+    if (p && cap >= count) return F2V_OK;
+    HIPC(hipStreamSynchronize(c->stream));
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    hipError_t e = hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T));
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? F2V_ENOMEM : F2V_ENODEV, "logistic-regression workspace: %s", hipGetErrorString(e));
+    cap = count;
+    return F2V_OK;
+}
+
+template <bool EVAL, int NA, int NZ>
+int launch_logreg_t(f2v_ctx *c, const LrArgs &a, uint32_t form) {
+    const size_t lds = lr_lds_bytes(a.D, a.cg);
+    if (lds > 65536 && !(c->lr.lds_allowed & (1u << form))) {
+        HIPC(hipFuncSetAttribute(reinterpret_cast<const void *>(&logreg_kernel<EVAL, NA, NZ>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        c->lr.lds_allowed |= 1u << form;
+    }
+    hipLaunchKernelGGL((logreg_kernel<EVAL, NA, NZ>), dim3((a.m + kLrBlock - 1) / kLrBlock, (a.nc + a.cg - 1) / a.cg), dim3(kLrThreads), lds, c->stream, a);
+    HIPC(hipGetLastError());
+    return F2V_OK;
+}
+
+// The instantiation for the call's class group: NZ logits per thread hold 8 NZ classes, NA gradient sums per thread hold 256 NA slots of
+// classes x Dp (Dp: the power of two that holds D).  4 NZ sums serve D <= 128; twice and four times as many D <= 256 and D <= 512,
+// where lr_group admits 32 and 16 classes.
+int launch_logreg(f2v_ctx *c, const LrArgs &a, bool eval) {
+    uint32_t nz = 1;
+    while (nz * kLrGroups < a.cg) nz *= 2;
+    const uint32_t wide = a.lg > 7 ? a.lg - 7 : 0;
+    if (!eval) return nz == 1 ? launch_logreg_t<false, 1, 1>(c, a, 0) : nz == 2 ? launch_logreg_t<false, 1, 2>(c, a, 1) : nz == 4 ? launch_logreg_t<false, 1, 4>(c, a, 2)
+                                                                                                                                  : launch_logreg_t<false, 1, 8>(c, a, 3);
+    switch (nz << (4 * wide)) {
+    case 0x001: return launch_logreg_t<true, 4, 1>(c, a, 4);
+    case 0x002: return launch_logreg_t<true, 8, 2>(c, a, 5);
+    case 0x004: return launch_logreg_t<true, 16, 4>(c, a, 6);
+    case 0x008: return launch_logreg_t<true, 32, 8>(c, a, 7);
+    case 0x010: return launch_logreg_t<true, 8, 1>(c, a, 8);
+    case 0x020: return launch_logreg_t<true, 16, 2>(c, a, 9);
+    case 0x040: return launch_logreg_t<true, 32, 4>(c, a, 10);
+    case 0x100: return launch_logreg_t<true, 16, 1>(c, a, 11);
+    case 0x200: return launch_logreg_t<true, 32, 2>(c, a, 12);
+    }
+    return fail(F2V_EINVAL, "logistic regression: no kernel for %u classes per workgroup at dim %u", a.cg, a.D);
+}
+
+// The entry points' common checks and the upload of the samples (and targets).  On success the ids are in lr.d_a / lr.d_b.
+int logreg_enter(f2v_ctx *c, const char *who, const uint32_t *a_ids, const uint32_t *b_ids, uint32_t m, int feature, const uint8_t *y, uint32_t classes) {
+    if (m == 0) return fail(F2V_EINVAL, "%s: m = 0 samples", who);
+    if (m > 0xFFFFFFFFu - kLrBlock) return fail(F2V_EINVAL, "%s: too many samples for 32-bit sample blocks", who);
+    if (classes == 0 || classes > F2V_LOGREG_MAX_CLASSES) return fail(F2V_EINVAL, "%s: classes = %u is outside 1..%d", who, classes, F2V_LOGREG_MAX_CLASSES);
+    if (b_ids && (feature < F2V_PAIR_HADAMARD || feature > F2V_PAIR_AVERAGE)) return fail(F2V_EINVAL, "%s: unknown pair feature %d", who, feature);
+    for (uint32_t i = 0; i < m; i++)
+        if (a_ids[i] >= c->n || (b_ids && b_ids[i] >= c->n))
+            return fail(F2V_EINVAL, "%s: sample %u names vertex %u of %u", who, i, a_ids[i] >= c->n ? a_ids[i] : b_ids[i], c->n);
+    const size_t ybytes = (size_t)m * classes;
+    for (size_t i = 0; y && i < ybytes; i++)
+        if (y[i] > 1) return fail(F2V_EINVAL, "%s: target %zu of sample %zu is %u, not 0 or 1", who, i % classes, i / classes, (unsigned)y[i]);
+    if (!c->have_x)
+        return fail(F2V_ESTATE, c->x_invalid ? "%s: the embeddings are invalid since a launch gave up a bounded wait: set or initialise them again"
+                                             : "%s: embeddings were never initialised", who);
+    HIPC(hipSetDevice(c->device));
+    int rc = flush_pending(c);
+    if (rc != F2V_OK) return rc;
+    f2v_ctx::Logreg &w = c->lr;
+    for (hipEvent_t &e : w.ev)
+        if (!e) HIPC(hipEventCreate(&e));
+    const size_t E = (size_t)c->D + 2;
+    if (!w.d_W) {
+        size_t cap = 0;
+        if ((rc = lr_grow(c, w.d_W, cap, (size_t)F2V_LOGREG_MAX_CLASSES * E)) != F2V_OK) return rc;
+        if ((rc = lr_grow(c, w.d_sums, cap = 0, (size_t)F2V_LOGREG_MAX_CLASSES * E)) != F2V_OK) return rc;
+        if ((rc = lr_grow(c, w.d_cmap, cap = 0, F2V_LOGREG_MAX_CLASSES)) != F2V_OK) return rc;
+    }
+    if (w.cap_m < m) {
+        size_t cap = w.cap_m;
+        if ((rc = lr_grow(c, w.d_a, cap, m)) != F2V_OK) return rc;
+        w.cap_m = 0;
+        if ((rc = lr_grow(c, w.d_b, cap = 0, m)) != F2V_OK) return rc;
+        w.cap_m = m;
+    }
+    HIPC(hipMemcpyAsync(w.d_a, a_ids, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (b_ids) HIPC(hipMemcpyAsync(w.d_b, b_ids, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (y) {
+        if ((rc = lr_grow(c, w.d_y, w.cap_y, ybytes)) != F2V_OK) return rc;
+        if ((rc = lr_grow(c, w.d_part, w.cap_part, (size_t)((m + kLrBlock - 1) / kLrBlock) * classes * E)) != F2V_OK) return rc;
+        HIPC(hipMemcpyAsync(w.d_y, y, ybytes, hipMemcpyHostToDevice, c->stream));
+    }
+    return F2V_OK;
+}
+
+LrArgs logreg_args(f2v_ctx *c, bool pairs, uint32_t m, int feature, uint32_t nc, uint32_t classes) {
+    LrArgs a{};
+    a.X = c->d_X[c->cur];
+    a.a = c->lr.d_a;
+    a.b = pairs ? c->lr.d_b : c->lr.d_a;
+    a.y = c->lr.d_y;
+    a.cmap = c->lr.d_cmap;
+    a.W = c->lr.d_W;
+    a.m = m;
+    a.D = c->D;
+    a.nc = nc;
+    a.C = classes;
+    a.cg = lr_group(c->D, nc);
+    a.lg = lr_log2(c->D);
+    a.feature = pairs ? feature : kLrRow;
+    return a;
+}
+
+// One pass over the uploaded samples: J and its gradient for the nc classes whose target columns are cmap[], at the weights W
+// (nc x (D + 1)) -> loss[nc], grad[nc x (D + 1)]; *seconds += the device time of the launches.
+int logreg_pass(f2v_ctx *c, bool pairs, uint32_t m, int feature, uint32_t classes, const uint32_t *cmap, uint32_t nc, const double *W, double lambda,
+                double *loss, double *grad, double *seconds) {
+    f2v_ctx::Logreg &w = c->lr;
+    const uint32_t D = c->D, E = D + 2, blocks = (m + kLrBlock - 1) / kLrBlock;
+    HIPC(hipMemcpyAsync(w.d_cmap, cmap, (size_t)nc * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(w.d_W, W, (size_t)nc * (D + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    LrArgs a = logreg_args(c, pairs, m, feature, nc, classes);
+    a.out = w.d_part;
+    HIPC(hipEventRecord(w.ev[0], c->stream));
+    int rc = launch_logreg(c, a, true);
+    if (rc != F2V_OK) return rc;
+    hipLaunchKernelGGL(logreg_reduce_kernel, dim3((nc * E + 255) / 256), dim3(256), 0, c->stream, (const double *)w.d_part, blocks, nc * E, w.d_sums);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(w.ev[1], c->stream));
+    std::vector<double> sums((size_t)nc * E);
+    HIPC(hipMemcpyAsync(sums.data(), w.d_sums, sums.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    HIPC(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
+    if (seconds) *seconds += ms * 1e-3;
+    for (uint32_t k = 0; k < nc; k++) {  // the regulariser, as f2v.h orders it
+        const double *wk = W + (size_t)k * (D + 1), *sk = sums.data() + (size_t)k * E;
+        double q = 0.0;
+        for (uint32_t d = 0; d < D; d++) q = std::fma(wk[d], wk[d], q);
+        loss[k] = std::fma(0.5 * lambda, q, sk[D + 1]);
+        for (uint32_t d = 0; d < D; d++) grad[(size_t)k * (D + 1) + d] = std::fma(lambda, wk[d], sk[d]);
+        grad[(size_t)k * (D + 1) + D] = sk[D];
+    }
+    return F2V_OK;
+}
+
+// ---- the solver of f2v.h: one L-BFGS state per class, plain fp64, sums in ascending order
+struct LbfgsClass {
+    std::vector<double> w, g, p, trial;
+    std::vector<std::vector<double>> S, Y;  // oldest first
+    std::vector<double> rho;
+    double f = 0.0, t = 0.0, gp = 0.0, gnorm = 0.0;
+    uint32_t iterations = 0, evaluations = 0, halvings = 0, converged = 0;
+    bool active = true, searching = false;
+};
+
+double lr_dot(const std::vector<double> &a, const std::vector<double> &b) {
+    double s = 0.0;
+    for (size_t i = 0; i < a.size(); i++) s += a[i] * b[i];
+    return s;
+}
+
+double lr_norm_inf(const std::vector<double> &a) {
+    double s = 0.0;
+    for (double v : a) s = std::fabs(v) > s || std::isnan(v) ? std::fabs(v) : s;
+    return s;
+}
+
+// the two-loop recursion -> p = -H g; steepest descent where there is no pair or H g does not descend
+void lbfgs_direction(LbfgsClass &k) {
+    const size_t n = k.g.size();
+    std::vector<double> q = k.g, alpha(k.S.size());
+    for (size_t i = k.S.size(); i-- > 0;) {
+        alpha[i] = k.rho[i] * lr_dot(k.S[i], q);
+        for (size_t j = 0; j < n; j++) q[j] -= alpha[i] * k.Y[i][j];
+    }
+    if (!k.S.empty()) {
+        const double gamma = lr_dot(k.S.back(), k.Y.back()) / lr_dot(k.Y.back(), k.Y.back());
+        for (size_t j = 0; j < n; j++) q[j] *= gamma;
+    }
+    for (size_t i = 0; i < k.S.size(); i++) {
+        const double beta = k.rho[i] * lr_dot(k.Y[i], q);
+        for (size_t j = 0; j < n; j++) q[j] += k.S[i][j] * (alpha[i] - beta);
+    }
+    k.p.resize(n);
+    for (size_t j = 0; j < n; j++) k.p[j] = -q[j];
+    k.gp = lr_dot(k.g, k.p);
+    if (!(k.gp < 0.0)) {
+        k.S.clear();
+        k.Y.clear();
+        k.rho.clear();
+        for (size_t j = 0; j < n; j++) k.p[j] = -k.g[j];
+        k.gp = lr_dot(k.g, k.p);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -3545,6 +3755,147 @@ int f2v_modularity(f2v_handle c, const uint32_t *labels, uint32_t n_clusters, do
         if (inside_out) inside_out[i] = t[1 + i];
         if (degree_out) degree_out[i] = t[1 + n_clusters + i];
     }
+    return F2V_OK;
+}
+
+int f2v_logreg_eval(f2v_handle c, const uint32_t *a_ids, const uint32_t *b_ids, uint32_t m, int feature, const uint8_t *y, uint32_t classes,
+                    const double *weights, double lambda, double *loss_out, double *grad_out, double *seconds_out) {
+    if (!c || !a_ids || !y || !weights || !loss_out || !grad_out) return fail(F2V_EINVAL, "f2v_logreg_eval: null argument");
+    if (!(lambda >= 0.0)) return fail(F2V_EINVAL, "f2v_logreg_eval: lambda must be a non-negative number");
+    int rc = logreg_enter(c, "f2v_logreg_eval", a_ids, b_ids, m, feature, y, classes);
+    if (rc != F2V_OK) return rc;
+    uint32_t cmap[F2V_LOGREG_MAX_CLASSES];
+    for (uint32_t k = 0; k < classes; k++) cmap[k] = k;
+    double seconds = 0.0;
+    if ((rc = logreg_pass(c, b_ids != nullptr, m, feature, classes, cmap, classes, weights, lambda, loss_out, grad_out, &seconds)) != F2V_OK) return rc;
+    if ((rc = check_kernel_err(c, "f2v_logreg_eval")) != F2V_OK) return rc;
+    if (seconds_out) *seconds_out = seconds;
+    return F2V_OK;
+}
+
+int f2v_logreg_fit(f2v_handle c, const uint32_t *a_ids, const uint32_t *b_ids, uint32_t m, int feature, const uint8_t *y, uint32_t classes,
+                   double lambda, double tol, uint32_t max_iter, double *weights_out, f2v_logreg_t *info_out) {
+    if (!c || !a_ids || !y || !weights_out || !info_out) return fail(F2V_EINVAL, "f2v_logreg_fit: null argument");
+    if (!(lambda >= 0.0)) return fail(F2V_EINVAL, "f2v_logreg_fit: lambda must be a non-negative number");
+    if (!(tol > 0.0)) return fail(F2V_EINVAL, "f2v_logreg_fit: tol must be positive");
+    int rc = logreg_enter(c, "f2v_logreg_fit", a_ids, b_ids, m, feature, y, classes);
+    if (rc != F2V_OK) return rc;
+    const uint32_t D = c->D, P = D + 1;
+    const bool pairs = b_ids != nullptr;
+    const double stop = tol * (double)m;
+    std::vector<LbfgsClass> cls(classes);
+    std::vector<uint32_t> cmap(classes);
+    std::vector<double> W((size_t)classes * P, 0.0), loss(classes), grad((size_t)classes * P);
+    double seconds = 0.0;
+    for (uint32_t k = 0; k < classes; k++) cmap[k] = k;
+    if ((rc = logreg_pass(c, pairs, m, feature, classes, cmap.data(), classes, W.data(), lambda, loss.data(), grad.data(), &seconds)) != F2V_OK) return rc;
+    for (uint32_t k = 0; k < classes; k++) {
+        LbfgsClass &s = cls[k];
+        s.w.assign(P, 0.0);
+        s.g.assign(grad.begin() + (size_t)k * P, grad.begin() + (size_t)(k + 1) * P);
+        s.f = loss[k];
+        s.evaluations = 1;
+        s.gnorm = lr_norm_inf(s.g);
+        s.converged = s.gnorm <= stop;
+        s.active = !s.converged && max_iter > 0;
+    }
+    for (;;) {
+        uint32_t nc = 0;
+        for (uint32_t k = 0; k < classes; k++) {
+            LbfgsClass &s = cls[k];
+            if (!s.active) continue;
+            if (!s.searching) {
+                lbfgs_direction(s);
+                double g1 = 0.0;
+                for (double v : s.g) g1 += std::fabs(v);
+                s.t = s.iterations == 0 ? 1.0 / g1 : 1.0;
+                s.halvings = 0;
+                s.searching = true;
+            }
+            s.trial.resize(P);
+            for (uint32_t j = 0; j < P; j++) s.trial[j] = s.w[j] + s.t * s.p[j];
+            std::copy(s.trial.begin(), s.trial.end(), W.begin() + (size_t)nc * P);
+            cmap[nc++] = k;
+        }
+        if (nc == 0) break;
+        if ((rc = logreg_pass(c, pairs, m, feature, classes, cmap.data(), nc, W.data(), lambda, loss.data(), grad.data(), &seconds)) != F2V_OK) return rc;
+        for (uint32_t i = 0; i < nc; i++) {
+            LbfgsClass &s = cls[cmap[i]];
+            s.evaluations++;
+            if (loss[i] <= s.f + 1e-4 * s.t * s.gp) {  // (a NaN loss is no descent)
+                std::vector<double> sv(P), yv(P);
+                for (uint32_t j = 0; j < P; j++) {
+                    sv[j] = s.trial[j] - s.w[j];
+                    yv[j] = grad[(size_t)i * P + j] - s.g[j];
+                }
+                const double sy = lr_dot(sv, yv);
+                if (sy > 0.0) {
+                    if (s.S.size() == 10) {
+                        s.S.erase(s.S.begin());
+                        s.Y.erase(s.Y.begin());
+                        s.rho.erase(s.rho.begin());
+                    }
+                    s.S.push_back(sv);
+                    s.Y.push_back(yv);
+                    s.rho.push_back(1.0 / sy);
+                }
+                s.w = s.trial;
+                s.g.assign(grad.begin() + (size_t)i * P, grad.begin() + (size_t)(i + 1) * P);
+                s.f = loss[i];
+                s.iterations++;
+                s.searching = false;
+                s.gnorm = lr_norm_inf(s.g);
+                s.converged = s.gnorm <= stop;
+                if (s.converged || s.iterations >= max_iter) s.active = false;
+            } else if (++s.halvings > 40) {
+                s.active = false;  // the line search failed: the class stays at its last accepted point
+            } else {
+                s.t *= 0.5;
+            }
+        }
+    }
+    if ((rc = check_kernel_err(c, "f2v_logreg_fit")) != F2V_OK) return rc;
+    for (uint32_t k = 0; k < classes; k++) {
+        const LbfgsClass &s = cls[k];
+        std::copy(s.w.begin(), s.w.end(), weights_out + (size_t)k * P);
+        f2v_logreg_t info{};
+        info.loss = s.f;
+        info.gnorm_inf = s.gnorm;
+        info.seconds = seconds;
+        info.iterations = s.iterations;
+        info.evaluations = s.evaluations;
+        info.converged = s.converged;
+        info_out[k] = info;
+    }
+    return F2V_OK;
+}
+
+int f2v_logreg_decision(f2v_handle c, const uint32_t *a_ids, const uint32_t *b_ids, uint32_t m, int feature, const double *weights, uint32_t classes,
+                        double *z_out, double *seconds_out) {
+    if (!c || !a_ids || !weights || !z_out) return fail(F2V_EINVAL, "f2v_logreg_decision: null argument");
+    int rc = logreg_enter(c, "f2v_logreg_decision", a_ids, b_ids, m, feature, nullptr, classes);
+    if (rc != F2V_OK) return rc;
+    f2v_ctx::Logreg &w = c->lr;
+    if ((rc = lr_grow(c, w.d_z, w.cap_z, (size_t)std::min(m, kLrDecisionChunk) * classes)) != F2V_OK) return rc;
+    HIPC(hipMemcpyAsync(w.d_W, weights, (size_t)classes * (c->D + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    double seconds = 0.0;
+    for (uint32_t lo = 0; lo < m; lo += kLrDecisionChunk) {
+        const uint32_t cnt = std::min(m - lo, kLrDecisionChunk);
+        LrArgs a = logreg_args(c, b_ids != nullptr, cnt, feature, classes, classes);
+        a.a += lo;
+        a.b += lo;
+        a.out = w.d_z;
+        HIPC(hipEventRecord(w.ev[0], c->stream));
+        if ((rc = launch_logreg(c, a, false)) != F2V_OK) return rc;
+        HIPC(hipEventRecord(w.ev[1], c->stream));
+        HIPC(hipMemcpyAsync(z_out + (size_t)lo * classes, w.d_z, (size_t)cnt * classes * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+        float ms = 0.f;
+        HIPC(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
+        seconds += ms * 1e-3;
+    }
+    if ((rc = check_kernel_err(c, "f2v_logreg_decision")) != F2V_OK) return rc;
+    if (seconds_out) *seconds_out = seconds;
     return F2V_OK;
 }
 

@@ -25,6 +25,24 @@ KMeans = namedtuple("KMeans", "labels centroids inertia iterations converged res
 Modularity = namedtuple("Modularity", "q edges inside degree")
 
 
+# Engine.logreg_fit / Engine.classify / Engine.link_predict (include/f2v.h: logistic regression)
+LogregModel = namedtuple("LogregModel", "weights feature loss gnorm_inf iterations evaluations converged seconds")
+F1 = namedtuple("F1", "micro macro")
+LinkScores = namedtuple("LinkScores", "accuracy f1_macro f1_micro")
+PAIR_FEATURES = {"hadamard": _lib.PAIR_HADAMARD, "l1": _lib.PAIR_L1, "l2": _lib.PAIR_L2, "average": _lib.PAIR_AVERAGE}
+
+
+def _f1(true, pred, classes):
+    """micro / macro F1 in percent of 0/1 matrices [samples, len(classes)] over the given class columns (a class without a
+    prediction and without a true label scores 0, as scikit-learn's f1_score does)."""
+    t, p = true[:, classes].astype(bool), pred[:, classes].astype(bool)
+    tp, fp, fn = (t & p).sum(0).astype(np.float64), (~t & p).sum(0).astype(np.float64), (t & ~p).sum(0).astype(np.float64)
+    den = 2 * tp + fp + fn
+    per = np.where(den > 0, 2 * tp / np.where(den > 0, den, 1), 0.0)
+    den_all = 2 * tp.sum() + fp.sum() + fn.sum()
+    return F1(100.0 * (2 * tp.sum() / den_all if den_all > 0 else 0.0), 100.0 * (sum(per.tolist()) / len(classes)) if len(classes) else 0.0)
+
+
 METRICS = {"dot": _lib.SIM_DOT, "l2": _lib.SIM_L2, "cos": _lib.SIM_COSINE, "cosine": _lib.SIM_COSINE}
 
 
@@ -51,7 +69,7 @@ class Engine:
         h = C.c_void_p()
         self._ck(self._L.f2v_create(_u32(rowptr), _u32(colids), self.n, self.nnz, self.dim, device, C.byref(h)))
         self._h = h
-        self.last_nearest_seconds = self.last_kmeans_seconds = 0.0  # device time of the last query / clustering
+        self.last_nearest_seconds = self.last_kmeans_seconds = self.last_logreg_seconds = 0.0  # device time of the last query / clustering / regression call
 
     def _ck(self, rc):
         check(rc, self._L)  # the error text lives in the library that returned the code
@@ -301,6 +319,109 @@ class Engine:
         self._ck(self._L.f2v_modularity(self._h, _u32(lab), nc, C.byref(q), C.byref(edges), inside.ctypes.data_as(C.POINTER(C.c_uint64)),
                                         degree.ctypes.data_as(C.POINTER(C.c_uint64))))
         return Modularity(q.value, edges.value, inside[:nc], degree[:nc])
+
+    # -- logistic regression (include/f2v.h: definition; a function of the matrix, the samples, the targets and the weights alone) --
+    def _samples(self, ids, pairs, feature):
+        """-> (a, b or None, feature code) of row samples `ids` or of `pairs` = (u, v)"""
+        if (ids is None) == (pairs is None):
+            raise ValueError("logreg: give either ids or pairs")
+        if ids is not None:
+            return np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1), None, _lib.PAIR_HADAMARD
+        a = np.ascontiguousarray(pairs[0], dtype=np.uint32).reshape(-1)
+        b = np.ascontiguousarray(pairs[1], dtype=np.uint32).reshape(-1)
+        if len(a) != len(b):
+            raise ValueError("logreg: pairs must be two arrays of one length")
+        if feature not in PAIR_FEATURES:
+            raise ValueError("logreg: feature must be one of %s" % sorted(PAIR_FEATURES))
+        return a, b, PAIR_FEATURES[feature]
+
+    @staticmethod
+    def _targets(y, m):
+        y = np.ascontiguousarray(y, dtype=np.uint8)
+        y = y.reshape(m, -1) if y.ndim != 2 else y
+        if y.shape[0] != m:
+            raise ValueError("logreg: one row of targets per sample")
+        return np.ascontiguousarray(y)
+
+    def logreg_eval(self, weights, y, ids=None, pairs=None, feature="hadamard", lam=1.0):
+        """Loss and gradient of every class at `weights` (float64 [classes, dim + 1], bias last) -> (loss [classes], grad
+        [classes, dim + 1]); y: 0/1 [m, classes]."""
+        a, b, code = self._samples(ids, pairs, feature)
+        y = self._targets(y, len(a))
+        W = np.ascontiguousarray(weights, dtype=np.float64)
+        if W.shape != (y.shape[1], self.dim + 1):
+            raise ValueError("logreg_eval: weights must be [%d, %d]" % (y.shape[1], self.dim + 1))
+        loss, grad, sec = np.empty(len(W)), np.empty_like(W), C.c_double()
+        self._ck(self._L.f2v_logreg_eval(self._h, _u32(a), _u32(b) if b is not None else None, len(a), code, y.ctypes.data_as(_lib.u8p), y.shape[1],
+                                         W.ctypes.data_as(_lib.f64p), lam, loss.ctypes.data_as(_lib.f64p), grad.ctypes.data_as(_lib.f64p), C.byref(sec)))
+        self.last_logreg_seconds = sec.value
+        return loss, grad
+
+    def logreg_fit(self, ids=None, pairs=None, y=None, feature="hadamard", lam=1.0, tol=1e-4, max_iter=100):
+        """One-vs-rest L2-regularised logistic regression on rows `ids` or on `pairs` = (u, v) with the given pair feature, fitted by
+        the L-BFGS of include/f2v.h with every pass over the samples on the GPU -> LogregModel(weights float64 [classes, dim + 1],
+        feature, and per class: loss, gnorm_inf, iterations, evaluations, converged; seconds of device time)."""
+        a, b, code = self._samples(ids, pairs, feature)
+        y = self._targets(y, len(a))
+        nc = y.shape[1]
+        W = np.empty((nc, self.dim + 1), dtype=np.float64)
+        info = (_lib.LogregInfo * max(nc, 1))()
+        self._ck(self._L.f2v_logreg_fit(self._h, _u32(a), _u32(b) if b is not None else None, len(a), code, y.ctypes.data_as(_lib.u8p), nc, lam, tol,
+                                        max_iter, W.ctypes.data_as(_lib.f64p), info))
+        self.last_logreg_seconds = info[0].seconds
+        col = lambda name, dtype: np.array([getattr(info[k], name) for k in range(nc)], dtype=dtype)
+        return LogregModel(W, feature if b is not None else None, col("loss", np.float64), col("gnorm_inf", np.float64), col("iterations", np.uint32),
+                           col("evaluations", np.uint32), col("converged", bool), info[0].seconds)
+
+    def logreg_decision(self, model, ids=None, pairs=None):
+        """The decision values z [m, classes] of `model` (a LogregModel, or weights [classes, dim + 1] with pair feature
+        "hadamard") for unseen samples."""
+        W, feature = (model.weights, model.feature) if isinstance(model, LogregModel) else (model, "hadamard")
+        a, b, code = self._samples(ids, pairs, feature or "hadamard")
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        if W.ndim != 2 or W.shape[1] != self.dim + 1:
+            raise ValueError("logreg_decision: weights must be [classes, %d]" % (self.dim + 1))
+        z, sec = np.empty((len(a), len(W)), dtype=np.float64), C.c_double()
+        self._ck(self._L.f2v_logreg_decision(self._h, _u32(a), _u32(b) if b is not None else None, len(a), code, W.ctypes.data_as(_lib.f64p), len(W),
+                                             z.ctypes.data_as(_lib.f64p), C.byref(sec)))
+        self.last_logreg_seconds = sec.value
+        return z
+
+    def classify(self, labels, train_ids, test_ids, lam=1.0, tol=1e-4, max_iter=100):
+        """Node classification as the reference scores it (performancescores/runnodeclassclust.py): `labels` is a list of label
+        lists, one per vertex; the classes are 0 .. (number of distinct labels) - 1.  Fits on `train_ids`, predicts for every test
+        vertex as many labels as it truly has -- the largest decision values, ties to the lower class -- and returns
+        F1(micro, macro) in percent over all classes."""
+        classes = len({v for l in labels for v in l})
+        train_ids, test_ids = np.asarray(train_ids, dtype=np.uint32), np.asarray(test_ids, dtype=np.uint32)
+
+        def onehot(ids):
+            y = np.zeros((len(ids), classes), dtype=np.uint8)
+            for r, v in enumerate(ids):
+                y[r, [l for l in labels[v] if l < classes]] = 1
+            return y
+
+        model = self.logreg_fit(ids=train_ids, y=onehot(train_ids), lam=lam, tol=tol, max_iter=max_iter)
+        z = self.logreg_decision(model, ids=test_ids)
+        true = onehot(test_ids)
+        order = np.argsort(-z, axis=1, kind="stable")  # descending decision value, ties to the lower class
+        pred = np.zeros_like(true)
+        for r in range(len(test_ids)):
+            pred[r, order[r, :int(true[r].sum())]] = 1
+        return _f1(true, pred, np.arange(classes))
+
+    def link_predict(self, u, v, y, train_frac=0.5, feature="hadamard", lam=1.0, tol=1e-4, max_iter=100):
+        """Link prediction as the reference scores it (performancescores/runlinkpredict.py:127-140): fits on the first
+        int(m * train_frac) pairs (u, v) with 0/1 targets y, predicts z > 0 on the rest -> LinkScores(accuracy, f1_macro, f1_micro)
+        in percent, the F1 values over the labels that occur among the predictions."""
+        u, v, y = np.asarray(u, dtype=np.uint32), np.asarray(v, dtype=np.uint32), np.asarray(y, dtype=np.uint8).reshape(-1)
+        cv = int(len(y) * train_frac)
+        model = self.logreg_fit(pairs=(u[:cv], v[:cv]), y=y[:cv].reshape(-1, 1), feature=feature, lam=lam, tol=tol, max_iter=max_iter)
+        pred = (self.logreg_decision(model, pairs=(u[cv:], v[cv:]))[:, 0] > 0).astype(np.uint8)
+        true = y[cv:]
+        two = lambda a: np.stack([a == 0, a == 1], axis=1)
+        f1 = _f1(two(true), two(pred), np.unique(pred))
+        return LinkScores(100.0 * float((pred == true).mean()) if len(true) else 0.0, f1.macro, f1.micro)
 
     def stats(self):
         s = _lib.Stats()

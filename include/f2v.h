@@ -6,6 +6,10 @@
  * rForce2Vec (CLI options 5-7, and 8-11 as their load-balanced equivalents).  The
  * reference has no FFI of its own; each entry point below names the reference interface
  * it replaces (file:line under the reference tree).  Plain pointers and sizes only.
+ * Beside training, what the reference judges an embedding by is evaluated on the matrix where it lies, in HBM: the training
+ * objective (f2v_objective), nearest rows (f2v_nearest_*), k-means and modularity (f2v_kmeans, f2v_modularity) and the
+ * logistic-regression scorers of node labels and links (f2v_logreg_*).  Each has a definition below that fixes every order of
+ * summation, so that its results are functions of its inputs alone.
  *
  * Conventions: every function returns 0 on success and a negative F2V_E* code on failure
  * (f2v_last_error() then holds a message for the calling thread).  The caller owns every
@@ -395,6 +399,69 @@ F2V_API int f2v_kmeans(f2v_handle h, uint32_t k, uint32_t max_iters, uint32_t re
  * a label >= n_clusters and a CSR whose column ids are not ascending inside every row (rows are searched; checked once per handle). */
 F2V_API int f2v_modularity(f2v_handle h, const uint32_t *labels /* n */, uint32_t n_clusters, double *q_out, uint64_t *edges_out,
                    uint64_t *inside_out, uint64_t *degree_out);
+
+/* ---- logistic regression -----------------------------------------------------------------------------------------------------
+ * The other two scores the reference judges an embedding by: node-classification F1 (performancescores/runnodeclassclust.py:289-309)
+ * and link-prediction accuracy / F1 (performancescores/runlinkpredict.py:127-140) are both an L2-regularised one-vs-rest logistic
+ * regression, fitted on rows of the matrix or on per-pair features of two rows.  fma(a, b, acc) is one correctly rounded fp64 fused
+ * multiply-add.
+ *   samples     m of them; sample i is the vertex a[i] with feature vector f_i = row a[i] (b_ids == NULL), or the pair (a[i], b[i])
+ *               with f_i formed per dimension in fp32, one rounding per operation (runlinkpredict.py:63-72): F2V_PAIR_HADAMARD
+ *               x_a * x_b, F2V_PAIR_L1 |x_a - x_b|, F2V_PAIR_L2 t * t with t = x_a - x_b, F2V_PAIR_AVERAGE (x_a + x_b) * 0.5f;
+ *               subnormals kept; duplicate ids and a == b are legal;
+ *   targets     y: m x C bytes of 0 / 1, one column per class (several columns of a sample may be 1), 1 <= C <= F2V_LOGREG_MAX_CLASSES;
+ *   objective   every class c is a problem of its own over (w_c in R^D, b_c), in fp64, the features converted exactly:
+ *               z_ic = the chain fma(f_id, w_cd, acc) from +0 over ascending d, then + b_c;
+ *               softplus(z) = max(z, 0) + log1p(exp(-|z|)) (as in the objective above), sigma(z) = 1 / (1 + exp(-z)) for z >= 0,
+ *               exp(z) / (1 + exp(z)) below; r_ic = sigma(z_ic) - y_ic; l_ic = softplus(z_ic) - y_ic * z_ic;
+ *               J_c = 0.5 * lambda * sum_d w_cd^2 + sum_i l_ic;  dJ/dw_cd = lambda * w_cd + sum_i r_ic * f_id;  dJ/db_c = sum_i r_ic
+ *               (the bias is not regularised: scikit-learn's lbfgs);
+ *   sums        every sum over samples has one order: the samples in the caller's order are cut into blocks of F2V_LOGREG_BLOCK
+ *               consecutive samples; a block is summed sequentially from +0 -- sum_i r_ic * f_id as fma(r_ic, f_id, acc), the
+ *               others by addition; the block sums are added sequentially from +0 in ascending block order.  The regulariser is
+ *               formed on the host: q_c = the chain fma(w_cd, w_cd, acc) from +0 over ascending d, J_c = fma(0.5 * lambda, q_c,
+ *               sum_i l_ic), dJ/dw_cd = fma(lambda, w_cd, sum_i r_ic * f_id).  No float atomics.
+ * Results are a function of (X, samples, y, weights, lambda) alone: never of launch shapes, of a tunable, of the handle or of the order
+ * in which workgroups run, and bitwise identical between calls, handles and GPUs.
+ *   solver      f2v_logreg_fit minimises every J_c on the host in plain fp64, deterministically, each class with an L-BFGS state of
+ *               its own: start W = 0, b = 0; the last 10 pairs (s, y) of accepted steps, a pair with s.y <= 0 dropped; the direction
+ *               from the two-loop recursion scaled by s.y / y.y of the newest pair (steepest descent without pairs, or where the
+ *               recursion's direction does not descend: the pairs are dropped then); trial step 1 / ||g||_1 in a class's first
+ *               iteration, 1 afterwards; Armijo backtracking J(x + t p) <= J(x) + 1e-4 t g.p, halving t at most 40 times -- a
+ *               class whose line search fails stops where it is with converged = 0; a class stops with converged = 1 once
+ *               ||g||_inf <= tol * m (scikit-learn's test on its objective J / m), and at max_iter iterations (accepted steps).
+ *               All classes still active take their trial points in the same device pass: one pass over the samples serves every
+ *               class.  lambda = 1, tol = 1e-4, max_iter = 100 are LogisticRegression()'s C = 1 and defaults.
+ * The three calls work on the matrix as f2v_get_embeddings would return it (pending minibatches are committed first), run on the
+ * handle's stream and change neither the matrices nor the rand() stream nor any later training result; on a handle attached to a
+ * push exchange they read this rank's replica.  Weights are classes x (D + 1) doubles, a class's bias last.  Workspace, allocated on
+ * first use (grown for a larger call) and freed by f2v_destroy: the ids (2 m words), the targets (m x C bytes), ceil(m / 1024) x C x
+ * (D + 2) doubles of block sums (a class's D + 1 gradient sums and its loss), 2 x C x (D + 2) doubles of weights and results, and for
+ * f2v_logreg_decision min(m, 262144) x C doubles.  seconds: device time between events around the call's own launches.
+ * F2V_ESTATE without valid embeddings; F2V_EINVAL for null pointers, m = 0, classes = 0 or > F2V_LOGREG_MAX_CLASSES, an id >= n, a
+ * target byte above 1, an unknown feature (pairs), a negative or NaN lambda, tol <= 0 or NaN. */
+#define F2V_LOGREG_MAX_CLASSES 64
+#define F2V_LOGREG_BLOCK 1024
+#define F2V_PAIR_HADAMARD 0
+#define F2V_PAIR_L1 1
+#define F2V_PAIR_L2 2
+#define F2V_PAIR_AVERAGE 3
+typedef struct {
+    double loss;       /* J_c at the returned weights */
+    double gnorm_inf;  /* ||grad J_c||_inf there */
+    double seconds;    /* device time of the whole call's launches (the same in every class's entry) */
+    uint32_t iterations, evaluations, converged, reserved;
+} f2v_logreg_t;
+/* One pass: loss_out[c] = J_c and grad_out[c] = (dJ/dw_c, dJ/db_c) of every class at the given weights. */
+F2V_API int f2v_logreg_eval(f2v_handle h, const uint32_t *a_ids, const uint32_t *b_ids /* NULL: row samples */, uint32_t m, int feature,
+                    const uint8_t *y /* m x classes */, uint32_t classes, const double *weights /* classes x (D + 1) */, double lambda,
+                    double *loss_out /* classes */, double *grad_out /* classes x (D + 1) */, double *seconds_out /* may be NULL */);
+F2V_API int f2v_logreg_fit(f2v_handle h, const uint32_t *a_ids, const uint32_t *b_ids, uint32_t m, int feature, const uint8_t *y,
+                   uint32_t classes, double lambda, double tol, uint32_t max_iter, double *weights_out /* classes x (D + 1) */,
+                   f2v_logreg_t *info_out /* classes */);
+/* z_out[i][c] = z_ic of the definition for the given samples and weights; argmax, top-k and F1 are the host's business. */
+F2V_API int f2v_logreg_decision(f2v_handle h, const uint32_t *a_ids, const uint32_t *b_ids, uint32_t m, int feature, const double *weights,
+                        uint32_t classes, double *z_out /* m x classes */, double *seconds_out /* may be NULL */);
 
 /* ---- host-side I/O of the drop-in boundary (no device needed) ----------------------------
  * f2v_read_mtx replaces SetInputMatricesAsCSR (sample/commonutility.h:44-54 -> ReadASCII
