@@ -22,6 +22,7 @@ one-vs-rest logistic regression on rows or pair features with every pass over th
 from . import _lib  # noqa: F401
 from ._lib import F2VError  # noqa: F401
 from ._lib import KMEANS_MAX_K, KMEANS_PIECE  # noqa: F401
+from ._lib import LABEL_NONE, SEPARATION_MAX_CLUSTERS, SEPARATION_PIECE, SEPARATION_SPAN  # noqa: F401
 from ._lib import LOGREG_BLOCK, LOGREG_MAX_CLASSES, PAIR_AVERAGE, PAIR_HADAMARD, PAIR_L1, PAIR_L2  # noqa: F401
 from ._lib import NEAREST_EXCLUDE_NEIGHBOURS, NEAREST_EXCLUDE_SELF, NEAREST_MAX_K, NEAREST_PAD_ID, SIM_COSINE, SIM_DOT, SIM_L2  # noqa: F401
 from .engine import Engine, KMeans, LogregModel, Modularity, algorithms, output_name, push_masks, read_embd, read_embd_bin, sm_table, write_embd, write_embd_bin  # noqa: F401

@@ -17,6 +17,8 @@ NEAREST_PAD_ID = 0xFFFFFFFF  # id of a slot past the last candidate (its score i
 KMEANS_MAX_K, KMEANS_PIECE = 1024, 64
 LOGREG_MAX_CLASSES, LOGREG_BLOCK = 64, 1024
 PAIR_HADAMARD, PAIR_L1, PAIR_L2, PAIR_AVERAGE = 0, 1, 2, 3
+LABEL_NONE = 0xFFFFFFFF  # F2V_LABEL_NONE: the vertex takes no part in a separation score
+SEPARATION_MAX_CLUSTERS, SEPARATION_PIECE, SEPARATION_SPAN = 1024, 64, 64
 
 u32p = C.POINTER(C.c_uint32)
 f32p = C.POINTER(C.c_float)
@@ -88,6 +90,8 @@ SIGNATURES = {
     "f2v_logreg_eval": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32, C.c_int, u8p, C.c_uint32, f64p, C.c_double, f64p, f64p, f64p]),
     "f2v_logreg_fit": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32, C.c_int, u8p, C.c_uint32, C.c_double, C.c_double, C.c_uint32, f64p, C.POINTER(LogregInfo)]),
     "f2v_logreg_decision": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32, C.c_int, f64p, C.c_uint32, f64p, f64p]),
+    "f2v_silhouette": (C.c_int, [C.c_void_p, u32p, C.c_uint32, u32p, C.c_uint32, f64p, u32p, f64p, f64p]),
+    "f2v_davies_bouldin": (C.c_int, [C.c_void_p, u32p, C.c_uint32, f64p, f32p, f64p, C.POINTER(C.c_uint64), f64p]),
     "f2v_push_export": (C.c_int, [C.c_void_p, C.c_void_p]),
     "f2v_push_attach": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "f2v_push_selftest": (C.c_int, [C.c_void_p]),

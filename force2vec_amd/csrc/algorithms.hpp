@@ -170,8 +170,10 @@ class algorithms {
 
     // -cluster <k>: k-means on the trained matrix (f2v_kmeans: `restarts` seeded runs from `seed`, the one of lowest inertia) as
     // "<embd output name>.clu", one line "v label" per vertex (0-based ids), then the modularity of that labelling on the graph.
+    std::vector<uint32_t> cluster_labels;  // of the last writeClusters (-separation kmeans scores them)
     void writeClusters(uint32_t k, uint32_t iters, uint32_t restarts, uint64_t seed) {
-        std::vector<uint32_t> labels(rows);
+        std::vector<uint32_t> &labels = cluster_labels;
+        labels.assign(rows, 0);
         f2v_kmeans_t info{};
         check(f2v_kmeans(h, k, iters, restarts, seed, nullptr, labels.data(), nullptr, nullptr, &info));
         double q = 0.0;
@@ -196,22 +198,29 @@ class algorithms {
         z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
         return z ^ (z >> 31);
     }
-    void classify(const std::string &path, double frac, uint32_t splits, uint64_t seed) {
+    // The labels reader of -classify and -separation: lines "vertex label", 1-based vertex ids, labels 0 .. max_labels - 1; a vertex
+    // may have several lines.  -> the labels of every vertex in file order; seen[l]: label l occurs.
+    std::vector<std::vector<uint32_t>> readLabels(const std::string &path, long max_labels, const char *flag, std::vector<bool> &seen) {
         FILE *f = fopen(path.c_str(), "r");
         if (!f) throw std::runtime_error("cannot read " + path);
         std::vector<std::vector<uint32_t>> labels(rows);
-        std::vector<bool> seen;
         long v = 0, l = 0;
         while (fscanf(f, "%ld %ld", &v, &l) == 2) {
-            if (v < 1 || v > (long)rows || l < 0 || l >= F2V_LOGREG_MAX_CLASSES) {
+            if (v < 1 || v > (long)rows || l < 0 || l >= max_labels) {
                 fclose(f);
-                throw std::runtime_error("-classify: \"" + std::to_string(v) + " " + std::to_string(l) + "\" is outside the graph's vertices or the 64 classes");
+                throw std::runtime_error(std::string(flag) + ": \"" + std::to_string(v) + " " + std::to_string(l) + "\" is outside the graph's vertices or the " +
+                                         std::to_string(max_labels) + " classes");
             }
             labels[v - 1].push_back((uint32_t)l);
             if (seen.size() <= (size_t)l) seen.resize(l + 1, false);
             seen[l] = true;
         }
         fclose(f);
+        return labels;
+    }
+    void classify(const std::string &path, double frac, uint32_t splits, uint64_t seed) {
+        std::vector<bool> seen;
+        const std::vector<std::vector<uint32_t>> labels = readLabels(path, F2V_LOGREG_MAX_CLASSES, "-classify", seen);
         const uint32_t C = (uint32_t)seen.size();
         if (C == 0 || std::find(seen.begin(), seen.end(), false) != seen.end()) throw std::runtime_error("-classify: the labels must be 0 .. C - 1, each used");
         std::vector<uint32_t> labelled;
@@ -267,6 +276,41 @@ class algorithms {
             macro_sum += 100.0 * (per / C);
         }
         printf("Classify: frac %g :F1-MICRO: %.17g :F1-MACRO: %.17g\n", frac, micro_sum / splits, macro_sum / splits);
+    }
+
+    // -separation <labels file | kmeans>: the silhouette and the Davies-Bouldin score of a labelling in the embedding space, the line
+    // performancescores/runvisualization.py prints.  A labels file is read as -classify reads it (a vertex's first label counts,
+    // labels 0 .. 1023); a vertex the file does not name takes no part (F2V_LABEL_NONE).  "kmeans": the labels of this run's -cluster.
+    // sample > 0: the silhouette of that many labelled vertices, the first of the order key(v) = mix64(mix64(seed) ^ v) ascending,
+    // ties by id (as f2v_kmeans seeds its rows), each scored against all labelled vertices; 0: of every labelled vertex.
+    void separation(const std::string &what, uint32_t sample, uint64_t seed) {
+        std::vector<uint32_t> labels;
+        if (what == "kmeans") {
+            labels = cluster_labels;
+        } else {
+            std::vector<bool> seen;
+            const std::vector<std::vector<uint32_t>> all = readLabels(what, F2V_SEPARATION_MAX_CLUSTERS, "-separation", seen);
+            labels.assign(rows, F2V_LABEL_NONE);
+            for (uint32_t v = 0; v < rows; v++)
+                if (!all[v].empty()) labels[v] = all[v][0];
+        }
+        uint32_t k = 0;
+        std::vector<std::pair<uint64_t, uint32_t>> keyed;
+        const uint64_t sm = mix64(seed);
+        for (uint32_t v = 0; v < rows; v++) {
+            if (labels[v] == F2V_LABEL_NONE) continue;
+            k = std::max(k, labels[v] + 1);
+            if (sample) keyed.push_back({mix64(sm ^ (uint64_t)v), v});
+        }
+        std::vector<uint32_t> ids;
+        if (sample) {
+            std::sort(keyed.begin(), keyed.end());
+            for (size_t i = 0; i < keyed.size() && i < sample; i++) ids.push_back(keyed[i].second);
+        }
+        double sil = 0.0, db = 0.0;
+        check(f2v_silhouette(h, labels.data(), k, sample ? ids.data() : nullptr, (uint32_t)ids.size(), nullptr, nullptr, &sil, nullptr));
+        check(f2v_davies_bouldin(h, labels.data(), k, &db, nullptr, nullptr, nullptr, nullptr));
+        printf("silhouette: %.17g davies_bouldin: %.17g\n", sil, db);
     }
 
     // writeToFile, sample/algorithms.h:118-136 (file name rule in f2v_output_name)

@@ -11,7 +11,8 @@
 // -nearest <k> [-metric dot|l2|cos] (after training: every vertex's k nearest rows as "<embd output name>.nn" and the
 // graph-reconstruction precision@k; default metric: the option's own similarity), -cluster <k> [-cluster-iters <n>]
 // [-cluster-restarts <r>] (after training: k-means on the embedding as "<embd output name>.clu" and its modularity on the graph),
-// -classify <labels file> [-classify-frac <f>] [-classify-splits <s>] (after training: node-classification F1 of the embedding).
+// -classify <labels file> [-classify-frac <f>] [-classify-splits <s>] (after training: node-classification F1 of the embedding),
+// -separation <labels file | kmeans> [-separation-sample <n>] (after training: the labelling's silhouette and Davies-Bouldin score).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -33,8 +34,8 @@ struct Settings {
     std::string input, output, init;
     long batch = 384, iter = 1200, threads = (long)std::thread::hardware_concurrency(), dim = 128, nsamples = 5, option = 5, bs = 0;
     long device = 0, seed = 1, cache = 0, binout = 0, fastrng = 0, notext = 0, gpus = 1, samegpu = 0, loss = 0, nearest = 0, cluster = 0, cluster_iters = 300, cluster_restarts = 10;
-    std::string metric, classify;
-    long classify_splits = 10;
+    std::string metric, classify, separation;
+    long classify_splits = 10, separation_sample = 0;
     double gamma = 1.0, lr = 0.02, classify_frac = 0.1;
 };
 
@@ -104,6 +105,8 @@ int main(int argc, char *argv[]) {
         {"-classify", Kind::Text, &s.classify, "<string>, a labels file of lines \"vertex label\" (1-based vertex ids, labels 0..C-1, C <= 64): after training fit a one-vs-rest logistic regression on a share of the labelled vertices on the GPU and print \"Classify: frac <f> :F1-MICRO: <x> :F1-MACRO: <y>\", the mean F1 of the others in percent (one GPU; splits seeded by -seed)."},
         {"-classify-frac", Kind::Real, &s.classify_frac, "<float>, share of the labelled vertices a -classify split trains on, in (0, 1). (default:0.1)"},
         {"-classify-splits", Kind::Integer, &s.classify_splits, "<int>, seeded splits of -classify whose F1 values are averaged. (default:10)"},
+        {"-separation", Kind::Text, &s.separation, "<string>, a labels file as -classify reads it (a vertex's first label counts, labels 0..1023), or \"kmeans\" for the clusters of this run's -cluster: after training print \"silhouette: <x> davies_bouldin: <y>\", how well the labelling separates in the embedding space (one GPU). A vertex the file does not name takes no part (the reference's script gives such vertices a cluster of their own, -1; on a fully labelled graph the two agree)."},
+        {"-separation-sample", Kind::Integer, &s.separation_sample, "<int>, silhouette of that many labelled vertices chosen by -seed, each scored against all labelled vertices; 0 = every labelled vertex. (default:0)"},
         {"-metric", Kind::Text, &s.metric, "<string>, similarity of -nearest: dot | l2 | cos. (default: l2 for options 5, 8, 11, dot for the sigmoid options)"},
     };
     const size_t nflags = sizeof flags / sizeof flags[0];
@@ -190,6 +193,18 @@ int main(int argc, char *argv[]) {
         printf("-classify is not available with -gpus > 1 (it scores one GPU's matrix).\n");
         return 1;
     }
+    if (s.separation == "kmeans" && s.cluster <= 0) {
+        printf("-separation kmeans scores the clusters of -cluster <k>: give it too.\n");
+        return 1;
+    }
+    if (s.separation_sample < 0 || s.separation_sample > 0x7FFFFFFF) {
+        printf("-separation-sample must be a non-negative number of vertices.\n");
+        return 1;
+    }
+    if (!s.separation.empty() && s.gpus > 1) {
+        printf("-separation is not available with -gpus > 1 (it scores one GPU's matrix).\n");
+        return 1;
+    }
     std::vector<VALUETYPE> seconds;
     int rank = 0;
     std::string meet;  // directory the ranks of a -gpus run meet in
@@ -234,6 +249,7 @@ int main(int argc, char *argv[]) {
             if (s.nearest > 0 && rank == 0) algo.writeNearest((uint32_t)s.nearest, metric, s.metric.c_str());
             if (s.cluster > 0 && rank == 0) algo.writeClusters((uint32_t)s.cluster, (uint32_t)s.cluster_iters, (uint32_t)s.cluster_restarts, (uint64_t)s.seed);
             if (!s.classify.empty() && rank == 0) algo.classify(s.classify, s.classify_frac, (uint32_t)s.classify_splits, (uint64_t)s.seed);
+            if (!s.separation.empty() && rank == 0) algo.separation(s.separation, (uint32_t)s.separation_sample, (uint64_t)s.seed);
             const double t = algo.gpu_train_seconds;
             if (rank == 0 && s.gpus == 1)
                 printf("GPU epoch loop: %.6f s, %.4g nnz/s, %.1f GB/s algorithmic\n", t, t > 0 ? algo.stats.nnz / t : 0.0,

@@ -35,6 +35,7 @@
 #include "f2v_nearest.hip.h"
 #include "f2v_kmeans.hip.h"
 #include "f2v_logreg.hip.h"
+#include "f2v_separation.hip.h"
 
 using namespace f2v;
 
@@ -186,6 +187,18 @@ struct f2v_ctx {
         hipEvent_t ev[2] = {nullptr, nullptr};
         uint32_t lds_allowed = 0;  // logreg_kernel instantiations whose dynamic-LDS limit has been raised
     } lr;
+    // separation (f2v_silhouette, f2v_davies_bouldin): beside the clustering workspace (the counting sort, the centroids, the piece
+    // sums) the buffers f2v.h states, allocated on first use and grown for a larger call; "separation_chunk": samples per launch,
+    // "separation_block" (0 = 64 | 64 | 128): sample rows per workgroup of separation_pair_kernel
+    struct Separation {
+        uint32_t *d_ids = nullptr, *d_sid = nullptr, *d_slab = nullptr, *d_other = nullptr, *d_span_start = nullptr, *d_span_cnt = nullptr,
+                 *d_cspan = nullptr;
+        double *d_ws = nullptr, *d_s = nullptr, *d_part = nullptr, *d_S = nullptr, *d_sum = nullptr;
+        size_t cap_ids = 0, cap_sid = 0, cap_slab = 0, cap_other = 0, cap_span_start = 0, cap_span_cnt = 0, cap_cspan = 0, cap_ws = 0, cap_s = 0,
+               cap_part = 0, cap_S = 0, cap_sum = 0;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        uint32_t chunk = 8192, block = 0;
+    } sep;
     uint32_t last_wide_width = 0;  // the layout width of the last wide-form f2v_train ("last_wide_width")
     bool last_wide_early = false;  // ... and whether it ran the kernel's EARLY form ("last_wide_early")
     int last_train_form = 0;  // how the last f2v_train launched: 0 one launch per minibatch, 1 chained, 2 chained in the wide form ("last_train_form")
@@ -2109,6 +2122,10 @@ const Param kParams[] = {
     {"nearest_chunk", F2V_FIELD(nn.chunk), kValue, kKeep, in<1, 65536>, "nearest_chunk must be 1..65536"},
     // rows per workgroup of the k-means assignment kernel (0: 256 for k <= 2, 128 for k <= 4, else 64); results do not depend on it
     {"kmeans_block", F2V_FIELD(km.block), kValue, kKeep, one_of<0, 64, 128, 256>, "kmeans_block must be 0, 64, 128 or 256"},
+    // samples per launch of the silhouette: bounds its workspace (chunk x spans doubles); results do not depend on it
+    {"separation_chunk", F2V_FIELD(sep.chunk), kValue, kKeep, in<1, 1048576>, "separation_chunk must be 1..1048576"},
+    // sample rows per workgroup of separation_pair_kernel (0: 64); results do not depend on it
+    {"separation_block", F2V_FIELD(sep.block), kValue, kKeep, one_of<0, 64, 128>, "separation_block must be 0, 64 or 128"},
     {"push_fused", F2V_FIELD(push.fused), kFlag},
     {"push_timeout_ms", F2V_FIELD(push.timeout_ms), kValue, kKeep, in<1, 600000>, "push_timeout_ms must be 1..600000"},
     // takes effect at the next f2v_push_export; read: what the exchange in place runs with
@@ -2243,7 +2260,9 @@ int f2v_destroy(f2v_handle c) {
                     c->nn.d_Q, c->nn.d_rq, c->nn.d_rc, c->nn.d_scores, c->nn.d_qids, c->nn.d_ids, c->nn.d_ws, c->nn.d_counts,
                     c->km.d_C, c->km.d_bestC, c->km.d_dist, c->km.d_labels, c->km.d_bestL, c->km.d_order, c->km.d_hist, c->km.d_counts, c->km.d_start, c->km.d_pstart,
                     c->km.d_changed, c->km.d_seed, c->km.d_mlabels, c->km.d_psum, c->km.d_ipart, c->km.d_inertia, c->km.d_tallies,
-                    c->lr.d_a, c->lr.d_b, c->lr.d_cmap, c->lr.d_y, c->lr.d_W, c->lr.d_sums, c->lr.d_part, c->lr.d_z};
+                    c->lr.d_a, c->lr.d_b, c->lr.d_cmap, c->lr.d_y, c->lr.d_W, c->lr.d_sums, c->lr.d_part, c->lr.d_z,
+                    c->sep.d_ids, c->sep.d_sid, c->sep.d_slab, c->sep.d_other, c->sep.d_span_start, c->sep.d_span_cnt, c->sep.d_cspan, c->sep.d_ws, c->sep.d_s,
+                    c->sep.d_part, c->sep.d_S, c->sep.d_sum};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
 #ifdef F2V_TEST_HOOKS
@@ -2258,6 +2277,8 @@ int f2v_destroy(f2v_handle c) {
     for (hipEvent_t e : c->km.ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->lr.ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->sep.ev)
         if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -3633,6 +3654,82 @@ void lbfgs_direction(LbfgsClass &k) {
     }
 }
 
+// ---- separation (f2v_separation.hip.h; definition in include/f2v.h) ----------------------------------------------------------------
+template <class T>
+int sep_grow(f2v_ctx *c, T *&p, size_t &cap, size_t count) {
+    if (p && cap >= count) return F2V_OK;
+    HIPC(hipStreamSynchronize(c->stream));
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    hipError_t e = hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T));
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? F2V_ENOMEM : F2V_ENODEV, "separation workspace: %s", hipGetErrorString(e));
+    cap = count;
+    return F2V_OK;
+}
+
+// What both scores share: the labelling checked, the labelled vertices (ascending id), the member counts
+struct SepLabels {
+    std::vector<uint32_t> ids, lab, counts;  // the labelled vertices, their labels, members per cluster
+    uint32_t nonempty = 0;
+};
+
+int sep_check(f2v_ctx *c, const char *who, const uint32_t *labels, uint32_t n_clusters, SepLabels &L) {
+    if (n_clusters == 0 || n_clusters > F2V_SEPARATION_MAX_CLUSTERS)
+        return fail(F2V_EINVAL, "%s: n_clusters = %u is outside 1..%d", who, n_clusters, F2V_SEPARATION_MAX_CLUSTERS);
+    L.counts.assign(n_clusters, 0);
+    for (uint32_t v = 0; v < c->n; v++) {
+        if (labels[v] == F2V_LABEL_NONE) continue;
+        if (labels[v] >= n_clusters) return fail(F2V_EINVAL, "%s: labels[%u] = %u is neither below n_clusters = %u nor F2V_LABEL_NONE", who, v, labels[v], n_clusters);
+        L.ids.push_back(v);
+        L.lab.push_back(labels[v]);
+        L.counts[labels[v]]++;
+    }
+    for (uint32_t k = 0; k < n_clusters; k++) L.nonempty += L.counts[k] != 0;
+    if (L.nonempty < 2) return fail(F2V_EINVAL, "%s: the labelling has %u non-empty clusters, two are needed", who, L.nonempty);
+    return F2V_OK;
+}
+
+// The state checks, the pending minibatches, the clustering workspace, and the members in cluster order: km.d_order holds the
+// labelled vertices by (label, id), km.d_counts / d_start / d_pstart their counts, starts and first pieces.  The counting sort of
+// f2v_kmeans.hip.h runs over the labelled vertices' places (a vertex without a label is simply not there) and separation_ids_kernel
+// turns the places into vertex ids.
+int sep_enter(f2v_ctx *c, const char *who, const SepLabels &L, uint32_t k) {
+    if (c->n >= 0xFFFFFFFFu - 256u) return fail(F2V_EINVAL, "%s: too many vertices for 32-bit row blocks", who);
+    if (!c->have_x)
+        return fail(F2V_ESTATE, c->x_invalid ? "%s: the embeddings are invalid since a launch gave up a bounded wait: set or initialise them again"
+                                             : "%s: embeddings were never initialised", who);
+    HIPC(hipSetDevice(c->device));
+    int rc = flush_pending(c);
+    if (rc != F2V_OK) return rc;
+    if ((rc = kmeans_workspace(c, k)) != F2V_OK) return rc;
+    f2v_ctx::Kmeans &w = c->km;
+    f2v_ctx::Separation &sp = c->sep;
+    for (hipEvent_t &e : sp.ev)
+        if (!e) HIPC(hipEventCreate(&e));
+    const uint32_t m = (uint32_t)L.ids.size(), blocks = (m + kKmSortBlock - 1) / kKmSortBlock;
+    if ((rc = sep_grow(c, sp.d_ids, sp.cap_ids, m)) != F2V_OK) return rc;
+    HIPC(hipMemcpyAsync(sp.d_ids, L.ids.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(w.d_labels, L.lab.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipEventRecord(sp.ev[0], c->stream));
+    hipLaunchKernelGGL(kmeans_hist_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint32_t *)w.d_labels, m, k, w.d_hist);
+    hipLaunchKernelGGL(kmeans_offsets_kernel, dim3(k), dim3(256), 0, c->stream, w.d_hist, blocks, k, w.d_counts);
+    hipLaunchKernelGGL(kmeans_starts_kernel, dim3(1), dim3(256), 0, c->stream, (const uint32_t *)w.d_counts, k, w.d_start, w.d_pstart);
+    hipLaunchKernelGGL(kmeans_scatter_kernel, dim3(blocks), dim3(64), 0, c->stream, (const uint32_t *)w.d_labels, m, k, (const uint32_t *)w.d_hist,
+                       (const uint32_t *)w.d_start, w.d_order);
+    hipLaunchKernelGGL(separation_ids_kernel, dim3((m + 255) / 256), dim3(256), 0, c->stream, w.d_order, (const uint32_t *)sp.d_ids, m);
+    HIPC(hipGetLastError());
+    return F2V_OK;
+}
+
+template <int RB>
+int launch_pair_t(f2v_ctx *c, SepPairArgs a, uint32_t spans) {
+    a.blocks = (a.nq + RB - 1) / RB;
+    hipLaunchKernelGGL((separation_pair_kernel<RB>), dim3(spans * a.blocks), dim3(kSepThreads), 0, c->stream, a);
+    HIPC(hipGetLastError());
+    return F2V_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3755,6 +3852,181 @@ int f2v_modularity(f2v_handle c, const uint32_t *labels, uint32_t n_clusters, do
         if (inside_out) inside_out[i] = t[1 + i];
         if (degree_out) degree_out[i] = t[1 + n_clusters + i];
     }
+    return F2V_OK;
+}
+
+int f2v_silhouette(f2v_handle c, const uint32_t *labels, uint32_t n_clusters, const uint32_t *sample_ids, uint32_t nq, double *s_out,
+                   uint32_t *other_out, double *score_out, double *seconds_out) {
+    if (!c || !labels || !score_out) return fail(F2V_EINVAL, "f2v_silhouette: null argument");
+    if (sample_ids && nq == 0) return fail(F2V_EINVAL, "f2v_silhouette: nq = 0 samples");
+    SepLabels L;
+    int rc = sep_check(c, "f2v_silhouette", labels, n_clusters, L);
+    if (rc != F2V_OK) return rc;
+    if (L.nonempty >= L.ids.size())
+        return fail(F2V_EINVAL, "f2v_silhouette: %u non-empty clusters for %zu labelled vertices (at most one fewer is allowed)", L.nonempty, L.ids.size());
+    const uint32_t k = n_clusters;
+    if (!sample_ids) nq = (uint32_t)L.ids.size();
+    const uint32_t *sid = sample_ids ? sample_ids : L.ids.data();
+    std::vector<uint32_t> slab(nq);
+    for (uint32_t i = 0; i < nq; i++) {
+        if (sid[i] >= c->n) return fail(F2V_EINVAL, "f2v_silhouette: sample %u names vertex %u of %u", i, sid[i], c->n);
+        if (labels[sid[i]] == F2V_LABEL_NONE) return fail(F2V_EINVAL, "f2v_silhouette: sample %u (vertex %u) has no label", i, sid[i]);
+        slab[i] = labels[sid[i]];
+    }
+    // the spans: cluster by cluster, 4096 members each but a cluster's last
+    std::vector<uint32_t> span_start, span_cnt, cspan(k + 1);
+    uint32_t run = 0;
+    for (uint32_t cl = 0; cl < k; cl++) {
+        cspan[cl] = (uint32_t)span_start.size();
+        for (uint32_t o = 0; o < L.counts[cl]; o += kSepPiece * kSepSpan) {
+            span_start.push_back(run + o);
+            span_cnt.push_back(std::min(L.counts[cl] - o, kSepPiece * kSepSpan));
+        }
+        run += L.counts[cl];
+    }
+    cspan[k] = (uint32_t)span_start.size();
+    const uint32_t spans = cspan[k], chunk = std::min(c->sep.chunk, nq), parts = (nq + kSepPiece - 1) / kSepPiece;
+    const uint32_t rb = c->sep.block ? c->sep.block : 64u;
+    if ((uint64_t)spans * ((chunk + rb - 1) / rb) > 0x7FFFFFFFull) return fail(F2V_EINVAL, "f2v_silhouette: too many workgroups per launch: lower \"separation_chunk\"");
+    if ((rc = sep_enter(c, "f2v_silhouette", L, k)) != F2V_OK) return rc;
+    f2v_ctx::Kmeans &w = c->km;
+    f2v_ctx::Separation &sp = c->sep;
+    if ((rc = sep_grow(c, sp.d_sid, sp.cap_sid, nq)) != F2V_OK || (rc = sep_grow(c, sp.d_slab, sp.cap_slab, nq)) != F2V_OK ||
+        (rc = sep_grow(c, sp.d_other, sp.cap_other, nq)) != F2V_OK || (rc = sep_grow(c, sp.d_s, sp.cap_s, nq)) != F2V_OK ||
+        (rc = sep_grow(c, sp.d_part, sp.cap_part, parts)) != F2V_OK || (rc = sep_grow(c, sp.d_sum, sp.cap_sum, 1)) != F2V_OK ||
+        (rc = sep_grow(c, sp.d_span_start, sp.cap_span_start, spans)) != F2V_OK || (rc = sep_grow(c, sp.d_span_cnt, sp.cap_span_cnt, spans)) != F2V_OK ||
+        (rc = sep_grow(c, sp.d_cspan, sp.cap_cspan, (size_t)k + 1)) != F2V_OK || (rc = sep_grow(c, sp.d_ws, sp.cap_ws, (size_t)spans * chunk)) != F2V_OK)
+        return rc;
+    HIPC(hipMemcpyAsync(sp.d_sid, sid, (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(sp.d_slab, slab.data(), (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(sp.d_span_start, span_start.data(), (size_t)spans * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(sp.d_span_cnt, span_cnt.data(), (size_t)spans * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(sp.d_cspan, cspan.data(), ((size_t)k + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
+        const uint32_t cq = std::min(chunk, nq - q0);
+        SepPairArgs a{};
+        a.X = c->d_X[c->cur];
+        a.order = w.d_order;
+        a.sid = sp.d_sid + q0;
+        a.span_start = sp.d_span_start;
+        a.span_cnt = sp.d_span_cnt;
+        a.ws = sp.d_ws;
+        a.D = c->D;
+        a.nq = cq;
+        a.chunk = chunk;
+        if ((rc = rb == 128 ? launch_pair_t<128>(c, a, spans) : launch_pair_t<64>(c, a, spans)) != F2V_OK) return rc;
+        SepFinishArgs f{};
+        f.ws = sp.d_ws;
+        f.slab = sp.d_slab + q0;
+        f.counts = w.d_counts;
+        f.cspan = sp.d_cspan;
+        f.s = sp.d_s + q0;
+        f.other = sp.d_other + q0;
+        f.nq = cq;
+        f.chunk = chunk;
+        f.k = k;
+        hipLaunchKernelGGL(separation_finish_kernel, dim3((cq + 255) / 256), dim3(256), 0, c->stream, f);
+        HIPC(hipGetLastError());
+    }
+    hipLaunchKernelGGL(separation_piece_kernel, dim3((parts + 255) / 256), dim3(256), 0, c->stream, (const double *)sp.d_s, nq, sp.d_part);
+    hipLaunchKernelGGL(kmeans_inertia_reduce_kernel, dim3(1), dim3(256), 0, c->stream, (const double *)sp.d_part, parts, sp.d_sum);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(sp.ev[1], c->stream));
+    double sum = 0.0;
+    HIPC(hipMemcpyAsync(&sum, sp.d_sum, sizeof sum, hipMemcpyDeviceToHost, c->stream));
+    if (s_out) HIPC(hipMemcpyAsync(s_out, sp.d_s, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (other_out) HIPC(hipMemcpyAsync(other_out, sp.d_other, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    if ((rc = check_kernel_err(c, "f2v_silhouette")) != F2V_OK) return rc;
+    *score_out = sum / (double)nq;
+    float ms = 0.f;
+    HIPC(hipEventElapsedTime(&ms, sp.ev[0], sp.ev[1]));
+    if (seconds_out) *seconds_out = ms * 1e-3;
+    return F2V_OK;
+}
+
+int f2v_davies_bouldin(f2v_handle c, const uint32_t *labels, uint32_t n_clusters, double *score_out, float *centroids_out, double *scatter_out,
+                       uint64_t *counts_out, double *seconds_out) {
+    if (!c || !labels || !score_out) return fail(F2V_EINVAL, "f2v_davies_bouldin: null argument");
+    SepLabels L;
+    int rc = sep_check(c, "f2v_davies_bouldin", labels, n_clusters, L);
+    if (rc != F2V_OK) return rc;
+    const uint32_t k = n_clusters, D = c->D;
+    if ((rc = sep_enter(c, "f2v_davies_bouldin", L, k)) != F2V_OK) return rc;
+    f2v_ctx::Kmeans &w = c->km;
+    f2v_ctx::Separation &sp = c->sep;
+    uint32_t pieces = 0;
+    for (uint32_t cl = 0; cl < k; cl++) pieces += (L.counts[cl] + kSepPiece - 1) / kSepPiece;
+    if ((rc = sep_grow(c, sp.d_part, sp.cap_part, pieces)) != F2V_OK || (rc = sep_grow(c, sp.d_S, sp.cap_S, k)) != F2V_OK) return rc;
+    // the centroids: the k-means update of f2v.h (an empty cluster's row stays zero)
+    KmSumArgs s{};
+    s.X = c->d_X[c->cur];
+    s.order = w.d_order;
+    s.start = w.d_start;
+    s.counts = w.d_counts;
+    s.pstart = w.d_pstart;
+    s.psum = w.d_psum;
+    s.n = c->n;
+    s.D = D;
+    s.k = k;
+    s.lanes = 1;
+    while (s.lanes < 64 && 4 * s.lanes < D) s.lanes *= 2;
+    HIPC(hipMemsetAsync(w.d_C, 0, (size_t)k * D * sizeof(float), c->stream));
+    hipLaunchKernelGGL(kmeans_piece_sum_kernel, dim3((uint32_t)(((size_t)pieces * s.lanes + kKmThreads - 1) / kKmThreads)), dim3(kKmThreads), 0, c->stream, s);
+    hipLaunchKernelGGL(kmeans_centroid_kernel, dim3(k, (D + 31) / 32), dim3(kKmThreads), 0, c->stream, (const double *)w.d_psum, (const uint32_t *)w.d_counts,
+                       (const uint32_t *)w.d_pstart, D, w.d_C);
+    SepScatterArgs a{};
+    a.X = s.X;
+    a.C = w.d_C;
+    a.order = w.d_order;
+    a.start = w.d_start;
+    a.counts = w.d_counts;
+    a.pstart = w.d_pstart;
+    a.part = sp.d_part;
+    a.D = D;
+    a.k = k;
+    hipLaunchKernelGGL(separation_scatter_kernel, dim3(pieces), dim3(64), 0, c->stream, a);
+    hipLaunchKernelGGL(separation_cluster_kernel, dim3((k + 63) / 64), dim3(64), 0, c->stream, (const double *)sp.d_part, (const uint32_t *)w.d_counts,
+                       (const uint32_t *)w.d_pstart, k, sp.d_S);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(sp.ev[1], c->stream));
+    std::vector<float> C((size_t)k * D);
+    std::vector<double> S(k);
+    HIPC(hipMemcpyAsync(C.data(), w.d_C, C.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipMemcpyAsync(S.data(), sp.d_S, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    if ((rc = check_kernel_err(c, "f2v_davies_bouldin")) != F2V_OK) return rc;
+    // K x K centroid distances and the maxima: small, on the host (this translation unit is built without fast-math and without
+    // contraction: fmaf and sqrtf are the single correctly rounded operations of the definition)
+    double total = 0.0;
+    for (uint32_t ci = 0; ci < k; ci++) {
+        if (!L.counts[ci]) continue;
+        double mx = 0.0;
+        bool first = true;
+        for (uint32_t di = 0; di < k; di++) {
+            if (di == ci || !L.counts[di]) continue;
+            const float *x = C.data() + (size_t)ci * D, *y = C.data() + (size_t)di * D;
+            float acc = 0.f;
+            for (uint32_t d = 0; d < D; d++) {
+                const float t = x[d] - y[d];
+                acc = std::fmaf(t, t, acc);
+            }
+            const double M = (double)std::sqrt(acc), ss = S[ci] + S[di];
+            const double R = ss == 0.0 ? 0.0 : ss / M;
+            if (first || R > mx) mx = R;
+            first = false;
+        }
+        total += mx;
+    }
+    *score_out = total / (double)L.nonempty;
+    if (centroids_out) memcpy(centroids_out, C.data(), C.size() * sizeof(float));
+    for (uint32_t i = 0; i < k; i++) {
+        if (scatter_out) scatter_out[i] = S[i];
+        if (counts_out) counts_out[i] = L.counts[i];
+    }
+    float ms = 0.f;
+    HIPC(hipEventElapsedTime(&ms, sp.ev[0], sp.ev[1]));
+    if (seconds_out) *seconds_out = ms * 1e-3;
     return F2V_OK;
 }
 

@@ -70,6 +70,7 @@ class Engine:
         self._ck(self._L.f2v_create(_u32(rowptr), _u32(colids), self.n, self.nnz, self.dim, device, C.byref(h)))
         self._h = h
         self.last_nearest_seconds = self.last_kmeans_seconds = self.last_logreg_seconds = 0.0  # device time of the last query / clustering / regression call
+        self.last_separation_seconds = 0.0  # ... / silhouette or Davies-Bouldin call
 
     def _ck(self, rc):
         check(rc, self._L)  # the error text lives in the library that returned the code
@@ -319,6 +320,45 @@ class Engine:
         self._ck(self._L.f2v_modularity(self._h, _u32(lab), nc, C.byref(q), C.byref(edges), inside.ctypes.data_as(C.POINTER(C.c_uint64)),
                                         degree.ctypes.data_as(C.POINTER(C.c_uint64))))
         return Modularity(q.value, edges.value, inside[:nc], degree[:nc])
+
+    # -- separation (include/f2v.h: definition; a function of the matrix, the labelling and the samples alone) ---------------------
+    def _labelling(self, labels):
+        """-> (uint32 labels with F2V_LABEL_NONE for negative entries, n_clusters = the largest label + 1)"""
+        lab = np.asarray(labels).reshape(-1)
+        if len(lab) != self.n or lab.dtype.kind not in "iu":
+            raise ValueError("separation: one integer label per vertex")
+        wide = lab.astype(np.int64)
+        none = wide < 0 if lab.dtype.kind == "i" else lab == _lib.LABEL_NONE
+        if lab.dtype.kind == "u":
+            wide = np.where(none, -1, wide)
+        out = np.where(none, _lib.LABEL_NONE, wide).astype(np.uint32)
+        return np.ascontiguousarray(out), int(wide.max()) + 1 if len(wide) and wide.max() >= 0 else 1
+
+    def silhouette(self, labels, ids=None, samples=False):
+        """The silhouette of `labels` (any integer array, one per vertex; negative = the vertex takes no part) in the embedding
+        space, on the GPU -> the mean s(i) over the samples `ids` (None: every labelled vertex), or with samples=True
+        (score, s float64[len(ids)], other uint32[len(ids)]: the nearest other cluster of every sample).  Every sample is scored
+        against all labelled vertices.  `last_separation_seconds` keeps the device time."""
+        lab, nc = self._labelling(labels)
+        q = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        nq = int((lab != _lib.LABEL_NONE).sum()) if q is None else len(q)
+        s, other = np.empty(nq, dtype=np.float64), np.empty(nq, dtype=np.uint32)
+        score, sec = C.c_double(), C.c_double()
+        self._ck(self._L.f2v_silhouette(self._h, _u32(lab), nc, _u32(q) if q is not None else None, nq, s.ctypes.data_as(_lib.f64p) if samples else None,
+                                        _u32(other) if samples else None, C.byref(score), C.byref(sec)))
+        self.last_separation_seconds = sec.value
+        return (score.value, s, other) if samples else score.value
+
+    def davies_bouldin(self, labels, details=False):
+        """The Davies-Bouldin score of `labels` in the embedding space, on the GPU -> the score, or with details=True
+        (score, centroids float32[n_clusters, dim], scatter float64[n_clusters], counts uint64[n_clusters])."""
+        lab, nc = self._labelling(labels)
+        centroids, scatter, counts = np.empty((nc, self.dim), dtype=np.float32), np.empty(nc, dtype=np.float64), np.empty(nc, dtype=np.uint64)
+        score, sec = C.c_double(), C.c_double()
+        self._ck(self._L.f2v_davies_bouldin(self._h, _u32(lab), nc, C.byref(score), _f32(centroids), scatter.ctypes.data_as(_lib.f64p),
+                                            counts.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(sec)))
+        self.last_separation_seconds = sec.value
+        return (score.value, centroids, scatter, counts) if details else score.value
 
     # -- logistic regression (include/f2v.h: definition; a function of the matrix, the samples, the targets and the weights alone) --
     def _samples(self, ids, pairs, feature):

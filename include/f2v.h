@@ -7,9 +7,10 @@
  * reference has no FFI of its own; each entry point below names the reference interface
  * it replaces (file:line under the reference tree).  Plain pointers and sizes only.
  * Beside training, what the reference judges an embedding by is evaluated on the matrix where it lies, in HBM: the training
- * objective (f2v_objective), nearest rows (f2v_nearest_*), k-means and modularity (f2v_kmeans, f2v_modularity) and the
- * logistic-regression scorers of node labels and links (f2v_logreg_*).  Each has a definition below that fixes every order of
- * summation, so that its results are functions of its inputs alone.
+ * objective (f2v_objective), nearest rows (f2v_nearest_*), k-means and modularity (f2v_kmeans, f2v_modularity), the
+ * logistic-regression scorers of node labels and links (f2v_logreg_*) and the separation of a labelling in the embedding space
+ * (f2v_silhouette, f2v_davies_bouldin).  Each has a definition below that fixes every order of summation, so that its results are
+ * functions of its inputs alone.
  *
  * Conventions: every function returns 0 on success and a negative F2V_E* code on failure
  * (f2v_last_error() then holds a message for the calling thread).  The caller owns every
@@ -462,6 +463,64 @@ F2V_API int f2v_logreg_fit(f2v_handle h, const uint32_t *a_ids, const uint32_t *
 /* z_out[i][c] = z_ic of the definition for the given samples and weights; argmax, top-k and F1 are the host's business. */
 F2V_API int f2v_logreg_decision(f2v_handle h, const uint32_t *a_ids, const uint32_t *b_ids, uint32_t m, int feature, const double *weights,
                         uint32_t classes, double *z_out /* m x classes */, double *seconds_out /* may be NULL */);
+
+/* ---- separation ------------------------------------------------------------------------------------------------------------------
+ * The fourth score the reference judges an embedding by (performancescores/runvisualization.py prints "silhouette: <x>
+ * davies_bouldin: <y>"): how well a labelling -- ground truth, or the clusters of f2v_kmeans -- separates in the embedding space.
+ * They are scikit-learn's silhouette_score(X, labels) and davies_bouldin_score(X, labels) with the Euclidean metric, defined so that
+ * they are deterministic; fma and dist are those of the clustering definition above:
+ *   labelling   labels[v] < n_clusters, or F2V_LABEL_NONE: such a vertex takes no part, neither as a sample nor as a member of any
+ *               cluster (the reference's script gives unlabelled vertices a cluster of their own, -1; this definition leaves them out);
+ *   distance    d(x, c) = sqrtf(dist(x, c)): dist is the fp32 chain fma(t_d, t_d, acc) from +0 over ascending d with t_d = x_d - c_d
+ *               (one rounded subtraction), the square root one correctly rounded fp32 operation; subnormals kept; always from
+ *               differences, never as |x|^2 + |c|^2 - 2 x.c;
+ *   members     the members of cluster c are the vertices with labels[v] == c in ascending vertex id, n_c of them; they are cut into
+ *               pieces of F2V_SEPARATION_PIECE consecutive members, the pieces into spans of F2V_SEPARATION_SPAN consecutive pieces;
+ *   cluster sum sum_c(i) = the fp64 sum of the fp32 distances d(x_i, x_j) over the members j of c (i itself included where it is a
+ *               member: its distance is +0): a piece is summed sequentially from +0 in member order, the piece sums of a span are
+ *               added sequentially from +0 in ascending order, a cluster's span sums are added sequentially from +0 in ascending
+ *               order.  Nothing is added for a place past a cluster's last member;
+ *   silhouette  with L = labels[i]: a(i) = sum_L(i) / (double)(n_L - 1); b(i) = the smallest m = sum_c(i) / (double)n_c over the
+ *               non-empty clusters c != L, taken in ascending c and replaced only where m < b, other(i) = that c;
+ *               s(i) = (b - a) / max(a, b) with max(a, b) = a > b ? a : b; s(i) = 0 where n_L == 1 or max(a, b) == 0;
+ *   score       the samples in the caller's order (sample_ids == NULL: every labelled vertex in ascending id) are cut into pieces of
+ *               64; the s(i) of a piece are added sequentially from +0, the piece sums are added sequentially from +0 in ascending
+ *               order, the result is divided by the number of samples.  A sample is scored against ALL labelled vertices (scikit-
+ *               learn's sample_size scores a sample against the other samples only); duplicate sample ids are legal;
+ *   Davies-Bouldin   centroid_c of a non-empty cluster = the k-means update above ((float)(fp64 sum in pieces of 64 members / n_c));
+ *               S_c = the fp64 sum of d(x_v, centroid_c) over the members in the piece / span order above, divided by (double)n_c;
+ *               M_cd = (double)d(centroid_c, centroid_d) on the fp32 centroids; R_cd = 0 where S_c + S_d == 0, else (S_c + S_d) /
+ *               M_cd (+inf for coincident centroids); the score is the sequential fp64 sum over the non-empty clusters c ascending
+ *               of max over the non-empty d != c of R_cd (taken in ascending d, replaced only where R > max), divided by their
+ *               number.  Departures from scikit-learn: fp32 distances and centroids instead of fp64 ones; its early `return 0.0`
+ *               where all centroid distances are close to zero is not reproduced (coincident centroids give +inf here, 0 only
+ *               where the scatters vanish too); an empty cluster id below n_clusters is simply not a cluster (scikit-learn
+ *               re-encodes the labels); centroids_out and scatter_out hold zeros for an empty cluster.
+ * Results are a function of (X, labels, samples) alone: never of launch shapes, of "separation_chunk" (f2v_set_param: samples per
+ * launch, default 8192), of "separation_block" (sample rows per workgroup, 0 = automatic | 64 | 128) or of any other tunable, of the
+ * handle or of the order in which workgroups run; no float atomics; bitwise identical between calls, handles and GPUs.
+ * Both calls work on the matrix as f2v_get_embeddings would return it (pending minibatches are committed first), run on the
+ * handle's stream and change neither the matrices nor the rand() stream nor any later training result; on a handle attached to a
+ * push exchange they read this rank's replica.  Workspace, allocated on first use (grown for a larger call) and freed by f2v_destroy:
+ * the clustering workspace of f2v_kmeans for n_clusters (its counting sort, centroids and piece sums are used), the labelled
+ * vertices (n words), per sample 3 words and a double, ceil(samples / 64) doubles of score pieces, per span 2 words, and
+ * min(samples, "separation_chunk") x spans doubles of span sums, spans = sum over c of ceil(n_c / 4096) <= n / 4096 + n_clusters:
+ * one double per (sample, span).  seconds: device time between events around the call's own launches.
+ * F2V_ESTATE without valid embeddings; F2V_EINVAL for null pointers (labels, score_out), n_clusters = 0 or above
+ * F2V_SEPARATION_MAX_CLUSTERS, a label that is neither below n_clusters nor F2V_LABEL_NONE, a sample id >= n or one whose label is
+ * F2V_LABEL_NONE, nq = 0 together with sample_ids, fewer than two non-empty clusters, and for the silhouette as many non-empty
+ * clusters as labelled vertices (scikit-learn's 2 <= n_labels <= n_samples - 1). */
+#define F2V_LABEL_NONE 0xFFFFFFFFu         /* the vertex takes no part: neither a sample nor a member of any cluster */
+#define F2V_SEPARATION_MAX_CLUSTERS 1024
+#define F2V_SEPARATION_PIECE 64            /* members per piece */
+#define F2V_SEPARATION_SPAN 64             /* pieces per span: 4096 members */
+F2V_API int f2v_silhouette(f2v_handle h, const uint32_t *labels /* n */, uint32_t n_clusters,
+                   const uint32_t *sample_ids /* NULL: every labelled vertex, ascending id */, uint32_t nq,
+                   double *s_out /* per sample, may be NULL */, uint32_t *other_out /* per sample: the cluster of b(i), may be NULL */,
+                   double *score_out, double *seconds_out /* may be NULL */);
+F2V_API int f2v_davies_bouldin(f2v_handle h, const uint32_t *labels, uint32_t n_clusters, double *score_out,
+                       float *centroids_out /* n_clusters x D, may be NULL */, double *scatter_out /* n_clusters, may be NULL */,
+                       uint64_t *counts_out /* n_clusters, may be NULL */, double *seconds_out /* may be NULL */);
 
 /* ---- host-side I/O of the drop-in boundary (no device needed) ----------------------------
  * f2v_read_mtx replaces SetInputMatricesAsCSR (sample/commonutility.h:44-54 -> ReadASCII
