@@ -19,6 +19,7 @@ LOGREG_MAX_CLASSES, LOGREG_BLOCK = 64, 1024
 PAIR_HADAMARD, PAIR_L1, PAIR_L2, PAIR_AVERAGE = 0, 1, 2, 3
 LABEL_NONE = 0xFFFFFFFF  # F2V_LABEL_NONE: the vertex takes no part in a separation score
 SEPARATION_MAX_CLUSTERS, SEPARATION_PIECE, SEPARATION_SPAN = 1024, 64, 64
+PCA_PIECE, TRUST_MAX_DIM = 4096, 512
 
 u32p = C.POINTER(C.c_uint32)
 f32p = C.POINTER(C.c_float)
@@ -46,6 +47,15 @@ class KMeansInfo(C.Structure):  # f2v_kmeans_t
 class LogregInfo(C.Structure):  # f2v_logreg_t
     _fields_ = [("loss", C.c_double), ("gnorm_inf", C.c_double), ("seconds", C.c_double), ("iterations", C.c_uint32),
                 ("evaluations", C.c_uint32), ("converged", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PcaInfo(C.Structure):  # f2v_pca_t
+    _fields_ = [("total_variance", C.c_double), ("seconds", C.c_double), ("sweeps", C.c_uint32), ("converged", C.c_uint32)]
+
+
+class TrustInfo(C.Structure):  # f2v_trust_t
+    _fields_ = [("trustworthiness", C.c_double), ("continuity", C.c_double), ("overlap", C.c_double), ("seconds", C.c_double),
+                ("penalty_x", C.c_uint64), ("penalty_y", C.c_uint64), ("hits", C.c_uint64)]
 
 
 # every entry point declared in include/f2v.h: name -> (restype, argtypes)
@@ -92,6 +102,8 @@ SIGNATURES = {
     "f2v_logreg_decision": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32, C.c_int, f64p, C.c_uint32, f64p, f64p]),
     "f2v_silhouette": (C.c_int, [C.c_void_p, u32p, C.c_uint32, u32p, C.c_uint32, f64p, u32p, f64p, f64p]),
     "f2v_davies_bouldin": (C.c_int, [C.c_void_p, u32p, C.c_uint32, f64p, f32p, f64p, C.POINTER(C.c_uint64), f64p]),
+    "f2v_pca": (C.c_int, [C.c_void_p, C.c_uint32, f32p, f64p, f64p, f64p, C.POINTER(PcaInfo)]),
+    "f2v_trustworthiness": (C.c_int, [C.c_void_p, f32p, C.c_uint32, C.c_uint32, u32p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(TrustInfo)]),
     "f2v_push_export": (C.c_int, [C.c_void_p, C.c_void_p]),
     "f2v_push_attach": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "f2v_push_selftest": (C.c_int, [C.c_void_p]),
@@ -133,6 +145,7 @@ TEST_SIGNATURES = {
     "f2v_test_xcd_times": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
     "f2v_test_plan_gather": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]),
     "f2v_test_interaction_stub": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "f2v_test_pca_scatter": (C.c_int, [C.c_void_p, f64p, f64p]),
     "f2v_test_wide_plan_check": (C.c_int, [u32p, u32p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.c_uint32, C.POINTER(C.c_uint64)]),
 }
 

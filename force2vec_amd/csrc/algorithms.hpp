@@ -313,6 +313,42 @@ class algorithms {
         printf("silhouette: %.17g davies_bouldin: %.17g\n", sil, db);
     }
 
+    // -layout <d>: the projection of the trained matrix onto its first d principal components (f2v_pca) as "<embd output name>.lay",
+    // one line "v y1 ... yd" per vertex (1-based ids, %g as the .embd writer), then the line performancescores/runvisualization.py
+    // prints for its picture, extended by the mirror score: f2v_trustworthiness of the layout with k neighbours.  sample > 0: over
+    // that many vertices, the first of the order key(v) = mix64(mix64(seed) ^ v) ascending, ties by id (as -separation-sample), each
+    // ranked against all vertices; 0: over every vertex.
+    void layout(uint32_t d, uint32_t k, uint32_t sample, uint64_t seed) {
+        std::vector<float> y((size_t)rows * d);
+        std::vector<double> var(d);
+        f2v_pca_t info{};
+        check(f2v_pca(h, d, y.data(), nullptr, nullptr, var.data(), &info));
+        const std::string name = last_output + ".lay";
+        FILE *f = fopen(name.c_str(), "w");
+        if (!f) throw std::runtime_error("cannot write " + name);
+        for (uint32_t v = 0; v < rows; v++) {
+            fprintf(f, "%u", v + 1);
+            for (uint32_t c = 0; c < d; c++) fprintf(f, " %g", y[(size_t)v * d + c]);
+            fputc('\n', f);
+        }
+        if (fclose(f) != 0) throw std::runtime_error("cannot write " + name);
+        std::vector<uint32_t> ids;
+        if (sample) {
+            std::vector<std::pair<uint64_t, uint32_t>> keyed;
+            const uint64_t sm = mix64(seed);
+            for (uint32_t v = 0; v < rows; v++) keyed.push_back({mix64(sm ^ (uint64_t)v), v});
+            std::sort(keyed.begin(), keyed.end());
+            for (size_t i = 0; i < keyed.size() && i < sample; i++) ids.push_back(keyed[i].second);
+        }
+        f2v_trust_t t{};
+        check(f2v_trustworthiness(h, y.data(), d, k, sample ? ids.data() : nullptr, (uint32_t)ids.size(), nullptr, nullptr, &t));
+        double kept = 0.0;
+        for (uint32_t c = 0; c < d; c++) kept += var[c];
+        printf("TrustWorthiness: %.17g Continuity: %.17g\n", t.trustworthiness, t.continuity);
+        printf("Layout: d=%u neighbours=%u samples=%u :EXPLAINED-VARIANCE: %.17g :OVERLAP: %.17g :SWEEPS: %u\n", d, k, sample ? (uint32_t)ids.size() : rows,
+               info.total_variance > 0 ? kept / info.total_variance : 0.0, t.overlap, info.sweeps);
+    }
+
     // writeToFile, sample/algorithms.h:118-136 (file name rule in f2v_output_name)
     void writeToFile(int option, int bs, INDEXTYPE B, INDEXTYPE IT, INDEXTYPE ns) {
         char name[4096];

@@ -12,7 +12,9 @@
 // graph-reconstruction precision@k; default metric: the option's own similarity), -cluster <k> [-cluster-iters <n>]
 // [-cluster-restarts <r>] (after training: k-means on the embedding as "<embd output name>.clu" and its modularity on the graph),
 // -classify <labels file> [-classify-frac <f>] [-classify-splits <s>] (after training: node-classification F1 of the embedding),
-// -separation <labels file | kmeans> [-separation-sample <n>] (after training: the labelling's silhouette and Davies-Bouldin score).
+// -separation <labels file | kmeans> [-separation-sample <n>] (after training: the labelling's silhouette and Davies-Bouldin score),
+// -layout <d> [-layout-neighbours <k>] [-layout-sample <n>] (after training: the d-dimensional principal-component layout as
+// "<embd output name>.lay" and its trustworthiness and continuity).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -35,7 +37,7 @@ struct Settings {
     long batch = 384, iter = 1200, threads = (long)std::thread::hardware_concurrency(), dim = 128, nsamples = 5, option = 5, bs = 0;
     long device = 0, seed = 1, cache = 0, binout = 0, fastrng = 0, notext = 0, gpus = 1, samegpu = 0, loss = 0, nearest = 0, cluster = 0, cluster_iters = 300, cluster_restarts = 10;
     std::string metric, classify, separation;
-    long classify_splits = 10, separation_sample = 0;
+    long classify_splits = 10, separation_sample = 0, layout = 0, layout_neighbours = 5, layout_sample = 0;
     double gamma = 1.0, lr = 0.02, classify_frac = 0.1;
 };
 
@@ -107,6 +109,9 @@ int main(int argc, char *argv[]) {
         {"-classify-splits", Kind::Integer, &s.classify_splits, "<int>, seeded splits of -classify whose F1 values are averaged. (default:10)"},
         {"-separation", Kind::Text, &s.separation, "<string>, a labels file as -classify reads it (a vertex's first label counts, labels 0..1023), or \"kmeans\" for the clusters of this run's -cluster: after training print \"silhouette: <x> davies_bouldin: <y>\", how well the labelling separates in the embedding space (one GPU). A vertex the file does not name takes no part (the reference's script gives such vertices a cluster of their own, -1; on a fully labelled graph the two agree)."},
         {"-separation-sample", Kind::Integer, &s.separation_sample, "<int>, silhouette of that many labelled vertices chosen by -seed, each scored against all labelled vertices; 0 = every labelled vertex. (default:0)"},
+        {"-layout", Kind::Integer, &s.layout, "<int>, d in 1..dim: after training write <output file>.lay, one line per vertex \"v y1 ... yd\" (1-based ids): the matrix projected onto its first d principal components on the GPU, and print \"TrustWorthiness: <t> Continuity: <c>\" of that picture and its explained-variance share (one GPU). (default:0)"},
+        {"-layout-neighbours", Kind::Integer, &s.layout_neighbours, "<int>, k in 1..128, below half the number of vertices: the neighbourhood size of the -layout scores. (default:5)"},
+        {"-layout-sample", Kind::Integer, &s.layout_sample, "<int>, score the -layout over that many vertices chosen by -seed, each ranked against all vertices; 0 = every vertex (O(N^2 dim) work). (default:0)"},
         {"-metric", Kind::Text, &s.metric, "<string>, similarity of -nearest: dot | l2 | cos. (default: l2 for options 5, 8, 11, dot for the sigmoid options)"},
     };
     const size_t nflags = sizeof flags / sizeof flags[0];
@@ -205,6 +210,22 @@ int main(int argc, char *argv[]) {
         printf("-separation is not available with -gpus > 1 (it scores one GPU's matrix).\n");
         return 1;
     }
+    if (s.layout < 0 || s.layout > s.dim) {
+        printf("-layout must be 0..-dim (%ld).\n", s.dim);
+        return 1;
+    }
+    if (s.layout_neighbours < 1 || s.layout_neighbours > F2V_NEAREST_MAX_K) {
+        printf("-layout-neighbours must be 1..%d.\n", F2V_NEAREST_MAX_K);
+        return 1;
+    }
+    if (s.layout_sample < 0 || s.layout_sample > 0x7FFFFFFF) {
+        printf("-layout-sample must be a non-negative number of vertices.\n");
+        return 1;
+    }
+    if (s.layout > 0 && s.gpus > 1) {
+        printf("-layout is not available with -gpus > 1 (it projects and scores one GPU's matrix).\n");
+        return 1;
+    }
     std::vector<VALUETYPE> seconds;
     int rank = 0;
     std::string meet;  // directory the ranks of a -gpus run meet in
@@ -250,6 +271,7 @@ int main(int argc, char *argv[]) {
             if (s.cluster > 0 && rank == 0) algo.writeClusters((uint32_t)s.cluster, (uint32_t)s.cluster_iters, (uint32_t)s.cluster_restarts, (uint64_t)s.seed);
             if (!s.classify.empty() && rank == 0) algo.classify(s.classify, s.classify_frac, (uint32_t)s.classify_splits, (uint64_t)s.seed);
             if (!s.separation.empty() && rank == 0) algo.separation(s.separation, (uint32_t)s.separation_sample, (uint64_t)s.seed);
+            if (s.layout > 0 && rank == 0) algo.layout((uint32_t)s.layout, (uint32_t)s.layout_neighbours, (uint32_t)s.layout_sample, (uint64_t)s.seed);
             const double t = algo.gpu_train_seconds;
             if (rank == 0 && s.gpus == 1)
                 printf("GPU epoch loop: %.6f s, %.4g nnz/s, %.1f GB/s algorithmic\n", t, t > 0 ? algo.stats.nnz / t : 0.0,

@@ -36,6 +36,7 @@
 #include "f2v_kmeans.hip.h"
 #include "f2v_logreg.hip.h"
 #include "f2v_separation.hip.h"
+#include "f2v_layout.hip.h"
 
 using namespace f2v;
 
@@ -159,10 +160,10 @@ struct f2v_ctx {
         float *d_Q = nullptr, *d_rq = nullptr, *d_rc = nullptr, *d_scores = nullptr;
         uint32_t *d_qids = nullptr, *d_ids = nullptr;
         unsigned long long *d_ws = nullptr, *d_counts = nullptr;
-        size_t q_cap = 0, ws_cap = 0, out_cap = 0;  // queries d_Q / d_rq / d_qids hold, keys d_ws holds, slots d_ids / d_scores hold
+        size_t q_cap = 0, qf_cap = 0, ws_cap = 0, out_cap = 0;  // queries d_rq / d_qids hold, floats d_Q holds, keys d_ws holds, slots d_ids / d_scores hold
         hipEvent_t ev[2] = {nullptr, nullptr};
         uint32_t splits = 0, block = 0, chunk = 8192;
-        uint32_t lds_allowed = 0;  // nearest_kernel instantiations whose dynamic-LDS limit has been raised (launch_nearest_t)
+        size_t lds_set[4] = {0, 0, 0, 0};  // per nearest_kernel instantiation: the dynamic-LDS limit it has been raised to (launch_nearest_t)
     } nn;
     int rows_sorted = -1;  // the CSR's ids ascend inside every row (rows are searched by the nearest queries and f2v_modularity): -1 not checked yet (rows_ascending)
     // clustering (f2v_kmeans, f2v_modularity): the workspace f2v.h states, allocated on first use for the call's k and grown for a
@@ -199,6 +200,19 @@ struct f2v_ctx {
         hipEvent_t ev[2] = {nullptr, nullptr};
         uint32_t chunk = 8192, block = 0;
     } sep;
+    // layout (f2v_pca, f2v_trustworthiness): the buffers f2v.h states, allocated on first use and grown for a larger call;
+    // "trust_chunk": samples per launch, "trust_block" (0 = 64 | 64 | 128): sample rows per workgroup of trust_rank_kernel
+    struct Layout {
+        double *d_ws = nullptr, *d_mean = nullptr, *d_S = nullptr, *d_W = nullptr;
+        float *d_P = nullptr, *d_Y = nullptr;  // the projection, the caller's second matrix
+        uint32_t *d_sid = nullptr, *d_nx = nullptr, *d_ny = nullptr, *d_hist = nullptr;
+        unsigned long long *d_thr = nullptr, *d_pen = nullptr, *d_sums = nullptr;
+        size_t cap_ws = 0, cap_mean = 0, cap_S = 0, cap_W = 0, cap_P = 0, cap_Y = 0, cap_sid = 0, cap_nx = 0, cap_ny = 0, cap_hist = 0, cap_thr = 0,
+               cap_pen = 0, cap_sums = 0;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        uint32_t chunk = 8192, block = 0;
+        size_t lds_set[2] = {0, 0};  // per trust_rank_kernel instantiation: the dynamic-LDS limit it has been raised to
+    } lay;
     uint32_t last_wide_width = 0;  // the layout width of the last wide-form f2v_train ("last_wide_width")
     bool last_wide_early = false;  // ... and whether it ran the kernel's EARLY form ("last_wide_early")
     int last_train_form = 0;  // how the last f2v_train launched: 0 one launch per minibatch, 1 chained, 2 chained in the wide form ("last_train_form")
@@ -2126,6 +2140,10 @@ const Param kParams[] = {
     {"separation_chunk", F2V_FIELD(sep.chunk), kValue, kKeep, in<1, 1048576>, "separation_chunk must be 1..1048576"},
     // sample rows per workgroup of separation_pair_kernel (0: 64); results do not depend on it
     {"separation_block", F2V_FIELD(sep.block), kValue, kKeep, one_of<0, 64, 128>, "separation_block must be 0, 64 or 128"},
+    // samples per launch of the trustworthiness kernels: bounds their workspace (chunk x k keys and counts); results do not depend on it
+    {"trust_chunk", F2V_FIELD(lay.chunk), kValue, kKeep, in<1, 1048576>, "trust_chunk must be 1..1048576"},
+    // sample rows per workgroup of trust_rank_kernel (0: 64; 128 holds where k <= 32, its thresholds live in LDS); results do not depend on it
+    {"trust_block", F2V_FIELD(lay.block), kValue, kKeep, one_of<0, 64, 128>, "trust_block must be 0, 64 or 128"},
     {"push_fused", F2V_FIELD(push.fused), kFlag},
     {"push_timeout_ms", F2V_FIELD(push.timeout_ms), kValue, kKeep, in<1, 600000>, "push_timeout_ms must be 1..600000"},
     // takes effect at the next f2v_push_export; read: what the exchange in place runs with
@@ -2262,7 +2280,9 @@ int f2v_destroy(f2v_handle c) {
                     c->km.d_changed, c->km.d_seed, c->km.d_mlabels, c->km.d_psum, c->km.d_ipart, c->km.d_inertia, c->km.d_tallies,
                     c->lr.d_a, c->lr.d_b, c->lr.d_cmap, c->lr.d_y, c->lr.d_W, c->lr.d_sums, c->lr.d_part, c->lr.d_z,
                     c->sep.d_ids, c->sep.d_sid, c->sep.d_slab, c->sep.d_other, c->sep.d_span_start, c->sep.d_span_cnt, c->sep.d_cspan, c->sep.d_ws, c->sep.d_s,
-                    c->sep.d_part, c->sep.d_S, c->sep.d_sum};
+                    c->sep.d_part, c->sep.d_S, c->sep.d_sum,
+                    c->lay.d_ws, c->lay.d_mean, c->lay.d_S, c->lay.d_W, c->lay.d_P, c->lay.d_Y, c->lay.d_sid, c->lay.d_nx, c->lay.d_ny, c->lay.d_hist, c->lay.d_thr,
+                    c->lay.d_pen, c->lay.d_sums};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
 #ifdef F2V_TEST_HOOKS
@@ -2279,6 +2299,8 @@ int f2v_destroy(f2v_handle c) {
     for (hipEvent_t e : c->lr.ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->sep.ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->lay.ev)
         if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -3176,10 +3198,10 @@ int train_impl(f2v_ctx *c, int option, uint32_t iters, uint32_t batch, uint32_t 
 template <bool L2, int WQ, int MI, int NI>
 int launch_nearest_t(f2v_ctx *c, const NnArgs &a, uint32_t qblocks, uint32_t splits) {
     const size_t lds = nn_lds_bytes(32u * WQ * MI, a.D);
-    const uint32_t form = 1u << ((L2 ? 2 : 0) + (WQ == 2 ? 1 : 0));
-    if (!(c->nn.lds_allowed & form)) {  // more than 64 KB of dynamic LDS has to be allowed once per kernel (D is fixed per handle)
+    const uint32_t form = (L2 ? 2 : 0) + (WQ == 2 ? 1 : 0);
+    if (c->nn.lds_set[form] < lds) {  // more than 64 KB of dynamic LDS has to be allowed per kernel: once for the handle's D, and again only for a wider second matrix (f2v_trustworthiness)
         HIPC(hipFuncSetAttribute(reinterpret_cast<const void *>(&nearest_kernel<L2, WQ, MI, NI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        c->nn.lds_allowed |= form;
+        c->nn.lds_set[form] = lds;
     }
     hipLaunchKernelGGL((nearest_kernel<L2, WQ, MI, NI>), dim3(qblocks, splits), dim3(kNnThreads), lds, c->stream, a);
     HIPC(hipGetLastError());
@@ -3199,11 +3221,12 @@ int nn_grow(f2v_ctx *c, T *&p, size_t count) {
 // What the three entry points share behind their preamble.  Queries are rows `qids` of the matrix (nullptr with `all`: rows 0 .. nq-1)
 // or the host vectors `vecs`; they are run in chunks of "nearest_chunk" queries, each chunk as gather / norms / nearest_kernel /
 // merge (/ count) on the handle's stream between two events.  ids_out / scores_out may be nullptr (the recall count needs neither).
-int nearest_run(f2v_ctx *c, const uint32_t *qids, bool all, const float *vecs, uint32_t nq, uint32_t k, int metric, uint32_t flags,
-                uint32_t *ids_out, float *scores_out, uint64_t *recall_out, double *seconds_out) {
+// `X`: the n x D matrix that is searched -- the handle's, or f2v_trustworthiness's second matrix (row queries, no cosine, no CSR flag);
+// `d_ids_dst` (may be nullptr): device array that also receives the ids, nq x k.
+int nearest_run_on(f2v_ctx *c, const float *X, uint32_t D, const uint32_t *qids, bool all, const float *vecs, uint32_t nq, uint32_t k, int metric,
+                   uint32_t flags, uint32_t *ids_out, float *scores_out, uint64_t *recall_out, double *seconds_out, uint32_t *d_ids_dst) {
     f2v_ctx::Nearest &w = c->nn;
-    const float *X = c->d_X[c->cur];
-    const uint32_t D = c->D, n = c->n;
+    const uint32_t n = c->n;
     const bool rows = qids || all, cosine = metric == F2V_SIM_COSINE;
     int rc;
     for (hipEvent_t &e : w.ev)
@@ -3216,7 +3239,7 @@ int nearest_run(f2v_ctx *c, const uint32_t *qids, bool all, const float *vecs, u
     std::vector<uint32_t> iota;
     for (uint32_t done = 0; done < nq; done += w.chunk) {
         const uint32_t cq = std::min(w.chunk, nq - done);
-        const uint32_t qb = w.block ? w.block : (D <= 128 && cq > 32 ? 128u : 32u);
+        const uint32_t qb = w.block && !(w.block == 128 && D > 128) ? w.block : (D <= 128 && cq > 32 ? 128u : 32u);
         const uint32_t qblocks = (cq + qb - 1) / qb;
         uint32_t splits = w.splits;
         if (!splits)  // enough workgroups for every CU a few times over, but never more keys per query than the merge reads quickly
@@ -3225,8 +3248,12 @@ int nearest_run(f2v_ctx *c, const uint32_t *qids, bool all, const float *vecs, u
         const uint32_t tps = (tiles + splits - 1) / splits;
         splits = (tiles + tps - 1) / tps;
         if (w.q_cap < cq) {
-            if ((rc = nn_grow(c, w.d_Q, (size_t)cq * D)) != F2V_OK || (rc = nn_grow(c, w.d_rq, cq)) != F2V_OK || (rc = nn_grow(c, w.d_qids, cq)) != F2V_OK) return rc;
+            if ((rc = nn_grow(c, w.d_rq, cq)) != F2V_OK || (rc = nn_grow(c, w.d_qids, cq)) != F2V_OK) return rc;
             w.q_cap = cq;
+        }
+        if (w.qf_cap < (size_t)cq * D) {
+            if ((rc = nn_grow(c, w.d_Q, (size_t)cq * D)) != F2V_OK) return rc;
+            w.qf_cap = (size_t)cq * D;
         }
         const size_t keys = (size_t)qblocks * qb * splits * k, slots = (size_t)cq * k;
         if (w.ws_cap < keys) {
@@ -3275,6 +3302,7 @@ int nearest_run(f2v_ctx *c, const uint32_t *qids, bool all, const float *vecs, u
             hipLaunchKernelGGL(nearest_recall_kernel, dim3((cq + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)w.d_ids, (const uint32_t *)w.d_qids, cq, k,
                                (const uint32_t *)c->d_rowptr, (const uint32_t *)c->d_colids, w.d_counts);
         HIPC(hipGetLastError());
+        if (d_ids_dst) HIPC(hipMemcpyAsync(d_ids_dst + (size_t)done * k, w.d_ids, slots * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
         HIPC(hipEventRecord(w.ev[1], c->stream));
         if (ids_out) HIPC(hipMemcpyAsync(ids_out + (size_t)done * k, w.d_ids, slots * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         if (scores_out) HIPC(hipMemcpyAsync(scores_out + (size_t)done * k, w.d_scores, slots * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -3290,6 +3318,11 @@ int nearest_run(f2v_ctx *c, const uint32_t *qids, bool all, const float *vecs, u
     }
     if (seconds_out) *seconds_out = seconds;
     return F2V_OK;
+}
+
+int nearest_run(f2v_ctx *c, const uint32_t *qids, bool all, const float *vecs, uint32_t nq, uint32_t k, int metric, uint32_t flags,
+                uint32_t *ids_out, float *scores_out, uint64_t *recall_out, double *seconds_out) {
+    return nearest_run_on(c, c->d_X[c->cur], c->D, qids, all, vecs, nq, k, metric, flags, ids_out, scores_out, recall_out, seconds_out, nullptr);
 }
 
 // Do the CSR's column ids ascend inside every row?  Checked once per handle, on the host copy.
@@ -4029,6 +4062,262 @@ int f2v_davies_bouldin(f2v_handle c, const uint32_t *labels, uint32_t n_clusters
     if (seconds_out) *seconds_out = ms * 1e-3;
     return F2V_OK;
 }
+
+}  // extern "C"
+
+// ---- layout (f2v_layout.hip.h; definition in include/f2v.h) -----------------------------------------------------------------------
+namespace {
+
+// The state checks and the pending minibatches (f2v_kmeans's preamble)
+int lay_enter(f2v_ctx *c, const char *who) {
+    if (c->n >= 0xFFFFFFFFu - kPcaPiece) return fail(F2V_EINVAL, "%s: too many vertices for 32-bit pieces", who);
+    if (!c->have_x)
+        return fail(F2V_ESTATE, c->x_invalid ? "%s: the embeddings are invalid since a launch gave up a bounded wait: set or initialise them again"
+                                             : "%s: embeddings were never initialised", who);
+    HIPC(hipSetDevice(c->device));
+    int rc = flush_pending(c);
+    if (rc != F2V_OK) return rc;
+    for (hipEvent_t &e : c->lay.ev)
+        if (!e) HIPC(hipEventCreate(&e));
+    return F2V_OK;
+}
+
+// The mean (lay.d_mean, D doubles) and the packed upper triangle of the scatter matrix (lay.d_S) of the settled matrix, enqueued on
+// the handle's stream: column sums and chains per piece of 4096 vertices, the pieces added in order.
+int pca_moments(f2v_ctx *c) {
+    f2v_ctx::Layout &w = c->lay;
+    const uint32_t n = c->n, D = c->D, pieces = (n + kPcaPiece - 1) / kPcaPiece, tiles = (D + kPcaTile - 1) / kPcaTile;
+    const size_t width = (size_t)D * (D + 1) / 2;
+    int rc;
+    if ((rc = sep_grow(c, w.d_ws, w.cap_ws, (size_t)pieces * width)) != F2V_OK || (rc = sep_grow(c, w.d_mean, w.cap_mean, D)) != F2V_OK ||
+        (rc = sep_grow(c, w.d_S, w.cap_S, width)) != F2V_OK)
+        return rc;
+    const float *X = c->d_X[c->cur];
+    hipLaunchKernelGGL(pca_colsum_kernel, dim3(pieces, (D + 63) / 64), dim3(64), 0, c->stream, X, n, D, w.d_ws);
+    hipLaunchKernelGGL(pca_reduce_kernel, dim3((D + 255) / 256), dim3(256), 0, c->stream, (const double *)w.d_ws, pieces, (size_t)D, (double)n, w.d_mean);
+    PcaScatterArgs a{};
+    a.X = X;
+    a.mean = w.d_mean;
+    a.ws = w.d_ws;
+    a.width = width;
+    a.n = n;
+    a.D = D;
+    a.tiles = tiles;
+    hipLaunchKernelGGL(pca_scatter_kernel, dim3(pieces, tiles * (tiles + 1) / 2), dim3(kPcaThreads), 0, c->stream, a);
+    hipLaunchKernelGGL(pca_reduce_kernel, dim3((uint32_t)((width + 255) / 256)), dim3(256), 0, c->stream, (const double *)w.d_ws, pieces, width, 1.0, w.d_S);
+    HIPC(hipGetLastError());
+    return F2V_OK;
+}
+
+// mean and the full symmetric scatter matrix on the host (and the device time of their launches)
+int pca_moments_host(f2v_ctx *c, std::vector<double> &mean, std::vector<double> &S, double *seconds) {
+    f2v_ctx::Layout &w = c->lay;
+    const uint32_t D = c->D;
+    const size_t width = (size_t)D * (D + 1) / 2;
+    HIPC(hipEventRecord(w.ev[0], c->stream));
+    int rc = pca_moments(c);
+    if (rc != F2V_OK) return rc;
+    HIPC(hipEventRecord(w.ev[1], c->stream));
+    std::vector<double> packed(width);
+    mean.resize(D);
+    HIPC(hipMemcpyAsync(mean.data(), w.d_mean, (size_t)D * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipMemcpyAsync(packed.data(), w.d_S, width * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    if ((rc = check_kernel_err(c, "f2v_pca")) != F2V_OK) return rc;
+    S.resize((size_t)D * D);
+    for (uint32_t d = 0; d < D; d++)
+        for (uint32_t e = d; e < D; e++) S[(size_t)d * D + e] = S[(size_t)e * D + d] = packed[pca_packed(D, d, e)];
+    float ms = 0.f;
+    HIPC(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
+    *seconds = ms * 1e-3;
+    return F2V_OK;
+}
+
+template <int RB>
+int launch_rank_t(f2v_ctx *c, TrustRankArgs a, uint32_t spans) {
+    a.blocks = (a.nq + RB - 1) / RB;
+    const size_t lds = trust_lds_bytes(RB, a.k);
+    size_t &set = c->lay.lds_set[RB == 128];
+    if (lds > 65536 && set < lds) {  // a sample block's thresholds and counts live in LDS: up to 114 KB at k = 128
+        HIPC(hipFuncSetAttribute(reinterpret_cast<const void *>(&trust_rank_kernel<RB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        set = lds;
+    }
+    hipLaunchKernelGGL((trust_rank_kernel<RB>), dim3(spans * a.blocks), dim3(kSepThreads), lds, c->stream, a);
+    HIPC(hipGetLastError());
+    return F2V_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int f2v_pca(f2v_handle c, uint32_t d2, float *y_out, double *components_out, double *mean_out, double *variance_out, f2v_pca_t *info) {
+    if (!c || !info) return fail(F2V_EINVAL, "f2v_pca: null argument");
+    if (d2 == 0 || d2 > c->D) return fail(F2V_EINVAL, "f2v_pca: d2 = %u is outside 1..dim = %u", d2, c->D);
+    if (c->n < 2) return fail(F2V_EINVAL, "f2v_pca: a graph of %u vertices has no variance", c->n);
+    int rc = lay_enter(c, "f2v_pca");
+    if (rc != F2V_OK) return rc;
+    f2v_ctx::Layout &w = c->lay;
+    const uint32_t n = c->n, D = c->D;
+    std::vector<double> mean, A, V((size_t)D * D);
+    double seconds = 0.0;
+    if ((rc = pca_moments_host(c, mean, A, &seconds)) != F2V_OK) return rc;
+    double trace = 0.0;
+    for (uint32_t d = 0; d < D; d++) trace += A[(size_t)d * D + d];
+    uint32_t sweeps = 0, converged = 0;
+    pca_jacobi_host(A.data(), V.data(), D, &sweeps, &converged);
+    // eigenvalue descending, ties by ascending column (a NaN after every number)
+    std::vector<uint32_t> order(D);
+    for (uint32_t d = 0; d < D; d++) order[d] = d;
+    auto lam = [&](uint32_t j) { return A[(size_t)j * D + j]; };
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+        const double lx = lam(x), ly = lam(y);
+        if (lx != lx || ly != ly) return ly != ly && lx == lx;
+        return lx > ly;
+    });
+    std::vector<double> W((size_t)d2 * D);
+    for (uint32_t k = 0; k < d2; k++) {
+        uint32_t big = 0;
+        for (uint32_t d = 0; d < D; d++) {
+            W[(size_t)k * D + d] = V[(size_t)d * D + order[k]];
+            if (std::fabs(W[(size_t)k * D + d]) > std::fabs(W[(size_t)k * D + big])) big = d;
+        }
+        if (W[(size_t)k * D + big] < 0.0)
+            for (uint32_t d = 0; d < D; d++) W[(size_t)k * D + d] = -W[(size_t)k * D + d];
+    }
+    if (y_out) {
+        if ((rc = sep_grow(c, w.d_W, w.cap_W, (size_t)d2 * D)) != F2V_OK || (rc = sep_grow(c, w.d_P, w.cap_P, (size_t)n * d2)) != F2V_OK) return rc;
+        HIPC(hipMemcpyAsync(w.d_W, W.data(), W.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIPC(hipEventRecord(w.ev[0], c->stream));
+        hipLaunchKernelGGL(pca_project_kernel, dim3((uint32_t)(((size_t)n * d2 + 255) / 256)), dim3(256), 0, c->stream, (const float *)c->d_X[c->cur],
+                           (const double *)w.d_mean, (const double *)w.d_W, n, D, d2, w.d_P);
+        HIPC(hipGetLastError());
+        HIPC(hipEventRecord(w.ev[1], c->stream));
+        HIPC(hipMemcpyAsync(y_out, w.d_P, (size_t)n * d2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+        if ((rc = check_kernel_err(c, "f2v_pca")) != F2V_OK) return rc;
+        float ms = 0.f;
+        HIPC(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
+        seconds += ms * 1e-3;
+    }
+    if (components_out) memcpy(components_out, W.data(), W.size() * sizeof(double));
+    if (mean_out) memcpy(mean_out, mean.data(), (size_t)D * sizeof(double));
+    for (uint32_t k = 0; variance_out && k < d2; k++) variance_out[k] = lam(order[k]) / (double)(n - 1);
+    info->total_variance = trace / (double)(n - 1);
+    info->seconds = seconds;
+    info->sweeps = sweeps;
+    info->converged = converged;
+    return F2V_OK;
+}
+
+int f2v_trustworthiness(f2v_handle c, const float *Y, uint32_t d2, uint32_t k, const uint32_t *sample_ids, uint32_t nq, uint64_t *penalty_x_out,
+                        uint64_t *penalty_y_out, f2v_trust_t *out) {
+    if (!c || !Y || !out) return fail(F2V_EINVAL, "f2v_trustworthiness: null argument");
+    if (d2 == 0 || d2 > F2V_TRUST_MAX_DIM) return fail(F2V_EINVAL, "f2v_trustworthiness: d2 = %u is outside 1..%d", d2, F2V_TRUST_MAX_DIM);
+    if (k == 0 || k > F2V_NEAREST_MAX_K) return fail(F2V_EINVAL, "f2v_trustworthiness: k = %u is outside 1..%d", k, F2V_NEAREST_MAX_K);
+    if (2 * (uint64_t)k >= c->n) return fail(F2V_EINVAL, "f2v_trustworthiness: k = %u must be below n / 2 = %u / 2", k, c->n);
+    if (sample_ids && nq == 0) return fail(F2V_EINVAL, "f2v_trustworthiness: nq = 0 samples");
+    const uint32_t n = c->n, D = c->D;
+    if (!sample_ids) nq = n;
+    std::vector<uint32_t> sid(nq);
+    for (uint32_t i = 0; i < nq; i++) {
+        sid[i] = sample_ids ? sample_ids[i] : i;
+        if (sid[i] >= n) return fail(F2V_EINVAL, "f2v_trustworthiness: sample %u names vertex %u of %u", i, sid[i], n);
+    }
+    int rc = lay_enter(c, "f2v_trustworthiness");
+    if (rc != F2V_OK) return rc;
+    f2v_ctx::Layout &w = c->lay;
+    const uint32_t chunk = std::min(w.chunk, nq), rb = w.block == 128 && k <= 32 ? 128u : 64u;
+    if ((rc = sep_grow(c, w.d_Y, w.cap_Y, (size_t)n * d2)) != F2V_OK || (rc = sep_grow(c, w.d_sid, w.cap_sid, nq)) != F2V_OK ||
+        (rc = sep_grow(c, w.d_nx, w.cap_nx, (size_t)chunk * k)) != F2V_OK || (rc = sep_grow(c, w.d_ny, w.cap_ny, (size_t)chunk * k)) != F2V_OK ||
+        (rc = sep_grow(c, w.d_thr, w.cap_thr, (size_t)chunk * k)) != F2V_OK || (rc = sep_grow(c, w.d_hist, w.cap_hist, (size_t)chunk * k)) != F2V_OK ||
+        (rc = sep_grow(c, w.d_pen, w.cap_pen, 2 * (size_t)nq)) != F2V_OK || (rc = sep_grow(c, w.d_sums, w.cap_sums, 3)) != F2V_OK)
+        return rc;
+    HIPC(hipMemcpyAsync(w.d_Y, Y, (size_t)n * d2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(w.d_sid, sid.data(), (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemsetAsync(w.d_sums, 0, 3 * sizeof(unsigned long long), c->stream));
+    const float *X = c->d_X[c->cur];
+    double seconds = 0.0;
+    for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
+        const uint32_t cq = std::min(chunk, nq - q0), blocks = (cq + rb - 1) / rb;
+        // the k nearest in both spaces, by the nearest-neighbour kernels as they are
+        double sec = 0.0;
+        if ((rc = nearest_run_on(c, X, D, sid.data() + q0, false, nullptr, cq, k, F2V_SIM_L2, F2V_NEAREST_EXCLUDE_SELF, nullptr, nullptr, nullptr, &sec, w.d_nx)) != F2V_OK) return rc;
+        seconds += sec;
+        if ((rc = nearest_run_on(c, w.d_Y, d2, sid.data() + q0, false, nullptr, cq, k, F2V_SIM_L2, F2V_NEAREST_EXCLUDE_SELF, nullptr, nullptr, nullptr, &sec, w.d_ny)) != F2V_OK) return rc;
+        seconds += sec;
+        // candidates per workgroup: enough workgroups for every CU a few times over (placement only: the counts add up exactly)
+        const uint32_t want = std::max(1u, 2048u / blocks);
+        uint32_t span = ((n + want - 1) / want + 63u) / 64u * 64u;
+        span = std::min(std::max(span, 256u), kTrustMaxSpan);
+        const uint32_t spans = (n + span - 1) / span;
+        if ((uint64_t)spans * blocks > 0x7FFFFFFFull) return fail(F2V_EINVAL, "f2v_trustworthiness: too many workgroups per launch: lower \"trust_chunk\"");
+        HIPC(hipEventRecord(w.ev[0], c->stream));
+        for (int dir = 0; dir < 2; dir++) {  // 0: the layout's neighbours ranked in X (trustworthiness), 1: X's neighbours ranked in Y (continuity)
+            TrustKeyArgs ka{};
+            ka.M = dir ? w.d_Y : X;
+            ka.sid = w.d_sid + q0;
+            ka.tgt = dir ? w.d_nx : w.d_ny;
+            ka.own = dir ? w.d_ny : w.d_nx;
+            ka.thr = w.d_thr;
+            ka.hits = dir ? nullptr : w.d_sums + 2;
+            ka.n = n;
+            ka.D = dir ? d2 : D;
+            ka.k = k;
+            hipLaunchKernelGGL(trust_keys_kernel, dim3(cq), dim3(128), 0, c->stream, ka);
+            HIPC(hipGetLastError());
+            HIPC(hipMemsetAsync(w.d_hist, 0, (size_t)cq * k * sizeof(uint32_t), c->stream));
+            TrustRankArgs ra{};
+            ra.M = ka.M;
+            ra.sid = ka.sid;
+            ra.thr = w.d_thr;
+            ra.hist = w.d_hist;
+            ra.n = n;
+            ra.D = ka.D;
+            ra.nq = cq;
+            ra.k = k;
+            ra.span = span;
+            if ((rc = rb == 128 ? launch_rank_t<128>(c, ra, spans) : launch_rank_t<64>(c, ra, spans)) != F2V_OK) return rc;
+            hipLaunchKernelGGL(trust_finish_kernel, dim3((cq + 255) / 256), dim3(256), 0, c->stream, (const nn_key_t *)w.d_thr, (const uint32_t *)w.d_hist, cq, k,
+                               w.d_pen + (size_t)dir * nq + q0, w.d_sums + dir);
+            HIPC(hipGetLastError());
+        }
+        HIPC(hipEventRecord(w.ev[1], c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+        float ms = 0.f;
+        HIPC(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
+        seconds += ms * 1e-3;
+    }
+    uint64_t sums[3] = {0, 0, 0};
+    HIPC(hipMemcpyAsync(sums, w.d_sums, sizeof sums, hipMemcpyDeviceToHost, c->stream));
+    if (penalty_x_out) HIPC(hipMemcpyAsync(penalty_x_out, w.d_pen, (size_t)nq * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (penalty_y_out) HIPC(hipMemcpyAsync(penalty_y_out, w.d_pen + nq, (size_t)nq * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    if ((rc = check_kernel_err(c, "f2v_trustworthiness")) != F2V_OK) return rc;
+    const double scale = 2.0 / ((double)nq * k * (2.0 * n - 3.0 * k - 1.0));
+    out->trustworthiness = 1.0 - (double)sums[0] * scale;
+    out->continuity = 1.0 - (double)sums[1] * scale;
+    out->overlap = (double)sums[2] / ((double)nq * k);
+    out->seconds = seconds;
+    out->penalty_x = sums[0];
+    out->penalty_y = sums[1];
+    out->hits = sums[2];
+    return F2V_OK;
+}
+
+#ifdef F2V_TEST_HOOKS
+int f2v_test_pca_scatter(f2v_handle c, double *mean_out, double *scatter_out) {
+    if (!c || !mean_out || !scatter_out) return fail(F2V_EINVAL, "f2v_test_pca_scatter: null argument");
+    int rc = lay_enter(c, "f2v_test_pca_scatter");
+    if (rc != F2V_OK) return rc;
+    std::vector<double> mean, S;
+    double seconds = 0.0;
+    if ((rc = pca_moments_host(c, mean, S, &seconds)) != F2V_OK) return rc;
+    memcpy(mean_out, mean.data(), mean.size() * sizeof(double));
+    memcpy(scatter_out, S.data(), S.size() * sizeof(double));
+    return F2V_OK;
+}
+#endif
 
 int f2v_logreg_eval(f2v_handle c, const uint32_t *a_ids, const uint32_t *b_ids, uint32_t m, int feature, const uint8_t *y, uint32_t classes,
                     const double *weights, double lambda, double *loss_out, double *grad_out, double *seconds_out) {

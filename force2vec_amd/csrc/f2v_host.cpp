@@ -157,6 +157,50 @@ void sm_table_host(float *t) {
 // the block boundary drained) lost ~38 % of their work, this loses ~12 %.  Same samples, same stream position afterwards (draws taken
 // ahead are given back, Rand::back), whatever the graph; where more than one walk in three is mispredicted (cora: half the steps draw
 // nothing, and the graph sits in the cache) the reference's own serial loop runs, 64 walks at a time.
+void pca_jacobi_host(double *A, double *V, uint32_t D, uint32_t *sweeps, uint32_t *converged) {
+    for (uint32_t i = 0; i < D; i++)
+        for (uint32_t j = 0; j < D; j++) V[(size_t)i * D + j] = i == j ? 1.0 : 0.0;
+    *sweeps = 0;
+    *converged = 0;
+    for (uint32_t sweep = 0; sweep < 64; sweep++) {
+        bool rotated = false;
+        for (uint32_t p = 0; p + 1 < D; p++)
+            for (uint32_t q = p + 1; q < D; q++) {
+                double *rp = A + (size_t)p * D, *rq = A + (size_t)q * D;
+                const double apq = rp[q], app = rp[p], aqq = rq[q];
+                if (apq == 0.0) continue;
+                const double g = std::fabs(apq);
+                if (std::fabs(app) + g == std::fabs(app) && std::fabs(aqq) + g == std::fabs(aqq)) {
+                    rp[q] = rq[p] = 0.0;
+                    continue;
+                }
+                const double theta = (aqq - app) / (2.0 * apq);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+                for (uint32_t j = 0; j < D; j++) {  // rows p and q
+                    const double x = rp[j], y = rq[j];
+                    rp[j] = c * x - s * y;
+                    rq[j] = s * x + c * y;
+                }
+                for (uint32_t i = 0; i < D; i++) {  // columns p and q, of A and of V
+                    double *r = A + (size_t)i * D, *v = V + (size_t)i * D;
+                    const double x = r[p], y = r[q], vx = v[p], vy = v[q];
+                    r[p] = c * x - s * y;
+                    r[q] = s * x + c * y;
+                    v[p] = c * vx - s * vy;
+                    v[q] = s * vx + c * vy;
+                }
+                rp[q] = rq[p] = 0.0;
+                rotated = true;
+            }
+        *sweeps = sweep + 1;
+        if (!rotated) {
+            *converged = 1;
+            return;
+        }
+    }
+}
+
 void walks_host(Rand &g, const uint32_t *rp, const uint32_t *ci, uint32_t n, uint64_t nnz, uint32_t *walks) {
     constexpr uint32_t L = (uint32_t)kWalkLength, SMAX = 64, RING = 1024, MASK = RING - 1;
     static_assert(RING >= 2 * SMAX * L && (RING & MASK) == 0, "the ring holds every draw a walk in flight may ask for");

@@ -43,6 +43,10 @@ void init_embeddings_host(Rand &g, float *x, size_t total, int kind);
 void sm_table_host(float *t);
 // One epoch's option-7 walk samples [5*n] drawn from `g` exactly as the reference's serial loop draws them (f2v_host.cpp)
 void walks_host(Rand &g, const uint32_t *rowptr, const uint32_t *colids, uint32_t n, uint64_t nnz, uint32_t *walks);
+// The cyclic Jacobi method of include/f2v.h ("layout") on the symmetric D x D matrix A (row-major; overwritten, the eigenvalues end on
+// its diagonal); V receives the eigenvectors as columns.  Plain fp64, one rounding per operation (f2v_host.cpp is built without
+// contraction).  *sweeps: sweeps run, the last one without a rotation included; *converged: 0 after 64 sweeps that all rotated.
+void pca_jacobi_host(double *A, double *V, uint32_t D, uint32_t *sweeps, uint32_t *converged);
 
 }  // namespace f2v
 #endif

@@ -25,6 +25,12 @@ KMeans = namedtuple("KMeans", "labels centroids inertia iterations converged res
 Modularity = namedtuple("Modularity", "q edges inside degree")
 
 
+# Engine.pca / Engine.trustworthiness (include/f2v.h: layout)
+Pca = namedtuple("Pca", "y components mean variance info")
+PcaInfo = namedtuple("PcaInfo", "total_variance seconds sweeps converged")
+Trust = namedtuple("Trust", "trustworthiness continuity overlap penalty_x penalty_y hits seconds samples_x samples_y")
+
+
 # Engine.logreg_fit / Engine.classify / Engine.link_predict (include/f2v.h: logistic regression)
 LogregModel = namedtuple("LogregModel", "weights feature loss gnorm_inf iterations evaluations converged seconds")
 F1 = namedtuple("F1", "micro macro")
@@ -71,6 +77,7 @@ class Engine:
         self._h = h
         self.last_nearest_seconds = self.last_kmeans_seconds = self.last_logreg_seconds = 0.0  # device time of the last query / clustering / regression call
         self.last_separation_seconds = 0.0  # ... / silhouette or Davies-Bouldin call
+        self.last_layout_seconds = 0.0  # ... / pca or trustworthiness call
 
     def _ck(self, rc):
         check(rc, self._L)  # the error text lives in the library that returned the code
@@ -359,6 +366,37 @@ class Engine:
                                             counts.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(sec)))
         self.last_separation_seconds = sec.value
         return (score.value, centroids, scatter, counts) if details else score.value
+
+    # -- layout (include/f2v.h: definition; functions of the matrix, d / the second matrix, k and the samples alone) ------------------
+    def pca(self, d=2, details=False):
+        """The projection of the matrix onto its first `d` principal components, on the GPU (the D x D eigenproblem on the host)
+        -> Y float32 [n, d], or with details=True Pca(y, components float64 [d, dim], mean float64 [dim], variance float64 [d],
+        info = PcaInfo(total_variance, seconds, sweeps, converged)).  `last_layout_seconds` keeps the device time."""
+        y = np.empty((self.n, d), dtype=np.float32)
+        comp, mean, var = np.empty((d, self.dim), dtype=np.float64), np.empty(self.dim, dtype=np.float64), np.empty(d, dtype=np.float64)
+        info = _lib.PcaInfo()
+        f64 = lambda a: a.ctypes.data_as(_lib.f64p)  # noqa: E731
+        self._ck(self._L.f2v_pca(self._h, d, _f32(y), f64(comp), f64(mean), f64(var), C.byref(info)))
+        self.last_layout_seconds = info.seconds
+        return Pca(y, comp, mean, var, PcaInfo(info.total_variance, info.seconds, info.sweeps, bool(info.converged))) if details else y
+
+    def trustworthiness(self, Y, k=5, ids=None, samples=False):
+        """How well the neighbourhoods of the matrix survive in `Y` (float32 [n, d2], any layout of the same vertices), on the GPU ->
+        Trust(trustworthiness, continuity, overlap, penalty_x, penalty_y, hits, seconds, samples_x, samples_y): scikit-learn's
+        trustworthiness(X, Y, n_neighbors=k), the same with the roles swapped, and the mean share of common k nearest neighbours,
+        over the samples `ids` (None: every vertex), each ranked against all vertices.  samples=True: samples_x / samples_y hold every
+        sample's penalties (uint64 [len(ids)]), else None."""
+        Y = np.ascontiguousarray(Y, dtype=np.float32)
+        if Y.ndim != 2 or Y.shape[0] != self.n:
+            raise ValueError("trustworthiness: Y must be [%d, d2]" % self.n)
+        q = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        nq = self.n if q is None else len(q)
+        px, py = (np.empty(nq, dtype=np.uint64), np.empty(nq, dtype=np.uint64)) if samples else (None, None)
+        u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64)) if a is not None else None  # noqa: E731
+        out = _lib.TrustInfo()
+        self._ck(self._L.f2v_trustworthiness(self._h, _f32(Y), Y.shape[1], k, _u32(q) if q is not None else None, nq, u64(px), u64(py), C.byref(out)))
+        self.last_layout_seconds = out.seconds
+        return Trust(out.trustworthiness, out.continuity, out.overlap, out.penalty_x, out.penalty_y, out.hits, out.seconds, px, py)
 
     # -- logistic regression (include/f2v.h: definition; a function of the matrix, the samples, the targets and the weights alone) --
     def _samples(self, ids, pairs, feature):

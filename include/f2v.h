@@ -8,8 +8,9 @@
  * it replaces (file:line under the reference tree).  Plain pointers and sizes only.
  * Beside training, what the reference judges an embedding by is evaluated on the matrix where it lies, in HBM: the training
  * objective (f2v_objective), nearest rows (f2v_nearest_*), k-means and modularity (f2v_kmeans, f2v_modularity), the
- * logistic-regression scorers of node labels and links (f2v_logreg_*) and the separation of a labelling in the embedding space
- * (f2v_silhouette, f2v_davies_bouldin).  Each has a definition below that fixes every order of summation, so that its results are
+ * logistic-regression scorers of node labels and links (f2v_logreg_*), the separation of a labelling in the embedding space
+ * (f2v_silhouette, f2v_davies_bouldin) and a two-dimensional picture of the matrix with the score of how faithful it is (f2v_pca,
+ * f2v_trustworthiness).  Each has a definition below that fixes every order of summation, so that its results are
  * functions of its inputs alone.
  *
  * Conventions: every function returns 0 on success and a negative F2V_E* code on failure
@@ -521,6 +522,74 @@ F2V_API int f2v_silhouette(f2v_handle h, const uint32_t *labels /* n */, uint32_
 F2V_API int f2v_davies_bouldin(f2v_handle h, const uint32_t *labels, uint32_t n_clusters, double *score_out,
                        float *centroids_out /* n_clusters x D, may be NULL */, double *scatter_out /* n_clusters, may be NULL */,
                        uint64_t *counts_out /* n_clusters, may be NULL */, double *seconds_out /* may be NULL */);
+
+/* ---- layout ----------------------------------------------------------------------------------------------------------------------
+ * The step that gives performancescores/runvisualization.py its name (:177-181, :190-198): reduce the embedding to two dimensions, say
+ * how faithful the picture is ("TrustWorthiness: <x>"), write the coordinates out.  The script's t-SNE is O(n^2) per iteration and
+ * chaotic; the deterministic answer is a principal-component projection, and the score is scikit-learn's trustworthiness itself, between
+ * the matrix and ANY second matrix over the same vertices.
+ *
+ * f2v_pca -- all fp64; fma(a, b, acc) is one correctly rounded fp64 fused multiply-add:
+ *   mean        the vertices in ascending id are cut into pieces of F2V_PCA_PIECE consecutive vertices; a piece is summed per dimension
+ *               sequentially from +0 (the floats converted exactly), the piece sums are added sequentially from +0 in ascending piece
+ *               order, mean_d = sum_d / (double)n;
+ *   scatter     S_de for d <= e from z_vd = (double)x_vd - mean_d (one rounded subtraction): within a piece the chain fma(z_vd, z_ve,
+ *               acc) from +0 in ascending vertex id, the piece sums added sequentially from +0 in ascending piece order; S_ed = S_de;
+ *   eigenvectors   the cyclic Jacobi method on S, every product and sum one rounded fp64 operation, no fma: A = S, V = I; a sweep visits
+ *               (p, q) for p = 0 .. D-2, q = p+1 .. D-1; a_pq == 0: the pair is skipped; |a_pp| + |a_pq| == |a_pp| and |a_qq| + |a_pq|
+ *               == |a_qq|: a_pq = a_qp = 0 and the pair is skipped; else theta = (a_qq - a_pp) / (2 a_pq), t = sgn(theta) / (|theta| +
+ *               sqrt(theta * theta + 1)) with sgn(theta) = +1 where theta >= 0 and -1 otherwise, c = 1 / sqrt(t * t + 1), s = t * c; rows
+ *               p and q of A become c a_p. - s a_q. and s a_p. + c a_q. (from the old rows), then columns p and q are updated the same
+ *               way, a_pq = a_qp = 0, and columns p and q of V are updated the same way: a rotation.  The method stops after the first
+ *               sweep without a rotation (converged = 1) and in any case after 64 sweeps (converged = 0); sweeps counts the sweeps run,
+ *               the one without a rotation included;
+ *   order, sign eigenpairs by eigenvalue (the diagonal of A) descending, ties by ascending original column, a NaN after every number; a
+ *               component is negated where its entry of largest magnitude is negative (the lowest d among equal magnitudes);
+ *   projection  y_vc = (float) of the chain fma(z_vd, w_cd, acc) from +0 over ascending d, c < d2, z_vd the difference above;
+ *   outputs     y_out n x d2 floats, components_out d2 x D, mean_out D, variance_out[c] = lambda_c / (double)(n - 1); every one may be
+ *               NULL; info->total_variance = (the sequential sum from +0 of S's diagonal in ascending d) / (double)(n - 1).
+ * The result is a function of the matrix and d2 alone: never of launch shapes, of a tunable, of the handle or of the order in which
+ * workgroups run; no float atomics; bitwise identical between calls and handles.  Like every evaluation call it works on the matrix as
+ * f2v_get_embeddings would return it (pending minibatches are committed first), runs on the handle's stream and changes neither the
+ * matrices nor the rand() stream nor any later training result; on a handle attached to a push exchange it reads this rank's replica.
+ * Workspace, allocated on first use (grown on demand) and freed by f2v_destroy: ceil(n / 4096) x D (D + 1) / 2 doubles of piece chains
+ * (the largest: 269 MB at n = 1 Mi, D = 512), D (D + 1) / 2 + D + d2 x D doubles and n x d2 floats.  The eigenproblem is the host's, O(D^3) per
+ * sweep and not part of `seconds`.  seconds: device time between events around the call's own launches.
+ * F2V_ESTATE without valid embeddings; F2V_EINVAL for a null info, d2 = 0, d2 > D, n < 2. */
+#define F2V_PCA_PIECE 4096
+typedef struct {
+    double total_variance, seconds;
+    uint32_t sweeps, converged;
+} f2v_pca_t;
+F2V_API int f2v_pca(f2v_handle h, uint32_t d2, float *y_out /* n x d2, may be NULL */, double *components_out /* d2 x D, may be NULL */,
+            double *mean_out /* D, may be NULL */, double *variance_out /* d2, may be NULL */, f2v_pca_t *info);
+/* f2v_trustworthiness -- neighbourhood preservation between the handle's matrix X and a second matrix Y (n x d2 on the host: the PCA
+ * layout, a -dim 2 run, a t-SNE made elsewhere, yesterday's checkpoint).  For a matrix M and a vertex i, the order of M around i is the
+ * result order of f2v_nearest_rows with F2V_SIM_L2 and F2V_NEAREST_EXCLUDE_SELF (the fp32 fma chain of squared differences, ascending
+ * distance, -0 = +0, equal distances by ascending vertex id, a NaN after every number); r_M(i, j) is the 1-based place of j in it,
+ * N_M(i, k) its first k vertices.  Then
+ *   penalty_x(i) = sum over j in N_Y(i, k) of max(0, r_X(i, j) - k)    the neighbours the picture invents,
+ *   penalty_y(i) = sum over j in N_X(i, k) of max(0, r_Y(i, j) - k)    the neighbours it loses,
+ *   overlap(i)   = |N_X(i, k) n N_Y(i, k)|,
+ * integers all three, their sums over the samples exact (penalty_x, penalty_y, hits: integer atomics, as in f2v_modularity), and the host
+ * forms trustworthiness = 1.0 - (double)penalty_x * (2.0 / ((double)nq * k * (2.0 * n - 3.0 * k - 1.0))), continuity the same from
+ * penalty_y, overlap = (double)hits / ((double)nq * k).  With every vertex a sample (sample_ids NULL) that is scikit-learn's
+ * trustworthiness(X, Y, n_neighbors = k) term for term, and continuity is trustworthiness(Y, X).  A sample subset is ranked against ALL
+ * n vertices; duplicate sample ids are legal.  Results are a function of (X, Y, k, samples) alone: never of "trust_chunk" (samples per
+ * launch, default 8192), "trust_block" (sample rows per workgroup, 0 = 64 | 64 | 128; 128 holds where k <= 32), the "nearest_*" tunables,
+ * the handle or the order in which workgroups run.  Evaluation rules as for f2v_pca.  Cost: every sample against all n rows in D and in
+ * d2 dimensions, O(nq n D).  Workspace, allocated on first use and freed by f2v_destroy: Y (n x d2 floats), the nearest-neighbour
+ * workspace, per sample of a chunk 2 k words of neighbour ids, k keys and k counts, per sample 5 words.
+ * F2V_ESTATE without valid embeddings; F2V_EINVAL for a null Y or out, d2 = 0 or d2 > F2V_TRUST_MAX_DIM, k = 0, k > F2V_NEAREST_MAX_K or
+ * 2 k >= n (scikit-learn's condition), a sample id >= n, nq = 0 together with sample_ids. */
+#define F2V_TRUST_MAX_DIM 512
+typedef struct {
+    double trustworthiness, continuity, overlap, seconds;
+    uint64_t penalty_x, penalty_y, hits;
+} f2v_trust_t;
+F2V_API int f2v_trustworthiness(f2v_handle h, const float *Y /* n x d2 */, uint32_t d2, uint32_t k, const uint32_t *sample_ids /* NULL: every vertex */,
+                        uint32_t nq, uint64_t *penalty_x_out /* per sample, may be NULL */, uint64_t *penalty_y_out /* per sample, may be NULL */,
+                        f2v_trust_t *out);
 
 /* ---- host-side I/O of the drop-in boundary (no device needed) ----------------------------
  * f2v_read_mtx replaces SetInputMatricesAsCSR (sample/commonutility.h:44-54 -> ReadASCII

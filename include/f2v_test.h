@@ -67,6 +67,10 @@ F2V_API int f2v_test_plan_gather(f2v_handle h, uint32_t row_lo, uint32_t row_hi,
  * staged in LDS; 0: off.  tools/interaction_stub_probe.py. */
 F2V_API int f2v_test_interaction_stub(f2v_handle h, uint32_t mode);
 
+/* The first two steps of f2v_pca alone: the mean (D doubles) and the full symmetric scatter matrix (D x D doubles) of the settled matrix,
+ * where the host's eigen-solver would make a comparison at D = 512 slow.  tests/test_layout.py. */
+F2V_API int f2v_test_pca_scatter(f2v_handle h, double *mean_out, double *scatter_out);
+
 #ifdef __cplusplus
 }
 #endif
