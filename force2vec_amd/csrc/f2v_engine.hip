@@ -113,6 +113,66 @@ static_assert(sizeof(PushExport) == F2V_PUSH_EXPORT_BYTES, "export blob layout")
 static_assert(kMaxRanks == F2V_PUSH_MAX_RANKS, "rank limit");
 constexpr uint32_t kPushMagic = 0x46325650u;  // "F2VP"
 
+// ---- what the scorers' host code shares: a grown-on-demand device buffer, a pair of timing events, and (further
+// down) settled_enter and allow_lds.  A new scorer uses these, it does not bring its own.
+#define F2VC(expr)                        \
+    do {                                  \
+        int rc__ = (expr);                \
+        if (rc__ != F2V_OK) return rc__;  \
+    } while (0)
+
+// A device array and the elements it holds: allocated on first use, grown (never shrunk, never rounded up) for a larger call, freed
+// with the handle (f2v_destroy has made the handle's device current by then)
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    operator T *() const { return p; }
+    // Room for `count` elements.  Growing waits for the handle's stream first (launches may still read the old array) and leaves the
+    // buffer empty where the allocation fails: "<what> workspace: <hip error>".
+    int reserve(f2v_ctx *c, size_t count, const char *what);
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+
+// Device time between two points of a stream: start, stop, and -- once the stream has been synchronised -- seconds
+struct DevTimer {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    DevTimer() = default;
+    DevTimer(const DevTimer &) = delete;
+    DevTimer &operator=(const DevTimer &) = delete;
+    ~DevTimer() { release(); }
+    int start(hipStream_t stream) {
+        for (hipEvent_t &e : ev)
+            if (!e) HIPC(hipEventCreate(&e));
+        HIPC(hipEventRecord(ev[0], stream));
+        return F2V_OK;
+    }
+    int stop(hipStream_t stream) {
+        HIPC(hipEventRecord(ev[1], stream));
+        return F2V_OK;
+    }
+    int seconds(double *sum) {  // *sum += the seconds from start to stop
+        float ms = 0.f;
+        HIPC(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        *sum += ms * 1e-3;
+        return F2V_OK;
+    }
+    void release() {
+        for (hipEvent_t &e : ev) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+    }
+};
+
 struct f2v_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -157,61 +217,48 @@ struct f2v_ctx {
     // nearest-neighbour queries (f2v_nearest_rows / _vectors, f2v_neighbour_recall): buffers of one query chunk, allocated on first
     // use and grown on demand; "nearest_splits" (0 = from nq and N), "nearest_block" (0 = from D and nq | 32 | 128), "nearest_chunk"
     struct Nearest {
-        float *d_Q = nullptr, *d_rq = nullptr, *d_rc = nullptr, *d_scores = nullptr;
-        uint32_t *d_qids = nullptr, *d_ids = nullptr;
-        unsigned long long *d_ws = nullptr, *d_counts = nullptr;
-        size_t q_cap = 0, qf_cap = 0, ws_cap = 0, out_cap = 0;  // queries d_rq / d_qids hold, floats d_Q holds, keys d_ws holds, slots d_ids / d_scores hold
-        hipEvent_t ev[2] = {nullptr, nullptr};
+        DevBuf<float> d_Q, d_rq, d_rc, d_scores;
+        DevBuf<uint32_t> d_qids, d_ids;
+        DevBuf<unsigned long long> d_ws, d_counts;
+        DevTimer timer;
         uint32_t splits = 0, block = 0, chunk = 8192;
-        size_t lds_set[4] = {0, 0, 0, 0};  // per nearest_kernel instantiation: the dynamic-LDS limit it has been raised to (launch_nearest_t)
     } nn;
     int rows_sorted = -1;  // the CSR's ids ascend inside every row (rows are searched by the nearest queries and f2v_modularity): -1 not checked yet (rows_ascending)
     // clustering (f2v_kmeans, f2v_modularity): the workspace f2v.h states, allocated on first use for the call's k and grown for a
     // larger one; "kmeans_block" (0 = from k | 64 | 128 | 256): rows per workgroup of kmeans_assign_kernel
     struct Kmeans {
-        float *d_C = nullptr, *d_bestC = nullptr, *d_dist = nullptr;
-        uint32_t *d_labels = nullptr, *d_bestL = nullptr, *d_order = nullptr, *d_hist = nullptr, *d_counts = nullptr, *d_start = nullptr,
-                 *d_pstart = nullptr, *d_changed = nullptr, *d_seed = nullptr, *d_mlabels = nullptr;
-        double *d_psum = nullptr, *d_ipart = nullptr, *d_inertia = nullptr;
-        unsigned long long *d_tallies = nullptr;
-        uint32_t cap_k = 0, cap_nc = 0;  // the k the buffers hold, the communities d_tallies holds
-        hipEvent_t ev[2] = {nullptr, nullptr};
+        DevBuf<float> d_C, d_bestC, d_dist;
+        DevBuf<uint32_t> d_labels, d_bestL, d_order, d_hist, d_counts, d_start, d_pstart, d_changed, d_seed, d_mlabels;
+        DevBuf<double> d_psum, d_ipart, d_inertia;
+        DevBuf<unsigned long long> d_tallies;
+        DevTimer timer;
         uint32_t block = 0;
-        uint32_t lds_allowed = 0;  // kmeans_assign_kernel instantiations whose dynamic-LDS limit has been raised
     } km;
     // logistic regression (f2v_logreg_*): the workspace f2v.h states, allocated on first use and grown for a larger call
     struct Logreg {
-        uint32_t *d_a = nullptr, *d_b = nullptr, *d_cmap = nullptr;
-        uint8_t *d_y = nullptr;
-        double *d_W = nullptr, *d_sums = nullptr, *d_part = nullptr, *d_z = nullptr;
-        size_t cap_m = 0, cap_y = 0, cap_part = 0, cap_z = 0;
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        uint32_t lds_allowed = 0;  // logreg_kernel instantiations whose dynamic-LDS limit has been raised
+        DevBuf<uint32_t> d_a, d_b, d_cmap;
+        DevBuf<uint8_t> d_y;
+        DevBuf<double> d_W, d_sums, d_part, d_z;
+        DevTimer timer;
     } lr;
     // separation (f2v_silhouette, f2v_davies_bouldin): beside the clustering workspace (the counting sort, the centroids, the piece
     // sums) the buffers f2v.h states, allocated on first use and grown for a larger call; "separation_chunk": samples per launch,
     // "separation_block" (0 = 64 | 64 | 128): sample rows per workgroup of separation_pair_kernel
     struct Separation {
-        uint32_t *d_ids = nullptr, *d_sid = nullptr, *d_slab = nullptr, *d_other = nullptr, *d_span_start = nullptr, *d_span_cnt = nullptr,
-                 *d_cspan = nullptr;
-        double *d_ws = nullptr, *d_s = nullptr, *d_part = nullptr, *d_S = nullptr, *d_sum = nullptr;
-        size_t cap_ids = 0, cap_sid = 0, cap_slab = 0, cap_other = 0, cap_span_start = 0, cap_span_cnt = 0, cap_cspan = 0, cap_ws = 0, cap_s = 0,
-               cap_part = 0, cap_S = 0, cap_sum = 0;
-        hipEvent_t ev[2] = {nullptr, nullptr};
+        DevBuf<uint32_t> d_ids, d_sid, d_slab, d_other, d_span_start, d_span_cnt, d_cspan;
+        DevBuf<double> d_ws, d_s, d_part, d_S, d_sum;
+        DevTimer timer;
         uint32_t chunk = 8192, block = 0;
     } sep;
     // layout (f2v_pca, f2v_trustworthiness): the buffers f2v.h states, allocated on first use and grown for a larger call;
     // "trust_chunk": samples per launch, "trust_block" (0 = 64 | 64 | 128): sample rows per workgroup of trust_rank_kernel
     struct Layout {
-        double *d_ws = nullptr, *d_mean = nullptr, *d_S = nullptr, *d_W = nullptr;
-        float *d_P = nullptr, *d_Y = nullptr;  // the projection, the caller's second matrix
-        uint32_t *d_sid = nullptr, *d_nx = nullptr, *d_ny = nullptr, *d_hist = nullptr;
-        unsigned long long *d_thr = nullptr, *d_pen = nullptr, *d_sums = nullptr;
-        size_t cap_ws = 0, cap_mean = 0, cap_S = 0, cap_W = 0, cap_P = 0, cap_Y = 0, cap_sid = 0, cap_nx = 0, cap_ny = 0, cap_hist = 0, cap_thr = 0,
-               cap_pen = 0, cap_sums = 0;
-        hipEvent_t ev[2] = {nullptr, nullptr};
+        DevBuf<double> d_ws, d_mean, d_S, d_W;
+        DevBuf<float> d_P, d_Y;  // the projection, the caller's second matrix
+        DevBuf<uint32_t> d_sid, d_nx, d_ny, d_hist;
+        DevBuf<unsigned long long> d_thr, d_pen, d_sums;
+        DevTimer timer;
         uint32_t chunk = 8192, block = 0;
-        size_t lds_set[2] = {0, 0};  // per trust_rank_kernel instantiation: the dynamic-LDS limit it has been raised to
     } lay;
     uint32_t last_wide_width = 0;  // the layout width of the last wide-form f2v_train ("last_wide_width")
     bool last_wide_early = false;  // ... and whether it ran the kernel's EARLY form ("last_wide_early")
@@ -329,6 +376,20 @@ struct f2v_ctx {
         uint32_t round = 0;        // exchanges done: (round & 1) is the half in use
     } push;
 };
+
+template <class T>
+int DevBuf<T>::reserve(f2v_ctx *c, size_t count, const char *what) {
+    if (p && cap >= count) return F2V_OK;
+    HIPC(hipStreamSynchronize(c->stream));
+    release();
+    hipError_t e = hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T));
+    if (e != hipSuccess) {
+        p = nullptr;
+        return fail(e == hipErrorOutOfMemory ? F2V_ENOMEM : F2V_ENODEV, "%s workspace: %s", what, hipGetErrorString(e));
+    }
+    cap = count;
+    return F2V_OK;
+}
 
 namespace {
 
@@ -1398,6 +1459,31 @@ int flush_pending(f2v_ctx *c) {
     return F2V_OK;
 }
 
+// What every call that reads the settled matrix begins with: the embeddings exist, the handle's device is current, the minibatches
+// stepped so far are folded in.  (Each call's own range checks stand before or after it, in the order its errors are documented.)
+int settled_enter(f2v_ctx *c, const char *who) {
+    if (!c->have_x)
+        return fail(F2V_ESTATE, c->x_invalid ? "%s: the embeddings are invalid since a launch gave up a bounded wait: set or initialise them again"
+                                             : "%s: embeddings were never initialised", who);
+    HIPC(hipSetDevice(c->device));
+    return flush_pending(c);
+}
+
+// More than 64 KiB of dynamic LDS has to be allowed per kernel.  The limit belongs to the kernel on its device, not to a handle, and so
+// does the record of what it has been raised to: one entry per kernel instantiation, raised when a launch needs more than any launch
+// before it and never lowered, whichever handle asks.
+int allow_lds(f2v_ctx *c, const void *kernel, size_t bytes) {
+    static std::mutex mutex;
+    static std::map<std::pair<int, const void *>, size_t> granted;
+    if (bytes <= 64 * 1024) return F2V_OK;
+    std::lock_guard<std::mutex> lock(mutex);
+    size_t &limit = granted[{c->device, kernel}];
+    if (bytes <= limit) return F2V_OK;
+    HIPC(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    limit = bytes;
+    return F2V_OK;
+}
+
 // ---- the training objective (f2v_objective, "loss_every") ---------------------------------------------------------------------
 int math_of_option(int option);
 
@@ -2274,15 +2360,7 @@ int f2v_destroy(f2v_handle c) {
     (void)hipSetDevice(c->device);
     (void)push_detach(c);
     void *ptrs[] = {c->d_rowptr, c->d_colids, c->d_walks, c->d_walks_alt, c->d_ids, c->d_X[0], c->d_X[1],
-                    c->d_partials, c->d_table, c->d_items, c->d_hubs, c->d_ready, c->d_kerr, c->d_wg, c->d_rowflag, c->d_snap, c->d_wide, c->d_jobs, c->d_ring, c->d_ring_partials, c->d_ring_flags, c->d_ring_ready, c->d_obj_items, c->d_obj_part, c->d_obj_out, c->push.flags, c->push.d_err, c->push.d_masks, c->push.d_patch, c->push.landing_buf,
-                    c->nn.d_Q, c->nn.d_rq, c->nn.d_rc, c->nn.d_scores, c->nn.d_qids, c->nn.d_ids, c->nn.d_ws, c->nn.d_counts,
-                    c->km.d_C, c->km.d_bestC, c->km.d_dist, c->km.d_labels, c->km.d_bestL, c->km.d_order, c->km.d_hist, c->km.d_counts, c->km.d_start, c->km.d_pstart,
-                    c->km.d_changed, c->km.d_seed, c->km.d_mlabels, c->km.d_psum, c->km.d_ipart, c->km.d_inertia, c->km.d_tallies,
-                    c->lr.d_a, c->lr.d_b, c->lr.d_cmap, c->lr.d_y, c->lr.d_W, c->lr.d_sums, c->lr.d_part, c->lr.d_z,
-                    c->sep.d_ids, c->sep.d_sid, c->sep.d_slab, c->sep.d_other, c->sep.d_span_start, c->sep.d_span_cnt, c->sep.d_cspan, c->sep.d_ws, c->sep.d_s,
-                    c->sep.d_part, c->sep.d_S, c->sep.d_sum,
-                    c->lay.d_ws, c->lay.d_mean, c->lay.d_S, c->lay.d_W, c->lay.d_P, c->lay.d_Y, c->lay.d_sid, c->lay.d_nx, c->lay.d_ny, c->lay.d_hist, c->lay.d_thr,
-                    c->lay.d_pen, c->lay.d_sums};
+                    c->d_partials, c->d_table, c->d_items, c->d_hubs, c->d_ready, c->d_kerr, c->d_wg, c->d_rowflag, c->d_snap, c->d_wide, c->d_jobs, c->d_ring, c->d_ring_partials, c->d_ring_flags, c->d_ring_ready, c->d_obj_items, c->d_obj_part, c->d_obj_out, c->push.flags, c->push.d_err, c->push.d_masks, c->push.d_patch, c->push.landing_buf};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
 #ifdef F2V_TEST_HOOKS
@@ -2292,18 +2370,9 @@ int f2v_destroy(f2v_handle c) {
     if (c->h_kerr) (void)hipHostFree(c->h_kerr);
     for (hipEvent_t e : c->ev_snap)
         if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->nn.ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->km.ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->lr.ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->sep.ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->lay.ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    const hipStream_t stream = c->stream;
+    delete c;  // the scorers' buffers and timers (DevBuf, DevTimer) go with it: before their stream, as every other buffer and event
+    if (stream) (void)hipStreamDestroy(stream);
     return F2V_OK;
 }
 
@@ -2396,11 +2465,10 @@ int f2v_set_embeddings(f2v_handle c, const float *x) {
 
 int f2v_get_embeddings(f2v_handle c, float *x_out) {
     if (!c || !x_out) return fail(F2V_EINVAL, "f2v_get_embeddings: null argument");
-    if (!c->have_x)
-        return fail(F2V_ESTATE, c->x_invalid ? "f2v_get_embeddings: the embeddings are invalid since a launch gave up a bounded wait: set or initialise them again"
-                                             : "f2v_get_embeddings: embeddings were never initialised");
-    int rc = quiesce(c);
-    if (rc != F2V_OK || (rc = check_kernel_err(c, "f2v_get_embeddings")) != F2V_OK) return rc;
+    int rc = settled_enter(c, "f2v_get_embeddings");
+    if (rc != F2V_OK) return rc;
+    HIPC(hipStreamSynchronize(c->stream));
+    if ((rc = check_kernel_err(c, "f2v_get_embeddings")) != F2V_OK) return rc;
     HIPC(hipMemcpy(x_out, c->d_X[c->cur], (size_t)c->n * c->D * sizeof(float), hipMemcpyDeviceToHost));
     return F2V_OK;
 }
@@ -2701,11 +2769,7 @@ int f2v_objective(f2v_handle c, int option, uint32_t ns, f2v_objective_t *out) {
     if (!c || !out) return fail(F2V_EINVAL, "f2v_objective: null argument");
     if (!math_of_option(option)) return fail(F2V_EINVAL, "f2v_objective: option %d is outside 5..11", option);
     if (c->n < 2) return fail(F2V_EINVAL, "f2v_objective: the graph needs at least two vertices");
-    if (!c->have_x)
-        return fail(F2V_ESTATE, c->x_invalid ? "f2v_objective: the embeddings are invalid since a launch gave up a bounded wait: set or initialise them again"
-                                             : "f2v_objective: embeddings were never initialised");
-    HIPC(hipSetDevice(c->device));
-    int rc = flush_pending(c);
+    int rc = settled_enter(c, "f2v_objective");
     if (rc != F2V_OK) return rc;
     if ((rc = objective_prepare(c)) != F2V_OK) return rc;
     if ((rc = launch_objective(c, c->d_X[c->cur], option, ns, c->d_obj_out + kLossLogMax)) != F2V_OK) return rc;
@@ -3198,23 +3262,9 @@ int train_impl(f2v_ctx *c, int option, uint32_t iters, uint32_t batch, uint32_t 
 template <bool L2, int WQ, int MI, int NI>
 int launch_nearest_t(f2v_ctx *c, const NnArgs &a, uint32_t qblocks, uint32_t splits) {
     const size_t lds = nn_lds_bytes(32u * WQ * MI, a.D);
-    const uint32_t form = (L2 ? 2 : 0) + (WQ == 2 ? 1 : 0);
-    if (c->nn.lds_set[form] < lds) {  // more than 64 KB of dynamic LDS has to be allowed per kernel: once for the handle's D, and again only for a wider second matrix (f2v_trustworthiness)
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void *>(&nearest_kernel<L2, WQ, MI, NI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        c->nn.lds_set[form] = lds;
-    }
+    F2VC(allow_lds(c, reinterpret_cast<const void *>(&nearest_kernel<L2, WQ, MI, NI>), lds));
     hipLaunchKernelGGL((nearest_kernel<L2, WQ, MI, NI>), dim3(qblocks, splits), dim3(kNnThreads), lds, c->stream, a);
     HIPC(hipGetLastError());
-    return F2V_OK;
-}
-
-template <class T>
-int nn_grow(f2v_ctx *c, T *&p, size_t count) {
-    HIPC(hipStreamSynchronize(c->stream));
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    hipError_t e = hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T));
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? F2V_ENOMEM : F2V_ENODEV, "nearest-neighbour workspace: %s", hipGetErrorString(e));
     return F2V_OK;
 }
 
@@ -3228,12 +3278,10 @@ int nearest_run_on(f2v_ctx *c, const float *X, uint32_t D, const uint32_t *qids,
     f2v_ctx::Nearest &w = c->nn;
     const uint32_t n = c->n;
     const bool rows = qids || all, cosine = metric == F2V_SIM_COSINE;
-    int rc;
-    for (hipEvent_t &e : w.ev)
-        if (!e) HIPC(hipEventCreate(&e));
-    if (!w.d_counts) HIPC(hipMalloc((void **)&w.d_counts, 2 * sizeof(unsigned long long)));
+    const char *what = "nearest-neighbour";
+    F2VC(w.d_counts.reserve(c, 2, what));
     if (recall_out) HIPC(hipMemsetAsync(w.d_counts, 0, 2 * sizeof(unsigned long long), c->stream));
-    if (cosine && !w.d_rc && (rc = nn_grow(c, w.d_rc, n)) != F2V_OK) return rc;
+    if (cosine) F2VC(w.d_rc.reserve(c, n, what));
     const uint32_t tiles = (n + kNnTile - 1) / kNnTile;
     double seconds = 0.0;
     std::vector<uint32_t> iota;
@@ -3247,30 +3295,20 @@ int nearest_run_on(f2v_ctx *c, const float *X, uint32_t D, const uint32_t *qids,
         splits = std::min(splits, tiles);
         const uint32_t tps = (tiles + splits - 1) / splits;
         splits = (tiles + tps - 1) / tps;
-        if (w.q_cap < cq) {
-            if ((rc = nn_grow(c, w.d_rq, cq)) != F2V_OK || (rc = nn_grow(c, w.d_qids, cq)) != F2V_OK) return rc;
-            w.q_cap = cq;
-        }
-        if (w.qf_cap < (size_t)cq * D) {
-            if ((rc = nn_grow(c, w.d_Q, (size_t)cq * D)) != F2V_OK) return rc;
-            w.qf_cap = (size_t)cq * D;
-        }
         const size_t keys = (size_t)qblocks * qb * splits * k, slots = (size_t)cq * k;
-        if (w.ws_cap < keys) {
-            if ((rc = nn_grow(c, w.d_ws, keys)) != F2V_OK) return rc;
-            w.ws_cap = keys;
-        }
-        if (w.out_cap < slots) {
-            if ((rc = nn_grow(c, w.d_ids, slots)) != F2V_OK || (rc = nn_grow(c, w.d_scores, slots)) != F2V_OK) return rc;
-            w.out_cap = slots;
-        }
+        F2VC(w.d_rq.reserve(c, cq, what));
+        F2VC(w.d_qids.reserve(c, cq, what));
+        F2VC(w.d_Q.reserve(c, (size_t)cq * D, what));
+        F2VC(w.d_ws.reserve(c, keys, what));
+        F2VC(w.d_ids.reserve(c, slots, what));
+        F2VC(w.d_scores.reserve(c, slots, what));
         if (all) {
             iota.resize(cq);
             for (uint32_t i = 0; i < cq; i++) iota[i] = done + i;
         }
         if (rows) HIPC(hipMemcpyAsync(w.d_qids, all ? iota.data() : qids + done, (size_t)cq * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
         else HIPC(hipMemcpyAsync(w.d_Q, vecs + (size_t)done * D, (size_t)cq * D * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        HIPC(hipEventRecord(w.ev[0], c->stream));
+        F2VC(w.timer.start(c->stream));
         if (rows) hipLaunchKernelGGL(nearest_gather_kernel, dim3(std::min<size_t>(((size_t)cq * D + 255) / 256, 4096)), dim3(256), 0, c->stream, X, (const uint32_t *)w.d_qids, cq, D, w.d_Q);
         if (cosine) {
             if (done == 0) hipLaunchKernelGGL(nearest_rnorm_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, X, n, D, w.d_rc);
@@ -3294,24 +3332,21 @@ int nearest_run_on(f2v_ctx *c, const float *X, uint32_t D, const uint32_t *qids,
         a.splits = splits;
         a.tiles_per_split = tps;
         a.cosine = cosine ? 1u : 0u;
-        if (metric == F2V_SIM_L2) rc = qb == 128 ? launch_nearest_t<true, 2, 2, 2>(c, a, qblocks, splits) : launch_nearest_t<true, 1, 1, 1>(c, a, qblocks, splits);
-        else rc = qb == 128 ? launch_nearest_t<false, 2, 2, 2>(c, a, qblocks, splits) : launch_nearest_t<false, 1, 1, 1>(c, a, qblocks, splits);
-        if (rc != F2V_OK) return rc;
+        if (metric == F2V_SIM_L2) F2VC((qb == 128 ? launch_nearest_t<true, 2, 2, 2>(c, a, qblocks, splits) : launch_nearest_t<true, 1, 1, 1>(c, a, qblocks, splits)));
+        else F2VC((qb == 128 ? launch_nearest_t<false, 2, 2, 2>(c, a, qblocks, splits) : launch_nearest_t<false, 1, 1, 1>(c, a, qblocks, splits)));
         hipLaunchKernelGGL(nearest_merge_kernel, dim3(cq), dim3(256), 0, c->stream, (const nn_key_t *)w.d_ws, splits, k, w.d_ids, w.d_scores);
         if (recall_out)
             hipLaunchKernelGGL(nearest_recall_kernel, dim3((cq + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)w.d_ids, (const uint32_t *)w.d_qids, cq, k,
                                (const uint32_t *)c->d_rowptr, (const uint32_t *)c->d_colids, w.d_counts);
         HIPC(hipGetLastError());
         if (d_ids_dst) HIPC(hipMemcpyAsync(d_ids_dst + (size_t)done * k, w.d_ids, slots * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-        HIPC(hipEventRecord(w.ev[1], c->stream));
+        F2VC(w.timer.stop(c->stream));
         if (ids_out) HIPC(hipMemcpyAsync(ids_out + (size_t)done * k, w.d_ids, slots * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         if (scores_out) HIPC(hipMemcpyAsync(scores_out + (size_t)done * k, w.d_scores, slots * sizeof(float), hipMemcpyDeviceToHost, c->stream));
         HIPC(hipStreamSynchronize(c->stream));
-        float ms = 0.f;
-        HIPC(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
-        seconds += ms * 1e-3;
+        F2VC(w.timer.seconds(&seconds));
     }
-    if ((rc = check_kernel_err(c, "nearest-neighbour query")) != F2V_OK) return rc;
+    F2VC(check_kernel_err(c, "nearest-neighbour query"));
     if (recall_out) {
         HIPC(hipMemcpyAsync(recall_out, w.d_counts, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
         HIPC(hipStreamSynchronize(c->stream));
@@ -3336,7 +3371,7 @@ bool rows_ascending(f2v_ctx *c) {
     return c->rows_sorted == 1;
 }
 
-// The entry points' common argument and state checks (f2v_objective's preamble).  -> 1: nq == 0, nothing to do and nothing touched.
+// The entry points' common argument checks, then settled_enter.  -> 1: nq == 0, nothing to do and nothing touched.
 // `by_row`: the call searches CSR rows (EXCLUDE_NEIGHBOURS, the recall count), which needs their ids ascending -- f2v_create documents
 // that order but no earlier kernel depended on it, so it is verified here, once per handle, on the host copy.
 int nearest_enter(f2v_ctx *c, const char *who, uint32_t nq, uint32_t k, int metric, uint32_t flags, bool by_row) {
@@ -3347,58 +3382,40 @@ int nearest_enter(f2v_ctx *c, const char *who, uint32_t nq, uint32_t k, int metr
     if (by_row) {
         if (!rows_ascending(c)) return fail(F2V_EINVAL, "%s: the CSR's column ids are not ascending inside every row (needed to search a row)", who);
     }
-    if (!c->have_x)
-        return fail(F2V_ESTATE, c->x_invalid ? "%s: the embeddings are invalid since a launch gave up a bounded wait: set or initialise them again"
-                                             : "%s: embeddings were never initialised", who);
-    if (nq == 0) return 1;
-    HIPC(hipSetDevice(c->device));
-    return flush_pending(c);
+    if (nq == 0 && c->have_x) return 1;
+    return settled_enter(c, who);
 }
 
 // ---- clustering (f2v_kmeans.hip.h; definition in include/f2v.h) ------------------------------------------------------------------
 template <int RB>
 int launch_assign_t(f2v_ctx *c, const KmAssignArgs &a) {
     const size_t lds = km_lds_bytes(RB, a.D, a.tile);
-    const uint32_t form = RB == 64 ? 1u : RB == 128 ? 2u : 4u;
-    if (lds > 65536 && !(c->km.lds_allowed & form)) {  // D is fixed per handle and the tile never outgrows kKmTileFloats or one sweep
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void *>(&kmeans_assign_kernel<RB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        c->km.lds_allowed |= form;
-    }
+    F2VC(allow_lds(c, reinterpret_cast<const void *>(&kmeans_assign_kernel<RB>), lds));
     hipLaunchKernelGGL((kmeans_assign_kernel<RB>), dim3((a.n + RB - 1) / RB), dim3(kKmThreads), lds, c->stream, a);
     HIPC(hipGetLastError());
     return F2V_OK;
 }
 
-template <class T>
-int km_alloc(T *&p, size_t count) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    hipError_t e = hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T));
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? F2V_ENOMEM : F2V_ENODEV, "clustering workspace: %s", hipGetErrorString(e));
-    return F2V_OK;
-}
-
-// the workspace of f2v_kmeans for `k` clusters (f2v.h states its size)
+// the workspace of f2v_kmeans for `k` clusters (f2v.h states its size): the per-vertex arrays once, the per-cluster ones for the largest k so far
 int kmeans_workspace(f2v_ctx *c, uint32_t k) {
     f2v_ctx::Kmeans &w = c->km;
-    for (hipEvent_t &e : w.ev)
-        if (!e) HIPC(hipEventCreate(&e));
-    if (w.cap_k >= k) return F2V_OK;
-    HIPC(hipStreamSynchronize(c->stream));
+    const char *what = "clustering";
     const size_t n = c->n, D = c->D, blocks = (n + kKmSortBlock - 1) / kKmSortBlock;
-    int rc;
-    if (!w.d_labels) {
-        if ((rc = km_alloc(w.d_labels, n)) != F2V_OK || (rc = km_alloc(w.d_bestL, n)) != F2V_OK || (rc = km_alloc(w.d_order, n)) != F2V_OK ||
-            (rc = km_alloc(w.d_dist, n)) != F2V_OK || (rc = km_alloc(w.d_ipart, (n + kKmPiece - 1) / kKmPiece)) != F2V_OK ||
-            (rc = km_alloc(w.d_inertia, 1)) != F2V_OK || (rc = km_alloc(w.d_changed, 1)) != F2V_OK)
-            return rc;
-    }
-    w.cap_k = 0;
-    if ((rc = km_alloc(w.d_C, k * D)) != F2V_OK || (rc = km_alloc(w.d_bestC, k * D)) != F2V_OK || (rc = km_alloc(w.d_hist, blocks * k)) != F2V_OK ||
-        (rc = km_alloc(w.d_counts, k)) != F2V_OK || (rc = km_alloc(w.d_start, (size_t)k + 1)) != F2V_OK || (rc = km_alloc(w.d_pstart, (size_t)k + 1)) != F2V_OK ||
-        (rc = km_alloc(w.d_seed, k)) != F2V_OK || (rc = km_alloc(w.d_psum, (n / kKmPiece + k) * D)) != F2V_OK)
-        return rc;
-    w.cap_k = k;
+    F2VC(w.d_labels.reserve(c, n, what));
+    F2VC(w.d_bestL.reserve(c, n, what));
+    F2VC(w.d_order.reserve(c, n, what));
+    F2VC(w.d_dist.reserve(c, n, what));
+    F2VC(w.d_ipart.reserve(c, (n + kKmPiece - 1) / kKmPiece, what));
+    F2VC(w.d_inertia.reserve(c, 1, what));
+    F2VC(w.d_changed.reserve(c, 1, what));
+    F2VC(w.d_C.reserve(c, k * D, what));
+    F2VC(w.d_bestC.reserve(c, k * D, what));
+    F2VC(w.d_hist.reserve(c, blocks * k, what));
+    F2VC(w.d_counts.reserve(c, k, what));
+    F2VC(w.d_start.reserve(c, (size_t)k + 1, what));
+    F2VC(w.d_pstart.reserve(c, (size_t)k + 1, what));
+    F2VC(w.d_seed.reserve(c, k, what));
+    F2VC(w.d_psum.reserve(c, (n / kKmPiece + k) * D, what));
     return F2V_OK;
 }
 
@@ -3424,13 +3441,39 @@ void kmeans_seed_rows(uint32_t n, uint32_t k, uint64_t seed, std::vector<uint32_
     for (uint32_t i = 0; i < k; i++) ids[i] = heap[i].second;
 }
 
-// histogram, scan: d_counts / d_start / d_pstart of `labels` and the per-block offsets the scatter needs
-void kmeans_count(f2v_ctx *c, const uint32_t *labels, uint32_t k) {
+// histogram, scan: d_counts / d_start / d_pstart of the `m` labels and the per-block offsets the scatter needs
+void kmeans_count(f2v_ctx *c, const uint32_t *labels, uint32_t m, uint32_t k) {
     f2v_ctx::Kmeans &w = c->km;
-    const uint32_t blocks = (c->n + kKmSortBlock - 1) / kKmSortBlock;
-    hipLaunchKernelGGL(kmeans_hist_kernel, dim3(blocks), dim3(256), 0, c->stream, labels, c->n, k, w.d_hist);
+    const uint32_t blocks = (m + kKmSortBlock - 1) / kKmSortBlock;
+    hipLaunchKernelGGL(kmeans_hist_kernel, dim3(blocks), dim3(256), 0, c->stream, labels, m, k, w.d_hist);
     hipLaunchKernelGGL(kmeans_offsets_kernel, dim3(k), dim3(256), 0, c->stream, w.d_hist, blocks, k, w.d_counts);
     hipLaunchKernelGGL(kmeans_starts_kernel, dim3(1), dim3(256), 0, c->stream, (const uint32_t *)w.d_counts, k, w.d_start, w.d_pstart);
+}
+
+// ... and the scatter: d_order = the places 0 .. m-1 by (label, place)
+void kmeans_sort(f2v_ctx *c, const uint32_t *labels, uint32_t m, uint32_t k) {
+    f2v_ctx::Kmeans &w = c->km;
+    kmeans_count(c, labels, m, k);
+    hipLaunchKernelGGL(kmeans_scatter_kernel, dim3((m + kKmSortBlock - 1) / kKmSortBlock), dim3(64), 0, c->stream, labels, m, k, (const uint32_t *)w.d_hist,
+                       (const uint32_t *)w.d_start, w.d_order);
+}
+
+// the arguments of kmeans_piece_sum_kernel over the sorted members
+KmSumArgs km_sum_args(f2v_ctx *c, uint32_t k) {
+    f2v_ctx::Kmeans &w = c->km;
+    KmSumArgs s{};
+    s.X = c->d_X[c->cur];
+    s.order = w.d_order;
+    s.start = w.d_start;
+    s.counts = w.d_counts;
+    s.pstart = w.d_pstart;
+    s.psum = w.d_psum;
+    s.n = c->n;
+    s.D = c->D;
+    s.k = k;
+    s.lanes = 1;
+    while (s.lanes < 64 && 4 * s.lanes < c->D) s.lanes *= 2;
+    return s;
 }
 
 // One run of the iteration of f2v.h from the centroids in d_C: leaves L_t in d_labels, C_(t-1) in d_C, the distances in d_dist.
@@ -3448,25 +3491,12 @@ int kmeans_run(f2v_ctx *c, uint32_t k, uint32_t max_iters, uint32_t *iterations,
     a.D = D;
     a.k = k;
     a.tile = km_tile(rb, D, k);
-    KmSumArgs s{};
-    s.X = a.X;
-    s.order = w.d_order;
-    s.start = w.d_start;
-    s.counts = w.d_counts;
-    s.pstart = w.d_pstart;
-    s.psum = w.d_psum;
-    s.n = n;
-    s.D = D;
-    s.k = k;
-    s.lanes = 1;
-    while (s.lanes < 64 && 4 * s.lanes < D) s.lanes *= 2;
-    const uint32_t blocks = (n + kKmSortBlock - 1) / kKmSortBlock;
+    const KmSumArgs s = km_sum_args(c, k);
     const size_t max_pieces = (size_t)n / kKmPiece + k;
     HIPC(hipMemsetAsync(w.d_labels, 0xFF, (size_t)n * sizeof(uint32_t), c->stream));  // no label yet: the first assignment changes every row
     for (uint32_t t = 1;; t++) {
         HIPC(hipMemsetAsync(w.d_changed, 0, sizeof(uint32_t), c->stream));
-        int rc = rb == 256 ? launch_assign_t<256>(c, a) : rb == 128 ? launch_assign_t<128>(c, a) : launch_assign_t<64>(c, a);
-        if (rc != F2V_OK) return rc;
+        F2VC(rb == 256 ? launch_assign_t<256>(c, a) : rb == 128 ? launch_assign_t<128>(c, a) : launch_assign_t<64>(c, a));
         uint32_t changed = 0;
         HIPC(hipMemcpyAsync(&changed, w.d_changed, sizeof changed, hipMemcpyDeviceToHost, c->stream));
         HIPC(hipStreamSynchronize(c->stream));
@@ -3480,9 +3510,7 @@ int kmeans_run(f2v_ctx *c, uint32_t k, uint32_t max_iters, uint32_t *iterations,
             *converged = 0;
             return F2V_OK;
         }
-        kmeans_count(c, w.d_labels, k);
-        hipLaunchKernelGGL(kmeans_scatter_kernel, dim3(blocks), dim3(64), 0, c->stream, (const uint32_t *)w.d_labels, n, k, (const uint32_t *)w.d_hist,
-                           (const uint32_t *)w.d_start, w.d_order);
+        kmeans_sort(c, w.d_labels, n, k);
         hipLaunchKernelGGL(kmeans_piece_sum_kernel, dim3((uint32_t)((max_pieces * s.lanes + kKmThreads - 1) / kKmThreads)), dim3(kKmThreads), 0, c->stream, s);
         hipLaunchKernelGGL(kmeans_centroid_kernel, dim3(k, (D + 31) / 32), dim3(kKmThreads), 0, c->stream, (const double *)w.d_psum, (const uint32_t *)w.d_counts,
                            (const uint32_t *)w.d_pstart, D, w.d_C);
@@ -3493,26 +3521,10 @@ int kmeans_run(f2v_ctx *c, uint32_t k, uint32_t max_iters, uint32_t *iterations,
 // ---- logistic regression (f2v_logreg.hip.h; definition in include/f2v.h) ----------------------------------------------------------
 constexpr uint32_t kLrDecisionChunk = 262144;  // samples per launch of f2v_logreg_decision: bounds its z buffer
 
-template <class T>
-int lr_grow(f2v_ctx *c, T *&p, size_t &cap, size_t count) {
-    if (p && cap >= count) return F2V_OK;
-    HIPC(hipStreamSynchronize(c->stream));
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T));
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? F2V_ENOMEM : F2V_ENODEV, "logistic-regression workspace: %s", hipGetErrorString(e));
-    cap = count;
-    return F2V_OK;
-}
-
 template <bool EVAL, int NA, int NZ>
-int launch_logreg_t(f2v_ctx *c, const LrArgs &a, uint32_t form) {
+int launch_logreg_t(f2v_ctx *c, const LrArgs &a) {
     const size_t lds = lr_lds_bytes(a.D, a.cg);
-    if (lds > 65536 && !(c->lr.lds_allowed & (1u << form))) {
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void *>(&logreg_kernel<EVAL, NA, NZ>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        c->lr.lds_allowed |= 1u << form;
-    }
+    F2VC(allow_lds(c, reinterpret_cast<const void *>(&logreg_kernel<EVAL, NA, NZ>), lds));
     hipLaunchKernelGGL((logreg_kernel<EVAL, NA, NZ>), dim3((a.m + kLrBlock - 1) / kLrBlock, (a.nc + a.cg - 1) / a.cg), dim3(kLrThreads), lds, c->stream, a);
     HIPC(hipGetLastError());
     return F2V_OK;
@@ -3525,18 +3537,18 @@ int launch_logreg(f2v_ctx *c, const LrArgs &a, bool eval) {
     uint32_t nz = 1;
     while (nz * kLrGroups < a.cg) nz *= 2;
     const uint32_t wide = a.lg > 7 ? a.lg - 7 : 0;
-    if (!eval) return nz == 1 ? launch_logreg_t<false, 1, 1>(c, a, 0) : nz == 2 ? launch_logreg_t<false, 1, 2>(c, a, 1) : nz == 4 ? launch_logreg_t<false, 1, 4>(c, a, 2)
-                                                                                                                                  : launch_logreg_t<false, 1, 8>(c, a, 3);
+    if (!eval) return nz == 1 ? launch_logreg_t<false, 1, 1>(c, a) : nz == 2 ? launch_logreg_t<false, 1, 2>(c, a) : nz == 4 ? launch_logreg_t<false, 1, 4>(c, a)
+                                                                                                                            : launch_logreg_t<false, 1, 8>(c, a);
     switch (nz << (4 * wide)) {
-    case 0x001: return launch_logreg_t<true, 4, 1>(c, a, 4);
-    case 0x002: return launch_logreg_t<true, 8, 2>(c, a, 5);
-    case 0x004: return launch_logreg_t<true, 16, 4>(c, a, 6);
-    case 0x008: return launch_logreg_t<true, 32, 8>(c, a, 7);
-    case 0x010: return launch_logreg_t<true, 8, 1>(c, a, 8);
-    case 0x020: return launch_logreg_t<true, 16, 2>(c, a, 9);
-    case 0x040: return launch_logreg_t<true, 32, 4>(c, a, 10);
-    case 0x100: return launch_logreg_t<true, 16, 1>(c, a, 11);
-    case 0x200: return launch_logreg_t<true, 32, 2>(c, a, 12);
+    case 0x001: return launch_logreg_t<true, 4, 1>(c, a);
+    case 0x002: return launch_logreg_t<true, 8, 2>(c, a);
+    case 0x004: return launch_logreg_t<true, 16, 4>(c, a);
+    case 0x008: return launch_logreg_t<true, 32, 8>(c, a);
+    case 0x010: return launch_logreg_t<true, 8, 1>(c, a);
+    case 0x020: return launch_logreg_t<true, 16, 2>(c, a);
+    case 0x040: return launch_logreg_t<true, 32, 4>(c, a);
+    case 0x100: return launch_logreg_t<true, 16, 1>(c, a);
+    case 0x200: return launch_logreg_t<true, 32, 2>(c, a);
     }
     return fail(F2V_EINVAL, "logistic regression: no kernel for %u classes per workgroup at dim %u", a.cg, a.D);
 }
@@ -3553,34 +3565,20 @@ int logreg_enter(f2v_ctx *c, const char *who, const uint32_t *a_ids, const uint3
     const size_t ybytes = (size_t)m * classes;
     for (size_t i = 0; y && i < ybytes; i++)
         if (y[i] > 1) return fail(F2V_EINVAL, "%s: target %zu of sample %zu is %u, not 0 or 1", who, i % classes, i / classes, (unsigned)y[i]);
-    if (!c->have_x)
-        return fail(F2V_ESTATE, c->x_invalid ? "%s: the embeddings are invalid since a launch gave up a bounded wait: set or initialise them again"
-                                             : "%s: embeddings were never initialised", who);
-    HIPC(hipSetDevice(c->device));
-    int rc = flush_pending(c);
-    if (rc != F2V_OK) return rc;
+    F2VC(settled_enter(c, who));
     f2v_ctx::Logreg &w = c->lr;
-    for (hipEvent_t &e : w.ev)
-        if (!e) HIPC(hipEventCreate(&e));
+    const char *what = "logistic-regression";
     const size_t E = (size_t)c->D + 2;
-    if (!w.d_W) {
-        size_t cap = 0;
-        if ((rc = lr_grow(c, w.d_W, cap, (size_t)F2V_LOGREG_MAX_CLASSES * E)) != F2V_OK) return rc;
-        if ((rc = lr_grow(c, w.d_sums, cap = 0, (size_t)F2V_LOGREG_MAX_CLASSES * E)) != F2V_OK) return rc;
-        if ((rc = lr_grow(c, w.d_cmap, cap = 0, F2V_LOGREG_MAX_CLASSES)) != F2V_OK) return rc;
-    }
-    if (w.cap_m < m) {
-        size_t cap = w.cap_m;
-        if ((rc = lr_grow(c, w.d_a, cap, m)) != F2V_OK) return rc;
-        w.cap_m = 0;
-        if ((rc = lr_grow(c, w.d_b, cap = 0, m)) != F2V_OK) return rc;
-        w.cap_m = m;
-    }
+    F2VC(w.d_W.reserve(c, (size_t)F2V_LOGREG_MAX_CLASSES * E, what));
+    F2VC(w.d_sums.reserve(c, (size_t)F2V_LOGREG_MAX_CLASSES * E, what));
+    F2VC(w.d_cmap.reserve(c, F2V_LOGREG_MAX_CLASSES, what));
+    F2VC(w.d_a.reserve(c, m, what));
+    F2VC(w.d_b.reserve(c, m, what));
     HIPC(hipMemcpyAsync(w.d_a, a_ids, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     if (b_ids) HIPC(hipMemcpyAsync(w.d_b, b_ids, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     if (y) {
-        if ((rc = lr_grow(c, w.d_y, w.cap_y, ybytes)) != F2V_OK) return rc;
-        if ((rc = lr_grow(c, w.d_part, w.cap_part, (size_t)((m + kLrBlock - 1) / kLrBlock) * classes * E)) != F2V_OK) return rc;
+        F2VC(w.d_y.reserve(c, ybytes, what));
+        F2VC(w.d_part.reserve(c, (size_t)((m + kLrBlock - 1) / kLrBlock) * classes * E, what));
         HIPC(hipMemcpyAsync(w.d_y, y, ybytes, hipMemcpyHostToDevice, c->stream));
     }
     return F2V_OK;
@@ -3614,18 +3612,15 @@ int logreg_pass(f2v_ctx *c, bool pairs, uint32_t m, int feature, uint32_t classe
     HIPC(hipMemcpyAsync(w.d_W, W, (size_t)nc * (D + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
     LrArgs a = logreg_args(c, pairs, m, feature, nc, classes);
     a.out = w.d_part;
-    HIPC(hipEventRecord(w.ev[0], c->stream));
-    int rc = launch_logreg(c, a, true);
-    if (rc != F2V_OK) return rc;
+    F2VC(w.timer.start(c->stream));
+    F2VC(launch_logreg(c, a, true));
     hipLaunchKernelGGL(logreg_reduce_kernel, dim3((nc * E + 255) / 256), dim3(256), 0, c->stream, (const double *)w.d_part, blocks, nc * E, w.d_sums);
     HIPC(hipGetLastError());
-    HIPC(hipEventRecord(w.ev[1], c->stream));
+    F2VC(w.timer.stop(c->stream));
     std::vector<double> sums((size_t)nc * E);
     HIPC(hipMemcpyAsync(sums.data(), w.d_sums, sums.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
-    if (seconds) *seconds += ms * 1e-3;
+    F2VC(w.timer.seconds(seconds));
     for (uint32_t k = 0; k < nc; k++) {  // the regulariser, as f2v.h orders it
         const double *wk = W + (size_t)k * (D + 1), *sk = sums.data() + (size_t)k * E;
         double q = 0.0;
@@ -3688,19 +3683,6 @@ void lbfgs_direction(LbfgsClass &k) {
 }
 
 // ---- separation (f2v_separation.hip.h; definition in include/f2v.h) ----------------------------------------------------------------
-template <class T>
-int sep_grow(f2v_ctx *c, T *&p, size_t &cap, size_t count) {
-    if (p && cap >= count) return F2V_OK;
-    HIPC(hipStreamSynchronize(c->stream));
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T));
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? F2V_ENOMEM : F2V_ENODEV, "separation workspace: %s", hipGetErrorString(e));
-    cap = count;
-    return F2V_OK;
-}
-
 // What both scores share: the labelling checked, the labelled vertices (ascending id), the member counts
 struct SepLabels {
     std::vector<uint32_t> ids, lab, counts;  // the labelled vertices, their labels, members per cluster
@@ -3729,27 +3711,16 @@ int sep_check(f2v_ctx *c, const char *who, const uint32_t *labels, uint32_t n_cl
 // turns the places into vertex ids.
 int sep_enter(f2v_ctx *c, const char *who, const SepLabels &L, uint32_t k) {
     if (c->n >= 0xFFFFFFFFu - 256u) return fail(F2V_EINVAL, "%s: too many vertices for 32-bit row blocks", who);
-    if (!c->have_x)
-        return fail(F2V_ESTATE, c->x_invalid ? "%s: the embeddings are invalid since a launch gave up a bounded wait: set or initialise them again"
-                                             : "%s: embeddings were never initialised", who);
-    HIPC(hipSetDevice(c->device));
-    int rc = flush_pending(c);
-    if (rc != F2V_OK) return rc;
-    if ((rc = kmeans_workspace(c, k)) != F2V_OK) return rc;
+    F2VC(settled_enter(c, who));
+    F2VC(kmeans_workspace(c, k));
     f2v_ctx::Kmeans &w = c->km;
     f2v_ctx::Separation &sp = c->sep;
-    for (hipEvent_t &e : sp.ev)
-        if (!e) HIPC(hipEventCreate(&e));
-    const uint32_t m = (uint32_t)L.ids.size(), blocks = (m + kKmSortBlock - 1) / kKmSortBlock;
-    if ((rc = sep_grow(c, sp.d_ids, sp.cap_ids, m)) != F2V_OK) return rc;
+    const uint32_t m = (uint32_t)L.ids.size();
+    F2VC(sp.d_ids.reserve(c, m, "separation"));
     HIPC(hipMemcpyAsync(sp.d_ids, L.ids.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIPC(hipMemcpyAsync(w.d_labels, L.lab.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIPC(hipEventRecord(sp.ev[0], c->stream));
-    hipLaunchKernelGGL(kmeans_hist_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint32_t *)w.d_labels, m, k, w.d_hist);
-    hipLaunchKernelGGL(kmeans_offsets_kernel, dim3(k), dim3(256), 0, c->stream, w.d_hist, blocks, k, w.d_counts);
-    hipLaunchKernelGGL(kmeans_starts_kernel, dim3(1), dim3(256), 0, c->stream, (const uint32_t *)w.d_counts, k, w.d_start, w.d_pstart);
-    hipLaunchKernelGGL(kmeans_scatter_kernel, dim3(blocks), dim3(64), 0, c->stream, (const uint32_t *)w.d_labels, m, k, (const uint32_t *)w.d_hist,
-                       (const uint32_t *)w.d_start, w.d_order);
+    F2VC(sp.timer.start(c->stream));
+    kmeans_sort(c, w.d_labels, m, k);
     hipLaunchKernelGGL(separation_ids_kernel, dim3((m + 255) / 256), dim3(256), 0, c->stream, w.d_order, (const uint32_t *)sp.d_ids, m);
     HIPC(hipGetLastError());
     return F2V_OK;
@@ -3774,13 +3745,8 @@ int f2v_kmeans(f2v_handle c, uint32_t k, uint32_t max_iters, uint32_t restarts, 
     if (restarts == 0) return fail(F2V_EINVAL, "f2v_kmeans: restarts must be at least 1");
     if (restarts > 1 && init_centroids) return fail(F2V_EINVAL, "f2v_kmeans: restarts > 1 need seeded centroids (init_centroids must be NULL)");
     if (c->n >= 0xFFFFFFFFu - 256u) return fail(F2V_EINVAL, "f2v_kmeans: too many vertices for 32-bit row blocks");
-    if (!c->have_x)
-        return fail(F2V_ESTATE, c->x_invalid ? "f2v_kmeans: the embeddings are invalid since a launch gave up a bounded wait: set or initialise them again"
-                                             : "f2v_kmeans: embeddings were never initialised");
-    HIPC(hipSetDevice(c->device));
-    int rc = flush_pending(c);
-    if (rc != F2V_OK) return rc;
-    if ((rc = kmeans_workspace(c, k)) != F2V_OK) return rc;
+    F2VC(settled_enter(c, "f2v_kmeans"));
+    F2VC(kmeans_workspace(c, k));
     f2v_ctx::Kmeans &w = c->km;
     const uint32_t n = c->n, D = c->D;
     const size_t cbytes = (size_t)k * D * sizeof(float), lbytes = (size_t)n * sizeof(uint32_t);
@@ -3790,7 +3756,7 @@ int f2v_kmeans(f2v_handle c, uint32_t k, uint32_t max_iters, uint32_t restarts, 
         kmeans_seed_rows(n, k, seed + r, ids);
         all_ids.insert(all_ids.end(), ids.begin(), ids.end());
     }
-    HIPC(hipEventRecord(w.ev[0], c->stream));
+    F2VC(w.timer.start(c->stream));
     for (uint32_t r = 0; r < restarts; r++) {
         if (init_centroids) {
             HIPC(hipMemcpyAsync(w.d_C, init_centroids, cbytes, hipMemcpyHostToDevice, c->stream));
@@ -3801,7 +3767,7 @@ int f2v_kmeans(f2v_handle c, uint32_t k, uint32_t max_iters, uint32_t restarts, 
             HIPC(hipGetLastError());
         }
         uint32_t iterations = 0, converged = 0;
-        if ((rc = kmeans_run(c, k, max_iters, &iterations, &converged)) != F2V_OK) return rc;
+        F2VC(kmeans_run(c, k, max_iters, &iterations, &converged));
         const uint32_t parts = (n + kKmPiece - 1) / kKmPiece;
         hipLaunchKernelGGL(kmeans_inertia_piece_kernel, dim3((parts + 255) / 256), dim3(256), 0, c->stream, (const float *)w.d_dist, n, w.d_ipart);
         hipLaunchKernelGGL(kmeans_inertia_reduce_kernel, dim3(1), dim3(256), 0, c->stream, (const double *)w.d_ipart, parts, w.d_inertia);
@@ -3822,19 +3788,17 @@ int f2v_kmeans(f2v_handle c, uint32_t k, uint32_t max_iters, uint32_t restarts, 
     }
     const uint32_t *L = restarts > 1 ? w.d_bestL : w.d_labels;
     const float *Cb = restarts > 1 ? w.d_bestC : w.d_C;
-    kmeans_count(c, L, k);
+    kmeans_count(c, L, n, k);
     HIPC(hipGetLastError());
-    HIPC(hipEventRecord(w.ev[1], c->stream));
+    F2VC(w.timer.stop(c->stream));
     std::vector<uint32_t> counts(k);
     HIPC(hipMemcpyAsync(labels_out, L, lbytes, hipMemcpyDeviceToHost, c->stream));
     if (centroids_out) HIPC(hipMemcpyAsync(centroids_out, Cb, cbytes, hipMemcpyDeviceToHost, c->stream));
     HIPC(hipMemcpyAsync(counts.data(), w.d_counts, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
-    if ((rc = check_kernel_err(c, "f2v_kmeans")) != F2V_OK) return rc;
+    F2VC(check_kernel_err(c, "f2v_kmeans"));
     for (uint32_t i = 0; counts_out && i < k; i++) counts_out[i] = counts[i];
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
-    best.seconds = ms * 1e-3;
+    F2VC(w.timer.seconds(&best.seconds));
     *info_out = best;
     return F2V_OK;
 }
@@ -3848,15 +3812,9 @@ int f2v_modularity(f2v_handle c, const uint32_t *labels, uint32_t n_clusters, do
     if (!rows_ascending(c)) return fail(F2V_EINVAL, "f2v_modularity: the CSR's column ids are not ascending inside every row (needed to search a row)");
     HIPC(hipSetDevice(c->device));
     f2v_ctx::Kmeans &w = c->km;
-    int rc;
-    if (!w.d_mlabels && (rc = km_alloc(w.d_mlabels, c->n)) != F2V_OK) return rc;
     const size_t words = 1 + 2 * (size_t)n_clusters;
-    if (w.cap_nc < n_clusters) {
-        HIPC(hipStreamSynchronize(c->stream));
-        w.cap_nc = 0;
-        if ((rc = km_alloc(w.d_tallies, words)) != F2V_OK) return rc;
-        w.cap_nc = n_clusters;
-    }
+    F2VC(w.d_mlabels.reserve(c, c->n, "clustering"));
+    F2VC(w.d_tallies.reserve(c, words, "clustering"));
     HIPC(hipMemcpyAsync(w.d_mlabels, labels, (size_t)c->n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIPC(hipMemsetAsync(w.d_tallies, 0, words * sizeof(unsigned long long), c->stream));
     ModArgs a{};
@@ -3893,8 +3851,7 @@ int f2v_silhouette(f2v_handle c, const uint32_t *labels, uint32_t n_clusters, co
     if (!c || !labels || !score_out) return fail(F2V_EINVAL, "f2v_silhouette: null argument");
     if (sample_ids && nq == 0) return fail(F2V_EINVAL, "f2v_silhouette: nq = 0 samples");
     SepLabels L;
-    int rc = sep_check(c, "f2v_silhouette", labels, n_clusters, L);
-    if (rc != F2V_OK) return rc;
+    F2VC(sep_check(c, "f2v_silhouette", labels, n_clusters, L));
     if (L.nonempty >= L.ids.size())
         return fail(F2V_EINVAL, "f2v_silhouette: %u non-empty clusters for %zu labelled vertices (at most one fewer is allowed)", L.nonempty, L.ids.size());
     const uint32_t k = n_clusters;
@@ -3921,15 +3878,20 @@ int f2v_silhouette(f2v_handle c, const uint32_t *labels, uint32_t n_clusters, co
     const uint32_t spans = cspan[k], chunk = std::min(c->sep.chunk, nq), parts = (nq + kSepPiece - 1) / kSepPiece;
     const uint32_t rb = c->sep.block ? c->sep.block : 64u;
     if ((uint64_t)spans * ((chunk + rb - 1) / rb) > 0x7FFFFFFFull) return fail(F2V_EINVAL, "f2v_silhouette: too many workgroups per launch: lower \"separation_chunk\"");
-    if ((rc = sep_enter(c, "f2v_silhouette", L, k)) != F2V_OK) return rc;
+    F2VC(sep_enter(c, "f2v_silhouette", L, k));
     f2v_ctx::Kmeans &w = c->km;
     f2v_ctx::Separation &sp = c->sep;
-    if ((rc = sep_grow(c, sp.d_sid, sp.cap_sid, nq)) != F2V_OK || (rc = sep_grow(c, sp.d_slab, sp.cap_slab, nq)) != F2V_OK ||
-        (rc = sep_grow(c, sp.d_other, sp.cap_other, nq)) != F2V_OK || (rc = sep_grow(c, sp.d_s, sp.cap_s, nq)) != F2V_OK ||
-        (rc = sep_grow(c, sp.d_part, sp.cap_part, parts)) != F2V_OK || (rc = sep_grow(c, sp.d_sum, sp.cap_sum, 1)) != F2V_OK ||
-        (rc = sep_grow(c, sp.d_span_start, sp.cap_span_start, spans)) != F2V_OK || (rc = sep_grow(c, sp.d_span_cnt, sp.cap_span_cnt, spans)) != F2V_OK ||
-        (rc = sep_grow(c, sp.d_cspan, sp.cap_cspan, (size_t)k + 1)) != F2V_OK || (rc = sep_grow(c, sp.d_ws, sp.cap_ws, (size_t)spans * chunk)) != F2V_OK)
-        return rc;
+    const char *what = "separation";
+    F2VC(sp.d_sid.reserve(c, nq, what));
+    F2VC(sp.d_slab.reserve(c, nq, what));
+    F2VC(sp.d_other.reserve(c, nq, what));
+    F2VC(sp.d_s.reserve(c, nq, what));
+    F2VC(sp.d_part.reserve(c, parts, what));
+    F2VC(sp.d_sum.reserve(c, 1, what));
+    F2VC(sp.d_span_start.reserve(c, spans, what));
+    F2VC(sp.d_span_cnt.reserve(c, spans, what));
+    F2VC(sp.d_cspan.reserve(c, (size_t)k + 1, what));
+    F2VC(sp.d_ws.reserve(c, (size_t)spans * chunk, what));
     HIPC(hipMemcpyAsync(sp.d_sid, sid, (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIPC(hipMemcpyAsync(sp.d_slab, slab.data(), (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIPC(hipMemcpyAsync(sp.d_span_start, span_start.data(), (size_t)spans * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
@@ -3947,7 +3909,7 @@ int f2v_silhouette(f2v_handle c, const uint32_t *labels, uint32_t n_clusters, co
         a.D = c->D;
         a.nq = cq;
         a.chunk = chunk;
-        if ((rc = rb == 128 ? launch_pair_t<128>(c, a, spans) : launch_pair_t<64>(c, a, spans)) != F2V_OK) return rc;
+        F2VC(rb == 128 ? launch_pair_t<128>(c, a, spans) : launch_pair_t<64>(c, a, spans));
         SepFinishArgs f{};
         f.ws = sp.d_ws;
         f.slab = sp.d_slab + q0;
@@ -3964,17 +3926,16 @@ int f2v_silhouette(f2v_handle c, const uint32_t *labels, uint32_t n_clusters, co
     hipLaunchKernelGGL(separation_piece_kernel, dim3((parts + 255) / 256), dim3(256), 0, c->stream, (const double *)sp.d_s, nq, sp.d_part);
     hipLaunchKernelGGL(kmeans_inertia_reduce_kernel, dim3(1), dim3(256), 0, c->stream, (const double *)sp.d_part, parts, sp.d_sum);
     HIPC(hipGetLastError());
-    HIPC(hipEventRecord(sp.ev[1], c->stream));
-    double sum = 0.0;
+    F2VC(sp.timer.stop(c->stream));
+    double sum = 0.0, seconds = 0.0;
     HIPC(hipMemcpyAsync(&sum, sp.d_sum, sizeof sum, hipMemcpyDeviceToHost, c->stream));
     if (s_out) HIPC(hipMemcpyAsync(s_out, sp.d_s, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (other_out) HIPC(hipMemcpyAsync(other_out, sp.d_other, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
-    if ((rc = check_kernel_err(c, "f2v_silhouette")) != F2V_OK) return rc;
+    F2VC(check_kernel_err(c, "f2v_silhouette"));
     *score_out = sum / (double)nq;
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, sp.ev[0], sp.ev[1]));
-    if (seconds_out) *seconds_out = ms * 1e-3;
+    F2VC(sp.timer.seconds(&seconds));
+    if (seconds_out) *seconds_out = seconds;
     return F2V_OK;
 }
 
@@ -3982,28 +3943,17 @@ int f2v_davies_bouldin(f2v_handle c, const uint32_t *labels, uint32_t n_clusters
                        uint64_t *counts_out, double *seconds_out) {
     if (!c || !labels || !score_out) return fail(F2V_EINVAL, "f2v_davies_bouldin: null argument");
     SepLabels L;
-    int rc = sep_check(c, "f2v_davies_bouldin", labels, n_clusters, L);
-    if (rc != F2V_OK) return rc;
+    F2VC(sep_check(c, "f2v_davies_bouldin", labels, n_clusters, L));
     const uint32_t k = n_clusters, D = c->D;
-    if ((rc = sep_enter(c, "f2v_davies_bouldin", L, k)) != F2V_OK) return rc;
+    F2VC(sep_enter(c, "f2v_davies_bouldin", L, k));
     f2v_ctx::Kmeans &w = c->km;
     f2v_ctx::Separation &sp = c->sep;
     uint32_t pieces = 0;
     for (uint32_t cl = 0; cl < k; cl++) pieces += (L.counts[cl] + kSepPiece - 1) / kSepPiece;
-    if ((rc = sep_grow(c, sp.d_part, sp.cap_part, pieces)) != F2V_OK || (rc = sep_grow(c, sp.d_S, sp.cap_S, k)) != F2V_OK) return rc;
+    F2VC(sp.d_part.reserve(c, pieces, "separation"));
+    F2VC(sp.d_S.reserve(c, k, "separation"));
     // the centroids: the k-means update of f2v.h (an empty cluster's row stays zero)
-    KmSumArgs s{};
-    s.X = c->d_X[c->cur];
-    s.order = w.d_order;
-    s.start = w.d_start;
-    s.counts = w.d_counts;
-    s.pstart = w.d_pstart;
-    s.psum = w.d_psum;
-    s.n = c->n;
-    s.D = D;
-    s.k = k;
-    s.lanes = 1;
-    while (s.lanes < 64 && 4 * s.lanes < D) s.lanes *= 2;
+    const KmSumArgs s = km_sum_args(c, k);
     HIPC(hipMemsetAsync(w.d_C, 0, (size_t)k * D * sizeof(float), c->stream));
     hipLaunchKernelGGL(kmeans_piece_sum_kernel, dim3((uint32_t)(((size_t)pieces * s.lanes + kKmThreads - 1) / kKmThreads)), dim3(kKmThreads), 0, c->stream, s);
     hipLaunchKernelGGL(kmeans_centroid_kernel, dim3(k, (D + 31) / 32), dim3(kKmThreads), 0, c->stream, (const double *)w.d_psum, (const uint32_t *)w.d_counts,
@@ -4022,13 +3972,13 @@ int f2v_davies_bouldin(f2v_handle c, const uint32_t *labels, uint32_t n_clusters
     hipLaunchKernelGGL(separation_cluster_kernel, dim3((k + 63) / 64), dim3(64), 0, c->stream, (const double *)sp.d_part, (const uint32_t *)w.d_counts,
                        (const uint32_t *)w.d_pstart, k, sp.d_S);
     HIPC(hipGetLastError());
-    HIPC(hipEventRecord(sp.ev[1], c->stream));
+    F2VC(sp.timer.stop(c->stream));
     std::vector<float> C((size_t)k * D);
     std::vector<double> S(k);
     HIPC(hipMemcpyAsync(C.data(), w.d_C, C.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPC(hipMemcpyAsync(S.data(), sp.d_S, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
-    if ((rc = check_kernel_err(c, "f2v_davies_bouldin")) != F2V_OK) return rc;
+    F2VC(check_kernel_err(c, "f2v_davies_bouldin"));
     // K x K centroid distances and the maxima: small, on the host (this translation unit is built without fast-math and without
     // contraction: fmaf and sqrtf are the single correctly rounded operations of the definition)
     double total = 0.0;
@@ -4057,9 +4007,9 @@ int f2v_davies_bouldin(f2v_handle c, const uint32_t *labels, uint32_t n_clusters
         if (scatter_out) scatter_out[i] = S[i];
         if (counts_out) counts_out[i] = L.counts[i];
     }
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, sp.ev[0], sp.ev[1]));
-    if (seconds_out) *seconds_out = ms * 1e-3;
+    double seconds = 0.0;
+    F2VC(sp.timer.seconds(&seconds));
+    if (seconds_out) *seconds_out = seconds;
     return F2V_OK;
 }
 
@@ -4068,18 +4018,10 @@ int f2v_davies_bouldin(f2v_handle c, const uint32_t *labels, uint32_t n_clusters
 // ---- layout (f2v_layout.hip.h; definition in include/f2v.h) -----------------------------------------------------------------------
 namespace {
 
-// The state checks and the pending minibatches (f2v_kmeans's preamble)
+// The layout calls' range check on n (their kernels count pieces in 32 bits), then settled_enter
 int lay_enter(f2v_ctx *c, const char *who) {
     if (c->n >= 0xFFFFFFFFu - kPcaPiece) return fail(F2V_EINVAL, "%s: too many vertices for 32-bit pieces", who);
-    if (!c->have_x)
-        return fail(F2V_ESTATE, c->x_invalid ? "%s: the embeddings are invalid since a launch gave up a bounded wait: set or initialise them again"
-                                             : "%s: embeddings were never initialised", who);
-    HIPC(hipSetDevice(c->device));
-    int rc = flush_pending(c);
-    if (rc != F2V_OK) return rc;
-    for (hipEvent_t &e : c->lay.ev)
-        if (!e) HIPC(hipEventCreate(&e));
-    return F2V_OK;
+    return settled_enter(c, who);
 }
 
 // The mean (lay.d_mean, D doubles) and the packed upper triangle of the scatter matrix (lay.d_S) of the settled matrix, enqueued on
@@ -4088,10 +4030,9 @@ int pca_moments(f2v_ctx *c) {
     f2v_ctx::Layout &w = c->lay;
     const uint32_t n = c->n, D = c->D, pieces = (n + kPcaPiece - 1) / kPcaPiece, tiles = (D + kPcaTile - 1) / kPcaTile;
     const size_t width = (size_t)D * (D + 1) / 2;
-    int rc;
-    if ((rc = sep_grow(c, w.d_ws, w.cap_ws, (size_t)pieces * width)) != F2V_OK || (rc = sep_grow(c, w.d_mean, w.cap_mean, D)) != F2V_OK ||
-        (rc = sep_grow(c, w.d_S, w.cap_S, width)) != F2V_OK)
-        return rc;
+    F2VC(w.d_ws.reserve(c, (size_t)pieces * width, "layout"));
+    F2VC(w.d_mean.reserve(c, D, "layout"));
+    F2VC(w.d_S.reserve(c, width, "layout"));
     const float *X = c->d_X[c->cur];
     hipLaunchKernelGGL(pca_colsum_kernel, dim3(pieces, (D + 63) / 64), dim3(64), 0, c->stream, X, n, D, w.d_ws);
     hipLaunchKernelGGL(pca_reduce_kernel, dim3((D + 255) / 256), dim3(256), 0, c->stream, (const double *)w.d_ws, pieces, (size_t)D, (double)n, w.d_mean);
@@ -4114,34 +4055,27 @@ int pca_moments_host(f2v_ctx *c, std::vector<double> &mean, std::vector<double> 
     f2v_ctx::Layout &w = c->lay;
     const uint32_t D = c->D;
     const size_t width = (size_t)D * (D + 1) / 2;
-    HIPC(hipEventRecord(w.ev[0], c->stream));
-    int rc = pca_moments(c);
-    if (rc != F2V_OK) return rc;
-    HIPC(hipEventRecord(w.ev[1], c->stream));
+    F2VC(w.timer.start(c->stream));
+    F2VC(pca_moments(c));
+    F2VC(w.timer.stop(c->stream));
     std::vector<double> packed(width);
     mean.resize(D);
     HIPC(hipMemcpyAsync(mean.data(), w.d_mean, (size_t)D * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPC(hipMemcpyAsync(packed.data(), w.d_S, width * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
-    if ((rc = check_kernel_err(c, "f2v_pca")) != F2V_OK) return rc;
+    F2VC(check_kernel_err(c, "f2v_pca"));
     S.resize((size_t)D * D);
     for (uint32_t d = 0; d < D; d++)
         for (uint32_t e = d; e < D; e++) S[(size_t)d * D + e] = S[(size_t)e * D + d] = packed[pca_packed(D, d, e)];
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
-    *seconds = ms * 1e-3;
-    return F2V_OK;
+    *seconds = 0.0;
+    return w.timer.seconds(seconds);
 }
 
 template <int RB>
 int launch_rank_t(f2v_ctx *c, TrustRankArgs a, uint32_t spans) {
     a.blocks = (a.nq + RB - 1) / RB;
-    const size_t lds = trust_lds_bytes(RB, a.k);
-    size_t &set = c->lay.lds_set[RB == 128];
-    if (lds > 65536 && set < lds) {  // a sample block's thresholds and counts live in LDS: up to 114 KB at k = 128
-        HIPC(hipFuncSetAttribute(reinterpret_cast<const void *>(&trust_rank_kernel<RB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        set = lds;
-    }
+    const size_t lds = trust_lds_bytes(RB, a.k);  // a sample block's thresholds and counts live in LDS: up to 114 KB at k = 128
+    F2VC(allow_lds(c, reinterpret_cast<const void *>(&trust_rank_kernel<RB>), lds));
     hipLaunchKernelGGL((trust_rank_kernel<RB>), dim3(spans * a.blocks), dim3(kSepThreads), lds, c->stream, a);
     HIPC(hipGetLastError());
     return F2V_OK;
@@ -4155,13 +4089,12 @@ int f2v_pca(f2v_handle c, uint32_t d2, float *y_out, double *components_out, dou
     if (!c || !info) return fail(F2V_EINVAL, "f2v_pca: null argument");
     if (d2 == 0 || d2 > c->D) return fail(F2V_EINVAL, "f2v_pca: d2 = %u is outside 1..dim = %u", d2, c->D);
     if (c->n < 2) return fail(F2V_EINVAL, "f2v_pca: a graph of %u vertices has no variance", c->n);
-    int rc = lay_enter(c, "f2v_pca");
-    if (rc != F2V_OK) return rc;
+    F2VC(lay_enter(c, "f2v_pca"));
     f2v_ctx::Layout &w = c->lay;
     const uint32_t n = c->n, D = c->D;
     std::vector<double> mean, A, V((size_t)D * D);
     double seconds = 0.0;
-    if ((rc = pca_moments_host(c, mean, A, &seconds)) != F2V_OK) return rc;
+    F2VC(pca_moments_host(c, mean, A, &seconds));
     double trace = 0.0;
     for (uint32_t d = 0; d < D; d++) trace += A[(size_t)d * D + d];
     uint32_t sweeps = 0, converged = 0;
@@ -4186,19 +4119,18 @@ int f2v_pca(f2v_handle c, uint32_t d2, float *y_out, double *components_out, dou
             for (uint32_t d = 0; d < D; d++) W[(size_t)k * D + d] = -W[(size_t)k * D + d];
     }
     if (y_out) {
-        if ((rc = sep_grow(c, w.d_W, w.cap_W, (size_t)d2 * D)) != F2V_OK || (rc = sep_grow(c, w.d_P, w.cap_P, (size_t)n * d2)) != F2V_OK) return rc;
+        F2VC(w.d_W.reserve(c, (size_t)d2 * D, "layout"));
+        F2VC(w.d_P.reserve(c, (size_t)n * d2, "layout"));
         HIPC(hipMemcpyAsync(w.d_W, W.data(), W.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HIPC(hipEventRecord(w.ev[0], c->stream));
+        F2VC(w.timer.start(c->stream));
         hipLaunchKernelGGL(pca_project_kernel, dim3((uint32_t)(((size_t)n * d2 + 255) / 256)), dim3(256), 0, c->stream, (const float *)c->d_X[c->cur],
                            (const double *)w.d_mean, (const double *)w.d_W, n, D, d2, w.d_P);
         HIPC(hipGetLastError());
-        HIPC(hipEventRecord(w.ev[1], c->stream));
+        F2VC(w.timer.stop(c->stream));
         HIPC(hipMemcpyAsync(y_out, w.d_P, (size_t)n * d2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
         HIPC(hipStreamSynchronize(c->stream));
-        if ((rc = check_kernel_err(c, "f2v_pca")) != F2V_OK) return rc;
-        float ms = 0.f;
-        HIPC(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
-        seconds += ms * 1e-3;
+        F2VC(check_kernel_err(c, "f2v_pca"));
+        F2VC(w.timer.seconds(&seconds));
     }
     if (components_out) memcpy(components_out, W.data(), W.size() * sizeof(double));
     if (mean_out) memcpy(mean_out, mean.data(), (size_t)D * sizeof(double));
@@ -4224,15 +4156,18 @@ int f2v_trustworthiness(f2v_handle c, const float *Y, uint32_t d2, uint32_t k, c
         sid[i] = sample_ids ? sample_ids[i] : i;
         if (sid[i] >= n) return fail(F2V_EINVAL, "f2v_trustworthiness: sample %u names vertex %u of %u", i, sid[i], n);
     }
-    int rc = lay_enter(c, "f2v_trustworthiness");
-    if (rc != F2V_OK) return rc;
+    F2VC(lay_enter(c, "f2v_trustworthiness"));
     f2v_ctx::Layout &w = c->lay;
     const uint32_t chunk = std::min(w.chunk, nq), rb = w.block == 128 && k <= 32 ? 128u : 64u;
-    if ((rc = sep_grow(c, w.d_Y, w.cap_Y, (size_t)n * d2)) != F2V_OK || (rc = sep_grow(c, w.d_sid, w.cap_sid, nq)) != F2V_OK ||
-        (rc = sep_grow(c, w.d_nx, w.cap_nx, (size_t)chunk * k)) != F2V_OK || (rc = sep_grow(c, w.d_ny, w.cap_ny, (size_t)chunk * k)) != F2V_OK ||
-        (rc = sep_grow(c, w.d_thr, w.cap_thr, (size_t)chunk * k)) != F2V_OK || (rc = sep_grow(c, w.d_hist, w.cap_hist, (size_t)chunk * k)) != F2V_OK ||
-        (rc = sep_grow(c, w.d_pen, w.cap_pen, 2 * (size_t)nq)) != F2V_OK || (rc = sep_grow(c, w.d_sums, w.cap_sums, 3)) != F2V_OK)
-        return rc;
+    const char *what = "layout";
+    F2VC(w.d_Y.reserve(c, (size_t)n * d2, what));
+    F2VC(w.d_sid.reserve(c, nq, what));
+    F2VC(w.d_nx.reserve(c, (size_t)chunk * k, what));
+    F2VC(w.d_ny.reserve(c, (size_t)chunk * k, what));
+    F2VC(w.d_thr.reserve(c, (size_t)chunk * k, what));
+    F2VC(w.d_hist.reserve(c, (size_t)chunk * k, what));
+    F2VC(w.d_pen.reserve(c, 2 * (size_t)nq, what));
+    F2VC(w.d_sums.reserve(c, 3, what));
     HIPC(hipMemcpyAsync(w.d_Y, Y, (size_t)n * d2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPC(hipMemcpyAsync(w.d_sid, sid.data(), (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIPC(hipMemsetAsync(w.d_sums, 0, 3 * sizeof(unsigned long long), c->stream));
@@ -4242,9 +4177,9 @@ int f2v_trustworthiness(f2v_handle c, const float *Y, uint32_t d2, uint32_t k, c
         const uint32_t cq = std::min(chunk, nq - q0), blocks = (cq + rb - 1) / rb;
         // the k nearest in both spaces, by the nearest-neighbour kernels as they are
         double sec = 0.0;
-        if ((rc = nearest_run_on(c, X, D, sid.data() + q0, false, nullptr, cq, k, F2V_SIM_L2, F2V_NEAREST_EXCLUDE_SELF, nullptr, nullptr, nullptr, &sec, w.d_nx)) != F2V_OK) return rc;
+        F2VC(nearest_run_on(c, X, D, sid.data() + q0, false, nullptr, cq, k, F2V_SIM_L2, F2V_NEAREST_EXCLUDE_SELF, nullptr, nullptr, nullptr, &sec, w.d_nx));
         seconds += sec;
-        if ((rc = nearest_run_on(c, w.d_Y, d2, sid.data() + q0, false, nullptr, cq, k, F2V_SIM_L2, F2V_NEAREST_EXCLUDE_SELF, nullptr, nullptr, nullptr, &sec, w.d_ny)) != F2V_OK) return rc;
+        F2VC(nearest_run_on(c, w.d_Y, d2, sid.data() + q0, false, nullptr, cq, k, F2V_SIM_L2, F2V_NEAREST_EXCLUDE_SELF, nullptr, nullptr, nullptr, &sec, w.d_ny));
         seconds += sec;
         // candidates per workgroup: enough workgroups for every CU a few times over (placement only: the counts add up exactly)
         const uint32_t want = std::max(1u, 2048u / blocks);
@@ -4252,7 +4187,7 @@ int f2v_trustworthiness(f2v_handle c, const float *Y, uint32_t d2, uint32_t k, c
         span = std::min(std::max(span, 256u), kTrustMaxSpan);
         const uint32_t spans = (n + span - 1) / span;
         if ((uint64_t)spans * blocks > 0x7FFFFFFFull) return fail(F2V_EINVAL, "f2v_trustworthiness: too many workgroups per launch: lower \"trust_chunk\"");
-        HIPC(hipEventRecord(w.ev[0], c->stream));
+        F2VC(w.timer.start(c->stream));
         for (int dir = 0; dir < 2; dir++) {  // 0: the layout's neighbours ranked in X (trustworthiness), 1: X's neighbours ranked in Y (continuity)
             TrustKeyArgs ka{};
             ka.M = dir ? w.d_Y : X;
@@ -4277,23 +4212,21 @@ int f2v_trustworthiness(f2v_handle c, const float *Y, uint32_t d2, uint32_t k, c
             ra.nq = cq;
             ra.k = k;
             ra.span = span;
-            if ((rc = rb == 128 ? launch_rank_t<128>(c, ra, spans) : launch_rank_t<64>(c, ra, spans)) != F2V_OK) return rc;
+            F2VC(rb == 128 ? launch_rank_t<128>(c, ra, spans) : launch_rank_t<64>(c, ra, spans));
             hipLaunchKernelGGL(trust_finish_kernel, dim3((cq + 255) / 256), dim3(256), 0, c->stream, (const nn_key_t *)w.d_thr, (const uint32_t *)w.d_hist, cq, k,
                                w.d_pen + (size_t)dir * nq + q0, w.d_sums + dir);
             HIPC(hipGetLastError());
         }
-        HIPC(hipEventRecord(w.ev[1], c->stream));
+        F2VC(w.timer.stop(c->stream));
         HIPC(hipStreamSynchronize(c->stream));
-        float ms = 0.f;
-        HIPC(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
-        seconds += ms * 1e-3;
+        F2VC(w.timer.seconds(&seconds));
     }
     uint64_t sums[3] = {0, 0, 0};
     HIPC(hipMemcpyAsync(sums, w.d_sums, sizeof sums, hipMemcpyDeviceToHost, c->stream));
     if (penalty_x_out) HIPC(hipMemcpyAsync(penalty_x_out, w.d_pen, (size_t)nq * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (penalty_y_out) HIPC(hipMemcpyAsync(penalty_y_out, w.d_pen + nq, (size_t)nq * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
-    if ((rc = check_kernel_err(c, "f2v_trustworthiness")) != F2V_OK) return rc;
+    F2VC(check_kernel_err(c, "f2v_trustworthiness"));
     const double scale = 2.0 / ((double)nq * k * (2.0 * n - 3.0 * k - 1.0));
     out->trustworthiness = 1.0 - (double)sums[0] * scale;
     out->continuity = 1.0 - (double)sums[1] * scale;
@@ -4308,11 +4241,10 @@ int f2v_trustworthiness(f2v_handle c, const float *Y, uint32_t d2, uint32_t k, c
 #ifdef F2V_TEST_HOOKS
 int f2v_test_pca_scatter(f2v_handle c, double *mean_out, double *scatter_out) {
     if (!c || !mean_out || !scatter_out) return fail(F2V_EINVAL, "f2v_test_pca_scatter: null argument");
-    int rc = lay_enter(c, "f2v_test_pca_scatter");
-    if (rc != F2V_OK) return rc;
+    F2VC(lay_enter(c, "f2v_test_pca_scatter"));
     std::vector<double> mean, S;
     double seconds = 0.0;
-    if ((rc = pca_moments_host(c, mean, S, &seconds)) != F2V_OK) return rc;
+    F2VC(pca_moments_host(c, mean, S, &seconds));
     memcpy(mean_out, mean.data(), mean.size() * sizeof(double));
     memcpy(scatter_out, S.data(), S.size() * sizeof(double));
     return F2V_OK;
@@ -4323,13 +4255,12 @@ int f2v_logreg_eval(f2v_handle c, const uint32_t *a_ids, const uint32_t *b_ids, 
                     const double *weights, double lambda, double *loss_out, double *grad_out, double *seconds_out) {
     if (!c || !a_ids || !y || !weights || !loss_out || !grad_out) return fail(F2V_EINVAL, "f2v_logreg_eval: null argument");
     if (!(lambda >= 0.0)) return fail(F2V_EINVAL, "f2v_logreg_eval: lambda must be a non-negative number");
-    int rc = logreg_enter(c, "f2v_logreg_eval", a_ids, b_ids, m, feature, y, classes);
-    if (rc != F2V_OK) return rc;
+    F2VC(logreg_enter(c, "f2v_logreg_eval", a_ids, b_ids, m, feature, y, classes));
     uint32_t cmap[F2V_LOGREG_MAX_CLASSES];
     for (uint32_t k = 0; k < classes; k++) cmap[k] = k;
     double seconds = 0.0;
-    if ((rc = logreg_pass(c, b_ids != nullptr, m, feature, classes, cmap, classes, weights, lambda, loss_out, grad_out, &seconds)) != F2V_OK) return rc;
-    if ((rc = check_kernel_err(c, "f2v_logreg_eval")) != F2V_OK) return rc;
+    F2VC(logreg_pass(c, b_ids != nullptr, m, feature, classes, cmap, classes, weights, lambda, loss_out, grad_out, &seconds));
+    F2VC(check_kernel_err(c, "f2v_logreg_eval"));
     if (seconds_out) *seconds_out = seconds;
     return F2V_OK;
 }
@@ -4339,8 +4270,7 @@ int f2v_logreg_fit(f2v_handle c, const uint32_t *a_ids, const uint32_t *b_ids, u
     if (!c || !a_ids || !y || !weights_out || !info_out) return fail(F2V_EINVAL, "f2v_logreg_fit: null argument");
     if (!(lambda >= 0.0)) return fail(F2V_EINVAL, "f2v_logreg_fit: lambda must be a non-negative number");
     if (!(tol > 0.0)) return fail(F2V_EINVAL, "f2v_logreg_fit: tol must be positive");
-    int rc = logreg_enter(c, "f2v_logreg_fit", a_ids, b_ids, m, feature, y, classes);
-    if (rc != F2V_OK) return rc;
+    F2VC(logreg_enter(c, "f2v_logreg_fit", a_ids, b_ids, m, feature, y, classes));
     const uint32_t D = c->D, P = D + 1;
     const bool pairs = b_ids != nullptr;
     const double stop = tol * (double)m;
@@ -4349,7 +4279,7 @@ int f2v_logreg_fit(f2v_handle c, const uint32_t *a_ids, const uint32_t *b_ids, u
     std::vector<double> W((size_t)classes * P, 0.0), loss(classes), grad((size_t)classes * P);
     double seconds = 0.0;
     for (uint32_t k = 0; k < classes; k++) cmap[k] = k;
-    if ((rc = logreg_pass(c, pairs, m, feature, classes, cmap.data(), classes, W.data(), lambda, loss.data(), grad.data(), &seconds)) != F2V_OK) return rc;
+    F2VC(logreg_pass(c, pairs, m, feature, classes, cmap.data(), classes, W.data(), lambda, loss.data(), grad.data(), &seconds));
     for (uint32_t k = 0; k < classes; k++) {
         LbfgsClass &s = cls[k];
         s.w.assign(P, 0.0);
@@ -4379,7 +4309,7 @@ int f2v_logreg_fit(f2v_handle c, const uint32_t *a_ids, const uint32_t *b_ids, u
             cmap[nc++] = k;
         }
         if (nc == 0) break;
-        if ((rc = logreg_pass(c, pairs, m, feature, classes, cmap.data(), nc, W.data(), lambda, loss.data(), grad.data(), &seconds)) != F2V_OK) return rc;
+        F2VC(logreg_pass(c, pairs, m, feature, classes, cmap.data(), nc, W.data(), lambda, loss.data(), grad.data(), &seconds));
         for (uint32_t i = 0; i < nc; i++) {
             LbfgsClass &s = cls[cmap[i]];
             s.evaluations++;
@@ -4415,7 +4345,7 @@ int f2v_logreg_fit(f2v_handle c, const uint32_t *a_ids, const uint32_t *b_ids, u
             }
         }
     }
-    if ((rc = check_kernel_err(c, "f2v_logreg_fit")) != F2V_OK) return rc;
+    F2VC(check_kernel_err(c, "f2v_logreg_fit"));
     for (uint32_t k = 0; k < classes; k++) {
         const LbfgsClass &s = cls[k];
         std::copy(s.w.begin(), s.w.end(), weights_out + (size_t)k * P);
@@ -4434,10 +4364,9 @@ int f2v_logreg_fit(f2v_handle c, const uint32_t *a_ids, const uint32_t *b_ids, u
 int f2v_logreg_decision(f2v_handle c, const uint32_t *a_ids, const uint32_t *b_ids, uint32_t m, int feature, const double *weights, uint32_t classes,
                         double *z_out, double *seconds_out) {
     if (!c || !a_ids || !weights || !z_out) return fail(F2V_EINVAL, "f2v_logreg_decision: null argument");
-    int rc = logreg_enter(c, "f2v_logreg_decision", a_ids, b_ids, m, feature, nullptr, classes);
-    if (rc != F2V_OK) return rc;
+    F2VC(logreg_enter(c, "f2v_logreg_decision", a_ids, b_ids, m, feature, nullptr, classes));
     f2v_ctx::Logreg &w = c->lr;
-    if ((rc = lr_grow(c, w.d_z, w.cap_z, (size_t)std::min(m, kLrDecisionChunk) * classes)) != F2V_OK) return rc;
+    F2VC(w.d_z.reserve(c, (size_t)std::min(m, kLrDecisionChunk) * classes, "logistic-regression"));
     HIPC(hipMemcpyAsync(w.d_W, weights, (size_t)classes * (c->D + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
     double seconds = 0.0;
     for (uint32_t lo = 0; lo < m; lo += kLrDecisionChunk) {
@@ -4446,16 +4375,14 @@ int f2v_logreg_decision(f2v_handle c, const uint32_t *a_ids, const uint32_t *b_i
         a.a += lo;
         a.b += lo;
         a.out = w.d_z;
-        HIPC(hipEventRecord(w.ev[0], c->stream));
-        if ((rc = launch_logreg(c, a, false)) != F2V_OK) return rc;
-        HIPC(hipEventRecord(w.ev[1], c->stream));
+        F2VC(w.timer.start(c->stream));
+        F2VC(launch_logreg(c, a, false));
+        F2VC(w.timer.stop(c->stream));
         HIPC(hipMemcpyAsync(z_out + (size_t)lo * classes, w.d_z, (size_t)cnt * classes * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPC(hipStreamSynchronize(c->stream));
-        float ms = 0.f;
-        HIPC(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
-        seconds += ms * 1e-3;
+        F2VC(w.timer.seconds(&seconds));
     }
-    if ((rc = check_kernel_err(c, "f2v_logreg_decision")) != F2V_OK) return rc;
+    F2VC(check_kernel_err(c, "f2v_logreg_decision"));
     if (seconds_out) *seconds_out = seconds;
     return F2V_OK;
 }

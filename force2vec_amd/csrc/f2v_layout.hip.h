@@ -266,12 +266,7 @@ __global__ __launch_bounds__(256) void trust_rank_kernel(const TrustRankArgs a) 
     const uint32_t my0 = a.sid[row0 + rp < a.nq ? row0 + rp : a.nq - 1], my1 = a.sid[row0 + rp + HP < a.nq ? row0 + rp + HP : a.nq - 1];
 
     uint32_t xv0[XP], xv1[XP];
-#pragma unroll
-    for (int i = 0; i < XP; i++) {
-        const uint32_t p = (tid + kSepThreads * i) >> 3, r0 = row0 + p, r1 = row0 + p + HP;
-        xv0[i] = a.sid[r0 < a.nq ? r0 : a.nq - 1];
-        xv1[i] = a.sid[r1 < a.nq ? r1 : a.nq - 1];
-    }
+    sep_samples<XP>(a.sid, row0, a.nq, HP, tid, xv0, xv1);
     float4 px0[XP], px1[XP], pc[CP];
     auto load = [&](uint32_t sweep, uint32_t d0) {
 #pragma unroll
@@ -293,34 +288,12 @@ __global__ __launch_bounds__(256) void trust_rank_kernel(const TrustRankArgs a) 
         for (int e = 0; e < (int)kSepAcc; e++) acc[e] = sep_f2{0.f, 0.f};
         for (uint32_t c = 0; c < nch; c++) {
             __syncthreads();  // the previous chunk has been read (and, the first time, the thresholds are in place)
-#pragma unroll
-            for (int i = 0; i < XP; i++) {
-                float *o = Xs + ((tid + kSepThreads * i) >> 3) * kSepXStride + 2 * q4;
-                *reinterpret_cast<float4 *>(o) = make_float4(px0[i].x, px1[i].x, px0[i].y, px1[i].y);
-                *reinterpret_cast<float4 *>(o + 4) = make_float4(px0[i].z, px1[i].z, px0[i].w, px1[i].w);
-            }
-#pragma unroll
-            for (int i = 0; i < CP; i++) *reinterpret_cast<float4 *>(Cs + ((tid + kSepThreads * i) >> 3) * kSepCStride + q4) = pc[i];
+            sep_stage<XP, CP>(Xs, Cs, px0, px1, pc, tid, q4);
             __syncthreads();
             // the next chunk (or the next sweep's first) travels while this one is scored
             if (c + 1 < nch) load(s, (c + 1) * kSepChunk);
             else if (s + 1 < nsw) load(s + 1, 0);
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const float4 xa = *reinterpret_cast<const float4 *>(Xs + rp * kSepXStride + 8 * j);
-                const float4 xb = *reinterpret_cast<const float4 *>(Xs + rp * kSepXStride + 8 * j + 4);
-                const sep_f2 x0 = {xa.x, xa.y}, x1 = {xa.z, xa.w}, x2 = {xb.x, xb.y}, x3 = {xb.z, xb.w};
-#pragma unroll
-                for (int e = 0; e < (int)kSepAcc; e++) {
-                    const float4 cc = *reinterpret_cast<const float4 *>(Cs + (g + G * e) * kSepCStride + 4 * j);
-                    sep_f2 t, u = acc[e];
-                    t = x0 - cc.x; u = __builtin_elementwise_fma(t, t, u);
-                    t = x1 - cc.y; u = __builtin_elementwise_fma(t, t, u);
-                    t = x2 - cc.z; u = __builtin_elementwise_fma(t, t, u);
-                    t = x3 - cc.w; u = __builtin_elementwise_fma(t, t, u);
-                    acc[e] = u;
-                }
-            }
+            sep_score<G>(Xs, Cs, rp, g, acc);
         }
         // compare and count: the farthest threshold first (most candidates are farther than every target and end here)
         const nn_key_t lim0 = thr[(size_t)rp * a.k + a.k - 1], lim1 = thr[(size_t)(rp + HP) * a.k + a.k - 1];

@@ -60,6 +60,51 @@ __device__ inline float4 sep_load4(const float *X, uint32_t D, uint32_t v, uint3
     return make_float4(e[0], e[1], e[2], e[3]);
 }
 
+// What separation_pair_kernel and trust_rank_kernel (f2v_layout.hip.h) share: the sample block's vertex ids, a chunk's way from the
+// registers into LDS, and the scoring of the staged chunk.  Thread `tid` loads rows (tid + 256 i) / 8 at dimensions q4 .. q4 + 3.
+template <int XP>
+__device__ __forceinline__ void sep_samples(const uint32_t *sid, uint32_t row0, uint32_t nq, uint32_t hp, uint32_t tid, uint32_t (&xv0)[XP], uint32_t (&xv1)[XP]) {
+#pragma unroll
+    for (int i = 0; i < XP; i++) {
+        const uint32_t p = (tid + kSepThreads * i) >> 3, r0 = row0 + p, r1 = row0 + p + hp;
+        xv0[i] = sid[r0 < nq ? r0 : nq - 1];
+        xv1[i] = sid[r1 < nq ? r1 : nq - 1];
+    }
+}
+
+template <int XP, int CP>
+__device__ __forceinline__ void sep_stage(float *Xs, float *Cs, const float4 (&px0)[XP], const float4 (&px1)[XP], const float4 (&pc)[CP], uint32_t tid, uint32_t q4) {
+#pragma unroll
+    for (int i = 0; i < XP; i++) {
+        float *o = Xs + ((tid + kSepThreads * i) >> 3) * kSepXStride + 2 * q4;
+        *reinterpret_cast<float4 *>(o) = make_float4(px0[i].x, px1[i].x, px0[i].y, px1[i].y);
+        *reinterpret_cast<float4 *>(o + 4) = make_float4(px0[i].z, px1[i].z, px0[i].w, px1[i].w);
+    }
+#pragma unroll
+    for (int i = 0; i < CP; i++) *reinterpret_cast<float4 *>(Cs + ((tid + kSepThreads * i) >> 3) * kSepCStride + q4) = pc[i];
+}
+
+// acc[e] += the squared differences, over the staged chunk, of the lane's two rows (pair rp) and candidate g + G e of the sweep
+template <uint32_t G>
+__device__ __forceinline__ void sep_score(const float *Xs, const float *Cs, uint32_t rp, uint32_t g, sep_f2 (&acc)[kSepAcc]) {
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const float4 xa = *reinterpret_cast<const float4 *>(Xs + rp * kSepXStride + 8 * j);
+        const float4 xb = *reinterpret_cast<const float4 *>(Xs + rp * kSepXStride + 8 * j + 4);
+        const sep_f2 x0 = {xa.x, xa.y}, x1 = {xa.z, xa.w}, x2 = {xb.x, xb.y}, x3 = {xb.z, xb.w};
+#pragma unroll
+        for (int e = 0; e < (int)kSepAcc; e++) {
+            const float4 cc = *reinterpret_cast<const float4 *>(Cs + (g + G * e) * kSepCStride + 4 * j);
+            sep_f2 t, u = acc[e];
+            t = x0 - cc.x; u = __builtin_elementwise_fma(t, t, u);
+            t = x1 - cc.y; u = __builtin_elementwise_fma(t, t, u);
+            t = x2 - cc.z; u = __builtin_elementwise_fma(t, t, u);
+            t = x3 - cc.w; u = __builtin_elementwise_fma(t, t, u);
+            acc[e] = u;
+        }
+    }
+}
+
 struct SepPairArgs {
     const float *X;              // n x D, the settled matrix
     const uint32_t *order;       // the labelled vertices in cluster order, ascending id inside a cluster
@@ -90,12 +135,7 @@ __global__ __launch_bounds__(256) void separation_pair_kernel(const SepPairArgs 
     const uint32_t q4 = 4 * (tid & 7u);
 
     uint32_t xv0[XP], xv1[XP], cv[CP], cvn[CP];
-#pragma unroll
-    for (int i = 0; i < XP; i++) {
-        const uint32_t p = (tid + kSepThreads * i) >> 3, r0 = row0 + p, r1 = row0 + p + HP;
-        xv0[i] = a.sid[r0 < a.nq ? r0 : a.nq - 1];
-        xv1[i] = a.sid[r1 < a.nq ? r1 : a.nq - 1];
-    }
+    sep_samples<XP>(a.sid, row0, a.nq, HP, tid, xv0, xv1);
     auto members = [&](uint32_t (&v)[CP], uint32_t sweep) {
 #pragma unroll
         for (int i = 0; i < CP; i++) {
@@ -126,34 +166,12 @@ __global__ __launch_bounds__(256) void separation_pair_kernel(const SepPairArgs 
         members(cvn, s + 1 < nsw ? s + 1 : s);  // the next sweep's ids travel while this one is scored
         for (uint32_t c = 0; c < nch; c++) {
             __syncthreads();  // the previous chunk has been read
-#pragma unroll
-            for (int i = 0; i < XP; i++) {
-                float *o = Xs + ((tid + kSepThreads * i) >> 3) * kSepXStride + 2 * q4;
-                *reinterpret_cast<float4 *>(o) = make_float4(px0[i].x, px1[i].x, px0[i].y, px1[i].y);
-                *reinterpret_cast<float4 *>(o + 4) = make_float4(px0[i].z, px1[i].z, px0[i].w, px1[i].w);
-            }
-#pragma unroll
-            for (int i = 0; i < CP; i++) *reinterpret_cast<float4 *>(Cs + ((tid + kSepThreads * i) >> 3) * kSepCStride + q4) = pc[i];
+            sep_stage<XP, CP>(Xs, Cs, px0, px1, pc, tid, q4);
             __syncthreads();
             // the next chunk (or the next sweep's first) travels while this one is scored
             if (c + 1 < nch) load(cv, (c + 1) * kSepChunk);
             else if (s + 1 < nsw) load(cvn, 0);
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const float4 xa = *reinterpret_cast<const float4 *>(Xs + rp * kSepXStride + 8 * j);
-                const float4 xb = *reinterpret_cast<const float4 *>(Xs + rp * kSepXStride + 8 * j + 4);
-                const sep_f2 x0 = {xa.x, xa.y}, x1 = {xa.z, xa.w}, x2 = {xb.x, xb.y}, x3 = {xb.z, xb.w};
-#pragma unroll
-                for (int e = 0; e < (int)kSepAcc; e++) {
-                    const float4 cc = *reinterpret_cast<const float4 *>(Cs + (g + G * e) * kSepCStride + 4 * j);
-                    sep_f2 t, u = acc[e];
-                    t = x0 - cc.x; u = __builtin_elementwise_fma(t, t, u);
-                    t = x1 - cc.y; u = __builtin_elementwise_fma(t, t, u);
-                    t = x2 - cc.z; u = __builtin_elementwise_fma(t, t, u);
-                    t = x3 - cc.w; u = __builtin_elementwise_fma(t, t, u);
-                    acc[e] = u;
-                }
-            }
+            sep_score<G>(Xs, Cs, rp, g, acc);
         }
         const uint32_t in_piece = (s * SW) % kSepPiece;  // the sweep's first place in its piece
 #pragma unroll
