@@ -266,12 +266,13 @@ struct f2v_ctx {
     bool plan_overflow = false;  // a launch plan needed more than 2^28 partial-sum slots (kItemSlotMask)
     uint32_t *h_kerr = nullptr;  // pinned: the kernel error words as of the last completed epoch-end copy (train_impl)
 #ifdef F2V_TEST_HOOKS
-    uint32_t test_withhold_slot = kNoSlot, test_withhold_row = kNoSlot;
-    uint32_t test_chain_mode = 0;  // f2v_test_chain_nowait's argument as given (bit 0 = the old on/off)
-    bool test_chain_nowait = false;  // timing experiment: chained launches without their row waits (results are then wrong)
-    unsigned long long *d_xcd = nullptr;     // f2v_test_xcd_times (StepArgs::xcd_times)
-    unsigned long long *d_stamps = nullptr;  // f2v_test_stamps: 4 wall-clock words per row (StepArgs::stamps)
-    uint32_t test_stub = 0;                  // f2v_test_interaction_stub (StepArgs::test_stub)
+    struct Hooks {  // what include/f2v_test.h switches on (fill_hooks hands it to the launches)
+        uint32_t withhold_slot = kNoSlot, withhold_row = kNoSlot;  // f2v_test_withhold_flag, f2v_test_withhold_row
+        uint32_t chain_mode = 0;                 // f2v_test_chain_nowait's argument as given: bit 0 -- chained launches without their row waits (results are then wrong)
+        unsigned long long *d_xcd = nullptr;     // f2v_test_xcd_times (StepArgs::xcd_times)
+        unsigned long long *d_stamps = nullptr;  // f2v_test_stamps: 4 wall-clock words per row (StepArgs::stamps)
+        uint32_t stub = 0;                       // f2v_test_interaction_stub (StepArgs::test_stub)
+    } hooks;
 #endif
     bool merge_fin = true, capturing = false;  // all combine-tree levels in one launch (not while a hipGraph is captured)
     int cur = 0;  // d_X[cur]: current matrix; d_X[cur^1]: receives the rows updated this epoch
@@ -1661,11 +1662,26 @@ void arm_waits(f2v_ctx *c, StepArgs &a, bool chained) {
     a.err = c->d_kerr;
     a.timeout_ticks = chained ? ms_to_ticks(std::min(c->tree_timeout_ms, c->chain_timeout_ms)) : tree_timeout_ticks(c);
     a.seq = next_launch_seq(c);
-#ifdef F2V_TEST_HOOKS
-    a.test_withhold_slot = c->test_withhold_slot;
-    a.test_withhold_row = chained ? c->test_withhold_row : kNoSlot;  // (chained launches only)
-#endif
 }
+
+// The self-test build's hook fields of a launch (include/f2v_test.h).  Row waits switched off: the wide form reads the mode's bits,
+// the chain form is told that no row was "written by an earlier minibatch" (chain_lo = 0xFFFFFFFF).
+#ifdef F2V_TEST_HOOKS
+void fill_hooks(const f2v_ctx *c, StepArgs &a, bool chained, bool wide) {
+    const f2v_ctx::Hooks &h = c->hooks;
+    a.test_withhold_slot = h.withhold_slot;
+    a.test_withhold_row = chained ? h.withhold_row : kNoSlot;
+    a.stamps = chained ? h.d_stamps : nullptr;
+    a.xcd_times = chained ? nullptr : h.d_xcd;
+    a.test_stub = chained ? 0u : h.stub;
+    a.test_nowait = wide ? h.chain_mode : 0u;
+    if (chained && !wide && (h.chain_mode & 1u)) a.chain_lo = 0xFFFFFFFFu;
+}
+bool hooks_forbid_ring(const f2v_ctx *c) { return c->hooks.d_stamps || c->hooks.chain_mode; }  // (they look at one epoch per launch)
+#else
+void fill_hooks(const f2v_ctx *, StepArgs &, bool, bool) {}
+bool hooks_forbid_ring(const f2v_ctx *) { return false; }
+#endif
 
 // Record a launch over rows [lo, hi) that computed `rows` rows against `samples` negative samples, `epochs` times over: the
 // statistics and -- unless nothing is left pending (the ring of the wide form) -- the updated range, with [p_lo, hi) the last minibatch
@@ -1721,10 +1737,7 @@ int launch_step(f2v_ctx *c, int math, uint32_t batch_lo, uint32_t batch_hi, uint
     a.batch_lo = batch_lo;
     a.n_items = plan.n_items;
     a.upd_rows = c->upd_hi - c->upd_lo;
-#ifdef F2V_TEST_HOOKS
-    a.xcd_times = c->d_xcd;
-    a.test_stub = c->test_stub;
-#endif
+    fill_hooks(c, a, false, false);
     push = push && c->push.attached && c->push.world > 1;
     if (push) fill_targets(c, a.push, c->cur ^ 1, batch_lo, push_masks);
 
@@ -1802,9 +1815,7 @@ void fill_chain_args(f2v_ctx *c, StepArgs &a, int math, const P &plan, uint32_t 
     arm_waits(c, a, true);
     a.rowflag = c->d_rowflag;
     a.chain_lo = plan.lo;
-#ifdef F2V_TEST_HOOKS
-    a.stamps = c->d_stamps;
-#endif
+    fill_hooks(c, a, true, std::is_same<P, WidePlan>::value);
 }
 
 // One chained launch: minibatches [plan.first_batch, +plan.n_batches) of an epoch whose sample ids (ids_stride per minibatch)
@@ -1814,9 +1825,6 @@ int launch_chain(f2v_ctx *c, int math, const ChainPlan &plan, const uint32_t *d_
     if ((rc = flush_unless_continued(c, plan.lo)) != F2V_OK) return rc;
     ChainArgs ca{};
     fill_chain_args(c, ca.base, math, plan, ns, lr, bs_mode);
-#ifdef F2V_TEST_HOOKS
-    if (c->test_chain_nowait) ca.base.chain_lo = 0xFFFFFFFFu;  // the kernel then treats no row as "written by an earlier minibatch"
-#endif
     ca.wg = c->d_wg + plan.wg_off;
     ca.ids = d_ids_epoch;
     ca.ids_stride = ids_stride;
@@ -1898,9 +1906,6 @@ int launch_wide(f2v_ctx *c, int math, const WidePlan &plan, const uint32_t *d_id
         wa.ring_stride = matrix;
         wa.ids_epoch_stride = ids_epoch_stride;
     }
-#ifdef F2V_TEST_HOOKS
-    a.test_nowait = c->test_chain_mode;
-#endif
     wa.wg = c->d_wide + plan.wg_off;
     wa.jobs = c->d_jobs + plan.job_off;
     wa.ids = d_ids_epoch;
@@ -2322,8 +2327,8 @@ int f2v_create(const uint32_t *rowptr, const uint32_t *colids, uint32_t n, uint6
     }
     if (const char *e = getenv("F2V_RECOVER")) c->recover = atoi(e) != 0;  // default of "recover" for new handles
 #ifdef F2V_TEST_HOOKS
-    if (const char *e = getenv("F2V_TEST_WITHHOLD_SLOT")) c->test_withhold_slot = (uint32_t)strtoul(e, nullptr, 0);  // f2v_test_withhold_flag from outside
-    if (const char *e = getenv("F2V_TEST_WITHHOLD_ROW")) c->test_withhold_row = (uint32_t)strtoul(e, nullptr, 0);
+    if (const char *e = getenv("F2V_TEST_WITHHOLD_SLOT")) c->hooks.withhold_slot = (uint32_t)strtoul(e, nullptr, 0);  // f2v_test_withhold_flag from outside
+    if (const char *e = getenv("F2V_TEST_WITHHOLD_ROW")) c->hooks.withhold_row = (uint32_t)strtoul(e, nullptr, 0);
 #endif
     {
         // Dispatch probe: the one-launch minibatch (combine-tree nodes waiting inside the step kernel's grid) counts on
@@ -2364,8 +2369,8 @@ int f2v_destroy(f2v_handle c) {
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
 #ifdef F2V_TEST_HOOKS
-    if (c->d_stamps) (void)hipFree(c->d_stamps);
-    if (c->d_xcd) (void)hipFree(c->d_xcd);
+    for (void *p : {(void *)c->hooks.d_stamps, (void *)c->hooks.d_xcd})
+        if (p) (void)hipFree(p);
 #endif
     if (c->h_kerr) (void)hipHostFree(c->h_kerr);
     for (hipEvent_t e : c->ev_snap)
@@ -2865,11 +2870,7 @@ int train_impl(f2v_ctx *c, int option, uint32_t iters, uint32_t batch, uint32_t 
     const bool wide = chained && wide_usable(c) && batch <= c->wide_max_batch && (chain_len(c, batch, true) >= 2 || c->wide_single);
     const uint32_t K = chained ? chain_len(c, batch, wide) : 1;
     uint32_t epochs_max = 1;  // "wide_epochs"
-    if (wide && all_upfront && math != 7 && !bs_mode && ns <= 8 && !c->mark_every
-#ifdef F2V_TEST_HOOKS
-        && !c->d_stamps && !c->test_chain_mode
-#endif
-    ) {
+    if (wide && all_upfront && math != 7 && !bs_mode && ns <= 8 && !c->mark_every && !hooks_forbid_ring(c)) {
         epochs_max = c->wide_epochs ? c->wide_epochs : (c->nnz <= (2ull << 20) ? 32u : 1u);
         epochs_max = (uint32_t)std::min<uint64_t>(epochs_max, (8ull << 30) / std::max<uint64_t>((uint64_t)n * c->D * sizeof(float), 1));  // the ring stays below 8 GiB
         if (2ull * n * c->D * sizeof(float) > 0xFFFFFFFFull) epochs_max = 1;  // an epoch's two matrices of the ring are read at 32-bit byte offsets (load16_agent)
@@ -4577,26 +4578,25 @@ int f2v_push_attach(f2v_handle c, uint32_t rank, uint32_t world, const void *all
 #ifdef F2V_TEST_HOOKS
 int f2v_test_withhold_flag(f2v_handle c, uint32_t slot) {
     if (!c) return fail(F2V_EINVAL, "null handle");
-    c->test_withhold_slot = slot;
+    c->hooks.withhold_slot = slot;
     return F2V_OK;
 }
 
 int f2v_test_withhold_row(f2v_handle c, uint32_t row) {
     if (!c) return fail(F2V_EINVAL, "null handle");
-    c->test_withhold_row = row;
+    c->hooks.withhold_row = row;
     return F2V_OK;
 }
 
 int f2v_test_chain_nowait(f2v_handle c, int on) {
     if (!c) return fail(F2V_EINVAL, "null handle");
-    c->test_chain_nowait = (on & 1) != 0;
-    c->test_chain_mode = (uint32_t)on;
+    c->hooks.chain_mode = (uint32_t)on;
     return F2V_OK;
 }
 
 int f2v_test_interaction_stub(f2v_handle c, uint32_t mode) {
     if (!c) return fail(F2V_EINVAL, "null handle");
-    c->test_stub = mode & 3u;
+    c->hooks.stub = mode & 3u;
     return F2V_OK;
 }
 
@@ -4784,16 +4784,16 @@ int f2v_test_stamps(f2v_handle c, int on, unsigned long long *out) {
     HIPC(hipStreamSynchronize(c->stream));
     const size_t bytes = 4 * (size_t)c->n * sizeof(unsigned long long);
     if (out) {
-        if (!c->d_stamps) return fail(F2V_ESTATE, "f2v_test_stamps: not switched on");
-        HIPC(hipMemcpy(out, c->d_stamps, bytes, hipMemcpyDeviceToHost));
+        if (!c->hooks.d_stamps) return fail(F2V_ESTATE, "f2v_test_stamps: not switched on");
+        HIPC(hipMemcpy(out, c->hooks.d_stamps, bytes, hipMemcpyDeviceToHost));
     }
     if (on) {
-        if (!c->d_stamps) HIPC(hipMalloc((void **)&c->d_stamps, bytes));
-        HIPC(hipMemsetAsync(c->d_stamps, 0, bytes, c->stream));
+        if (!c->hooks.d_stamps) HIPC(hipMalloc((void **)&c->hooks.d_stamps, bytes));
+        HIPC(hipMemsetAsync(c->hooks.d_stamps, 0, bytes, c->stream));
         HIPC(hipStreamSynchronize(c->stream));
-    } else if (c->d_stamps) {
-        (void)hipFree(c->d_stamps);
-        c->d_stamps = nullptr;
+    } else if (c->hooks.d_stamps) {
+        (void)hipFree(c->hooks.d_stamps);
+        c->hooks.d_stamps = nullptr;
     }
     return F2V_OK;
 }
@@ -4906,15 +4906,15 @@ int f2v_test_xcd_times(f2v_handle c, int on, unsigned long long *out) {
     if (!c) return fail(F2V_EINVAL, "null handle");
     HIPC(hipSetDevice(c->device));
     HIPC(hipStreamSynchronize(c->stream));
-    if (out && c->d_xcd) HIPC(hipMemcpy(out, c->d_xcd, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (out && c->hooks.d_xcd) HIPC(hipMemcpy(out, c->hooks.d_xcd, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     if (on) {
-        if (!c->d_xcd) HIPC(hipMalloc((void **)&c->d_xcd, 32 * sizeof(unsigned long long)));
+        if (!c->hooks.d_xcd) HIPC(hipMalloc((void **)&c->hooks.d_xcd, 32 * sizeof(unsigned long long)));
         unsigned long long init[32];
         for (int k = 0; k < 32; k++) init[k] = (k >= 8 && k < 16) ? ~0ull : 0ull;
-        HIPC(hipMemcpy(c->d_xcd, init, sizeof init, hipMemcpyHostToDevice));
-    } else if (c->d_xcd) {
-        (void)hipFree(c->d_xcd);
-        c->d_xcd = nullptr;
+        HIPC(hipMemcpy(c->hooks.d_xcd, init, sizeof init, hipMemcpyHostToDevice));
+    } else if (c->hooks.d_xcd) {
+        (void)hipFree(c->hooks.d_xcd);
+        c->hooks.d_xcd = nullptr;
     }
     return F2V_OK;
 }

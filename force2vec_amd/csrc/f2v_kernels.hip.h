@@ -142,6 +142,84 @@ struct FinalizeArgs {
     PushTargets push;
 };
 
+// ---- the self-test build's hooks ----------------------------------------------------------------------------
+// Everything the kernels below do for include/f2v_test.h, in one place: the product build's versions are empty or a constant false,
+// so a site reads `if (hook_...(a, ...))` and compiles to what it would be without the line.  `A` is StepArgs or FinalizeTreeArgs:
+// they carry the hook fields under the same names.
+enum : uint32_t { kStampPiece = 0, kStampNode = 1, kStampRow = 2, kStampSeen = 3, kStampNone = 4 };  // the words of StepArgs::stamps
+struct FinalizeTreeArgs;
+#ifdef F2V_TEST_HOOKS
+template <class A> __device__ __forceinline__ bool hook_row_withheld(const A &a, uint32_t row) { return row == a.test_withhold_row; }
+template <class A> __device__ __forceinline__ bool hook_slot_withheld(const A &a, uint32_t slot) { return slot == a.test_withhold_slot; }
+__device__ __forceinline__ bool hook_slot_withheld(const FinalizeTreeArgs &, uint32_t) { return false; }  // (pieces and wide jobs only)
+template <class A> __device__ __forceinline__ void hook_stamp(const A &a, uint32_t row, uint32_t word) {
+    if (a.stamps && word < kStampNone) a.stamps[4 * (size_t)row + word] = wall_clock64();
+}
+template <class A> __device__ __forceinline__ void hook_stamp_max(const A &a, uint32_t row, uint32_t word) {
+    if (a.stamps && word < kStampNone) atomicMax(a.stamps + 4 * (size_t)row + word, word == kStampSeen ? ~wall_clock64() : wall_clock64());
+}
+template <class A> __device__ __forceinline__ bool hook_nowait(const A &a, uint32_t bits) { return (a.test_nowait & bits) != 0u; }
+template <class A> __device__ __forceinline__ bool hook_nowait_chain(const A &a) { return a.chain_lo == 0xFFFFFFFFu; }  // (the chain form's convention)
+template <class A> __device__ __forceinline__ bool hook_stub(const A &a, uint32_t bits) { return (a.test_stub & bits) != 0u; }
+// f2v_test_interaction_stub: a gathered row costs one add per register (results WRONG; what is left is the kernel's memory side and frame)
+template <int NB>
+__device__ __forceinline__ void stub_update_q(const float4 (&xj4)[NB], float (&Y)[NB][4]) {
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        Y[b][0] = Y[b][0] + xj4[b].x; Y[b][1] = Y[b][1] + xj4[b].y; Y[b][2] = Y[b][2] + xj4[b].z; Y[b][3] = Y[b][3] + xj4[b].w;
+    }
+}
+// f2v_test_xcd_times: a workgroup's start, and at its end the words of its XCD
+template <class A> __device__ __forceinline__ unsigned long long hook_xcd_begin(const A &a) { return a.xcd_times ? wall_clock64() : 0ull; }
+template <class A> __device__ __forceinline__ void hook_xcd_end(const A &a, unsigned long long t0) {
+    if (a.xcd_times && threadIdx.x == 0u) {
+        uint32_t id;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(id));
+        const unsigned long long t1 = wall_clock64();
+        atomicMax(a.xcd_times + (id & 7u), t1);
+        atomicMin(a.xcd_times + 8u + (id & 7u), t0);
+        atomicAdd(a.xcd_times + 16u + (id & 7u), t1 - t0);
+        atomicAdd(a.xcd_times + 24u + (id & 7u), 1ull);
+    }
+}
+template <class T, class A> __device__ __forceinline__ void hook_copy(T &to, const A &a) {
+    to.stamps = a.stamps;
+    to.test_withhold_row = a.test_withhold_row;
+}
+#else
+template <class A> __device__ __forceinline__ constexpr bool hook_row_withheld(const A &, uint32_t) { return false; }
+template <class A> __device__ __forceinline__ constexpr bool hook_slot_withheld(const A &, uint32_t) { return false; }
+template <class A> __device__ __forceinline__ void hook_stamp(const A &, uint32_t, uint32_t) {}
+template <class A> __device__ __forceinline__ void hook_stamp_max(const A &, uint32_t, uint32_t) {}
+template <class A> __device__ __forceinline__ constexpr bool hook_nowait(const A &, uint32_t) { return false; }
+template <class A> __device__ __forceinline__ constexpr bool hook_nowait_chain(const A &) { return false; }
+template <class A> __device__ __forceinline__ constexpr bool hook_stub(const A &, uint32_t) { return false; }
+template <int NB> __device__ __forceinline__ void stub_update_q(const float4 (&)[NB], float (&)[NB][4]) {}
+template <class A> __device__ __forceinline__ constexpr unsigned long long hook_xcd_begin(const A &) { return 0ull; }
+template <class A> __device__ __forceinline__ void hook_xcd_end(const A &, unsigned long long) {}
+template <class T, class A> __device__ __forceinline__ void hook_copy(T &, const A &) {}
+#endif
+
+// ---- the in-grid hand-off: the announce ------------------------------------------------------------------------
+// ACKNOWLEDGED BEFORE ANNOUNCED.  A producer stores its bytes written through (sc1), waits until they have been acknowledged
+// (s_waitcnt(0); where several wavefronts stored, a barrier behind it) and only then lets ONE lane announce them: a relaxed
+// agent-scope store of the launch's sequence number into the row's flag or the partial-sum slot's.  What precedes the announce and
+// which lane makes it is the caller's; the store, the fault injection that withholds it and the time stamps are here.
+// (The readers' bounded waits -- finalize_tree_node, wait_row_slow, the wide form's kJobImport -- keep a loop each: through one shared
+// function the chained kernels' register counts moved, and with wait_row_slow left out the wide form still measured 0.3 % slower:
+// profiles/sync_helpers_refactor.txt.)
+template <class A>
+__device__ __forceinline__ void announce_row(const A &a, uint32_t row) {
+    if (!hook_row_withheld(a, row)) __hip_atomic_store(a.rowflag + row, a.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    hook_stamp(a, row, kStampRow);
+}
+// (`row`, `word`: whose stamp the announcement is -- an inner tree node's or a wide job's sum, or a hub piece's)
+template <class A>
+__device__ __forceinline__ void announce_slot(const A &a, uint32_t slot, uint32_t row, uint32_t word = kStampNode) {
+    if (!hook_slot_withheld(a, slot)) __hip_atomic_store(a.ready + slot, a.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    hook_stamp_max(a, row, word);
+}
+
 // ---- cross-lane primitives -------------------------------------------------------------------
 template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float v) {
@@ -621,13 +699,7 @@ __device__ __forceinline__ void finalize_tree_node(const FinalizeTreeArgs &a, ui
         if constexpr (ROW_THROUGH) {
             store_row_agent<VEC, EXACT>(f.Xn + (size_t)h.row * D, lane, D, Y);
             __builtin_amdgcn_s_waitcnt(0);  // the row is in memory before it is announced
-#ifdef F2V_TEST_HOOKS
-            if (h.row == a.test_withhold_row) return;  // fault injection: this row is never announced
-#endif
-            if (lane == 0) __hip_atomic_store(a.rowflag + h.row, a.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifdef F2V_TEST_HOOKS
-            if (a.stamps && lane == 0) a.stamps[4 * (size_t)h.row + 2] = wall_clock64();
-#endif
+            if (lane == 0 && !hook_row_withheld(a, h.row)) announce_row(a, h.row);  // (a withheld root is not stamped either)
         } else {
             store_row<VEC, EXACT>(f.Xn + (size_t)h.row * D, lane, D, Y);
         }
@@ -638,11 +710,18 @@ __device__ __forceinline__ void finalize_tree_node(const FinalizeTreeArgs &a, ui
     } else {
         store_row_agent<VEC, EXACT>(f.partials + (size_t)h.out * D, lane, D, Y);
         __builtin_amdgcn_s_waitcnt(0);  // the sum is in memory before it is announced
-        if (lane == 0) __hip_atomic_store(a.ready + h.out, a.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifdef F2V_TEST_HOOKS
-        if (a.stamps && lane == 0) atomicMax(a.stamps + 4 * (size_t)h.row + 1, wall_clock64());
-#endif
+        if (lane == 0) announce_slot(a, h.out, h.row);
     }
+}
+
+// the trees that ride in a step launch's own grid (`n` nodes at `items`): every node adds sums of this launch
+__device__ __forceinline__ FinalizeTreeArgs tree_args_in_grid(const StepArgs &a, const FinItem *items, uint32_t n, uint32_t D) {
+    FinalizeTreeArgs ft;
+    ft.f.X = a.X; ft.f.partials = a.partials; ft.f.Xn = a.Xn; ft.f.items = items; ft.f.n_items = n; ft.f.D = D;
+    ft.f.push = a.push;
+    ft.ready = a.ready; ft.err = a.err; ft.timeout_ticks = a.timeout_ticks; ft.seq = a.seq; ft.first_dep = 0u; ft.rowflag = a.rowflag;
+    hook_copy(ft, a);
+    return ft;
 }
 
 template <int OPT, int VEC, bool EXACT>
@@ -878,17 +957,6 @@ __device__ __forceinline__ void lds_samples5_q(const float4 (*smp)[LPI * NB], ui
     }
 }
 
-#ifdef F2V_TEST_HOOKS
-// f2v_test_interaction_stub: a gathered row costs one add per register (results WRONG; what is left is the kernel's memory side and frame)
-template <int NB>
-__device__ __forceinline__ void stub_update_q(const float4 (&xj4)[NB], float (&Y)[NB][4]) {
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        Y[b][0] = Y[b][0] + xj4[b].x; Y[b][1] = Y[b][1] + xj4[b].y; Y[b][2] = Y[b][2] + xj4[b].z; Y[b][3] = Y[b][3] + xj4[b].w;
-    }
-}
-#endif
-
 // Chained minibatches: row j is written by an earlier minibatch of this launch -- wait until it has been announced
 // (rowflag[j] == seq, stored by its writer after the written-through row was acknowledged).  -> true: gave up (time-out, or
 // the launch is lost already); the caller then stores nothing.
@@ -900,9 +968,7 @@ __device__ __forceinline__ bool wait_row_slow(const StepArgs &a, const uint32_t 
     for (uint32_t spins = 1;; ++spins) {
         __builtin_amdgcn_s_sleep(1);
         if (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.seq) {
-#ifdef F2V_TEST_HOOKS
-            if (a.stamps) atomicMax(a.stamps + 4 * (size_t)j + 3, ~wall_clock64());
-#endif
+            hook_stamp_max(a, j, kStampSeen);
             return false;
         }
         if ((spins & 15u) != 0u) continue;
@@ -1017,14 +1083,12 @@ __device__ __forceinline__ void qprocess(const StepArgs &a, const HandSrc &hs, c
             // (keeps every load above the predicated interactions: left free, the compiler sinks row 0's loads into the first one's
             // block, behind the others, and waits vmcnt(0) there -- for the next ids too)
             asm volatile("" ::: "memory");
-#ifdef F2V_TEST_HOOKS
-            if (a.test_stub & 1u) {
+            if (hook_stub(a, 1u)) {
 #pragma unroll
                 for (int u = 0; u < U; ++u)
                     if (g + u < cnt) stub_update_q<NB>(xj[u], Y);
                 continue;
             }
-#endif
             if constexpr (OPT == 5 && !NEG && NB * U <= 8) {
                 // four rows at a time (a quad of lanes evaluates their coefficients; U = 8: two rounds -- all eight at once are a dozen
                 // registers more, a wave per SIMD): the rows' sums first, each row consumed under its own counted wait as it arrives --
@@ -1163,9 +1227,7 @@ __device__ __forceinline__ void qprocess_pre(const StepArgs &a, const HandSrc &h
 #pragma unroll
                     for (int b = 0; b < NB; ++b) {
                         if (!(FULL || 4u * LPI * b + 4u * t < D)) xj[u][b] = make_float4(0.f, 0.f, 0.f, 0.f);
-#ifdef F2V_TEST_HOOKS
-                        else if (a.test_nowait & 4u) xj[u][b] = *reinterpret_cast<const float4 *>((inr[u] ? a.Xn : a.X) + (size_t)j0[u] * D + t * 4 + 4 * LPI * b);
-#endif
+                        else if (hook_nowait(a, 4u)) xj[u][b] = *reinterpret_cast<const float4 *>((inr[u] ? a.Xn : a.X) + (size_t)j0[u] * D + t * 4 + 4 * LPI * b);
                         else xj[u][b] = load16_agent(hs.r, off + 16u * LPI * b);
                     }
                     handed[u] = false;
@@ -1216,9 +1278,7 @@ __device__ __forceinline__ void qprocess_pre(const StepArgs &a, const HandSrc &h
 #pragma unroll
                 for (int b = 0; b < NB; ++b) {
                     if (!(FULL || 4u * LPI * b + 4u * t < D)) xj[u][b] = make_float4(0.f, 0.f, 0.f, 0.f);
-#ifdef F2V_TEST_HOOKS
-                    else if (a.test_nowait & 4u) xj[u][b] = *reinterpret_cast<const float4 *>((inr[u] ? a.Xn : a.X) + (size_t)j0[u] * D + t * 4 + 4 * LPI * b);
-#endif
+                    else if (hook_nowait(a, 4u)) xj[u][b] = *reinterpret_cast<const float4 *>((inr[u] ? a.Xn : a.X) + (size_t)j0[u] * D + t * 4 + 4 * LPI * b);
                     else xj[u][b] = load16_agent(hs.r, off + 16u * LPI * b);
                 }
                 cf[u] = pair_coef_q<OPT, LPI, NB, false>(xi, xj[u], a.lr, c0, table);
@@ -1255,14 +1315,7 @@ __device__ __forceinline__ void qstep_body(const StepArgs &a, const uint32_t blk
         // the tail of the grid: one wavefront per node of the combine trees of this launch's hub rows; every node
         // waits for the partial sums it adds (hub pieces below announce theirs through the same flags)
         constexpr int FVEC = DP >= 64u ? (int)(DP / 64u) : 1;
-        FinalizeTreeArgs ft;
-        ft.f.X = a.X; ft.f.partials = a.partials; ft.f.Xn = a.Xn; ft.f.items = a.fin_items; ft.f.n_items = a.fin_n; ft.f.D = D;
-        ft.f.push = a.push;
-        ft.ready = a.ready; ft.err = a.err; ft.timeout_ticks = a.timeout_ticks; ft.seq = a.seq; ft.first_dep = 0u; ft.rowflag = a.rowflag;
-#ifdef F2V_TEST_HOOKS
-        ft.stamps = a.stamps;
-        ft.test_withhold_row = a.test_withhold_row;
-#endif
+        const FinalizeTreeArgs ft = tree_args_in_grid(a, a.fin_items, a.fin_n, D);
         const uint32_t node = (uint32_t)__builtin_amdgcn_readfirstlane((int)((blk - a.step_blocks) * wpb + (threadIdx.x >> 6)));
         finalize_tree_node<OPT, FVEC, (FULL && DP % 64u == 0u), CHAIN>(ft, node, lane);
         return;
@@ -1350,10 +1403,7 @@ __device__ __forceinline__ void qstep_body(const StepArgs &a, const uint32_t blk
     if (lds_samples) {
         if (active && last_chunk) {
             // option 5 in the plain launch, where an item has the lanes for it: the samples' coefficients in one evaluation
-            bool together = OPT == 5 && !CHAIN && LPI >= kLdsSamples;
-#ifdef F2V_TEST_HOOKS
-            together = together && (a.test_stub & 2u) == 0u;
-#endif
+            const bool together = OPT == 5 && !CHAIN && LPI >= kLdsSamples && !hook_stub(a, 2u);
             if constexpr (OPT == 5 && !CHAIN && LPI >= kLdsSamples) {
                 if (together) lds_samples5_q<LPI, NB>(smp, a.ns, t, xi, Y, a.lr);
             }
@@ -1361,12 +1411,10 @@ __device__ __forceinline__ void qstep_body(const StepArgs &a, const uint32_t blk
                 float4 xs[NB];
 #pragma unroll
                 for (int b = 0; b < NB; ++b) xs[b] = smp[sidx][LPI * b + t];
-#ifdef F2V_TEST_HOOKS
-                if (a.test_stub & 2u) {
+                if (hook_stub(a, 2u)) {
                     stub_update_q<NB>(xs, Y);
                     continue;
                 }
-#endif
                 pair_update_q<OPT, LPI, NB, true>(xi, xs, Y, a.lr, c0, table);
             }
         }
@@ -1423,25 +1471,13 @@ __device__ __forceinline__ void qstep_body(const StepArgs &a, const uint32_t blk
     if constexpr (PUSH) __builtin_amdgcn_s_waitcnt(0);  // the peers' memory has acknowledged this wave's rows
     if constexpr (CHAIN) {
         __builtin_amdgcn_s_waitcnt(0);  // new rows are in memory before they are announced to the later minibatches of the launch
-#ifdef F2V_TEST_HOOKS
-        if (active && !partial && ts == 0u && row != a.test_withhold_row)
-#else
-        if (active && !partial && ts == 0u)
-#endif
-            __hip_atomic_store(a.rowflag + row, a.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifdef F2V_TEST_HOOKS
-        if (a.stamps && active && !partial && ts == 0u) a.stamps[4 * (size_t)row + 2] = wall_clock64();
-#endif
+        if (active && !partial && ts == 0u) announce_row(a, row);
     }
     if (a.fin_items) {
         __builtin_amdgcn_s_waitcnt(0);  // partial sums are in memory before they are announced
-#ifdef F2V_TEST_HOOKS
-        if ((it.flags & kItemSlotMask) == a.test_withhold_slot) return;  // fault injection: this piece never announces its sum
-#endif
-        if (active && partial && ts == 0u) __hip_atomic_store(a.ready + (it.flags & kItemSlotMask), a.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifdef F2V_TEST_HOOKS
-        if (a.stamps && active && partial && it.cnt != 0u && ts == 0u) atomicMax(a.stamps + 4 * (size_t)row, wall_clock64());
-#endif
+        const uint32_t slot = it.flags & kItemSlotMask;
+        // (a withheld piece is not stamped either; nor is a padding piece, cnt == 0, which belongs to no row)
+        if (active && partial && ts == 0u && !hook_slot_withheld(a, slot)) announce_slot(a, slot, row, it.cnt != 0u ? kStampPiece : kStampNone);
     }
 }
 
@@ -1457,21 +1493,9 @@ constexpr int kStepWaves = (OPT == 5 && NB * U <= 8) ? 5 : 1;
 #endif
 template <int OPT, int LPI, int NB, int U, bool PUSH = false, bool FULL = true>
 __global__ __launch_bounds__(256, (kStepWaves<OPT, NB, U>)) void qstep_kernel(const StepArgs a) {
-#ifdef F2V_TEST_HOOKS
-    const unsigned long long t0 = a.xcd_times ? wall_clock64() : 0ull;
-#endif
+    const unsigned long long t0 = hook_xcd_begin(a);
     qstep_body<OPT, LPI, NB, U, PUSH, FULL, false>(a, blockIdx.x);
-#ifdef F2V_TEST_HOOKS
-    if (a.xcd_times && threadIdx.x == 0u) {
-        uint32_t id;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(id));
-        const unsigned long long t1 = wall_clock64();
-        atomicMax(a.xcd_times + (id & 7u), t1);
-        atomicMin(a.xcd_times + 8u + (id & 7u), t0);
-        atomicAdd(a.xcd_times + 16u + (id & 7u), t1 - t0);
-        atomicAdd(a.xcd_times + 24u + (id & 7u), 1ull);
-    }
-#endif
+    hook_xcd_end(a, t0);
 }
 
 // ---- chained minibatches: several consecutive minibatches in ONE launch ---------------------------------------------
@@ -1518,9 +1542,7 @@ __global__ __launch_bounds__(256, (NB <= 2 && U <= 4) ? 5 : 1) void qstep_chain_
     a.batch_lo = bd.lo;
     a.upd_rows = bd.lo - a.upd_lo;      // rows [upd_lo, this minibatch's first row) are read from the second matrix ...
     a.chain_rows = bd.lo - a.chain_lo;  // ... those from chain_lo on after waiting for their flag
-#ifdef F2V_TEST_HOOKS
-    if (a.chain_lo == 0xFFFFFFFFu) a.chain_rows = 0u;  // f2v_test_chain_nowait
-#endif
+    if (hook_nowait_chain(a)) a.chain_rows = 0u;  // f2v_test_chain_nowait
     a.sample_ids = c.ids + (size_t)bd.index * c.ids_stride;
     a.items = c.base.items + bd.item_off;
     a.n_items = bd.n_items;
@@ -1631,9 +1653,7 @@ __global__ __launch_bounds__(256, (NB <= 2 && U <= 4) ? (MODE == 2 ? 2 : OPT == 
     a.batch_lo = bd.lo;
     a.upd_rows = bd.lo - a.upd_lo;      // rows [upd_lo, this minibatch's first row) are read from the second matrix ...
     a.chain_rows = bd.lo - a.chain_lo;  // ... those from chain_lo on after waiting for their flag
-#ifdef F2V_TEST_HOOKS
-    if (a.test_nowait & 1u) a.chain_rows = 0u;  // f2v_test_chain_nowait (further bits: timing experiments, results WRONG)
-#endif
+    if (hook_nowait(a, 1u)) a.chain_rows = 0u;  // f2v_test_chain_nowait (further bits: timing experiments, results WRONG)
     a.sample_ids = w.ids + (EPOCHS ? (size_t)ep * w.ids_epoch_stride : (size_t)0) + (size_t)bd.index * w.ids_stride;
     const uint32_t D = FULL ? DP : a.D;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -1649,14 +1669,7 @@ __global__ __launch_bounds__(256, (NB <= 2 && U <= 4) ? (MODE == 2 ? 2 : OPT == 
     const rsrc_t part_rsrc = hand_rsrc(a.partials);  // helpers' group sums (partial-sum slot s at byte s * 4D)
     if (bd.kind == 1u) {
         constexpr int FVEC = DP >= 64u ? (int)(DP / 64u) : 1;
-        FinalizeTreeArgs ft;
-        ft.f.X = a.X; ft.f.partials = a.partials; ft.f.Xn = a.Xn; ft.f.items = a.fin_items + bd.a; ft.f.n_items = bd.b; ft.f.D = D;
-        ft.f.push = a.push;
-        ft.ready = a.ready; ft.err = a.err; ft.timeout_ticks = a.timeout_ticks; ft.seq = a.seq; ft.first_dep = 0u; ft.rowflag = a.rowflag;
-#ifdef F2V_TEST_HOOKS
-        ft.stamps = a.stamps;
-        ft.test_withhold_row = a.test_withhold_row;
-#endif
+        const FinalizeTreeArgs ft = tree_args_in_grid(a, a.fin_items + bd.a, bd.b, D);
         const uint32_t node = (uint32_t)__builtin_amdgcn_readfirstlane((int)(bd.c * 4u + wave));
         finalize_tree_node<OPT, FVEC, (FULL && DP % 64u == 0u), true>(ft, node, lane);
         return;
@@ -1787,11 +1800,7 @@ __global__ __launch_bounds__(256, (NB <= 2 && U <= 4) ? (MODE == 2 ? 2 : OPT == 
                         else if (prev_flags != nullptr) xi1 = __builtin_bit_cast(float, __hip_atomic_load(reinterpret_cast<const uint32_t *>(a.X + (size_t)jb.row * D + d), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
                         else xi1 = a.X[(size_t)jb.row * D + d];
                     }
-#ifdef F2V_TEST_HOOKS
-                    const bool skip_sums = (a.test_nowait & 8u) != 0u;
-#else
-                    constexpr bool skip_sums = false;
-#endif
+                    const bool skip_sums = hook_nowait(a, 8u);
                     if (jb.n2 != 0u && !skip_sums) S[(size_t)jb.dst2 * DP + d] = sum32(jb.src2, jb.n2);  // (read back by this very lane below)
                     float acc = sum32(jb.src, skip_sums ? 1u : jb.n);
                     if (jb.kind == kJobLds) {
@@ -1804,31 +1813,15 @@ __global__ __launch_bounds__(256, (NB <= 2 && U <= 4) ? (MODE == 2 ? 2 : OPT == 
                         const bool mine = gather16<1>(one, lane, piece, fd);  // quads -> 16-byte written-through stores
                         float *out = jb.kind == kJobRow ? a.Xn + (size_t)jb.row * D : a.partials + (size_t)jb.dst * D;
                         if (mine) store16_agent(out + d, piece[0]);
-#ifdef F2V_TEST_HOOKS
-                        if (!(a.test_nowait & 2u))
-#endif
-                        __builtin_amdgcn_s_waitcnt(0);  // this wavefront's written-through bytes have been acknowledged ...
+                        if (!hook_nowait(a, 2u)) __builtin_amdgcn_s_waitcnt(0);  // this wavefront's written-through bytes have been acknowledged ...
                     }
                 }
                 jc += 1u;
                 lds_barrier();  // ... by every wavefront that stored, before one lane announces them
                 if (threadIdx.x == 0u && (jb.kind == kJobPart || jb.kind == kJobRow)) {
-                    if (jb.kind == kJobRow) {
-#ifdef F2V_TEST_HOOKS
-                        if (jb.row != a.test_withhold_row)  // fault injection: this row is never announced
-#endif
-                        __hip_atomic_store(a.rowflag + jb.row, a.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    } else {
-#ifdef F2V_TEST_HOOKS
-                        if (a.stamps) atomicMax(a.stamps + 4 * (size_t)jb.row + 1, wall_clock64());
-                        if (jb.dst != a.test_withhold_slot)  // fault injection: this sum is never announced
-#endif
-                        __hip_atomic_store(a.ready + jb.dst, a.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
+                    if (jb.kind == kJobRow) announce_row(a, jb.row);
+                    else announce_slot(a, jb.dst, jb.row);
                 }
-#ifdef F2V_TEST_HOOKS
-                if (jb.kind == kJobRow && a.stamps && threadIdx.x == 0u) a.stamps[4 * (size_t)jb.row + 2] = wall_clock64();
-#endif
                 continue;
             }
             if (team < len) {
@@ -1875,11 +1868,7 @@ __global__ __launch_bounds__(256, (NB <= 2 && U <= 4) ? (MODE == 2 ? 2 : OPT == 
                     for (uint32_t c = tl; 4u * c < D; c += 32u) {
                         float4 xi4 = make_float4(0.f, 0.f, 0.f, 0.f);
                         if (OPT == 5 && jb.kind == kJobRow) xi4 = prev_flags != nullptr ? load16_agent(hs.r, hs.at(jb.row, false) + 16u * c) : *reinterpret_cast<const float4 *>(a.X + (size_t)jb.row * D + 4u * c);
-#ifdef F2V_TEST_HOOKS
-                        const bool skip_sums = (a.test_nowait & 8u) != 0u;
-#else
-                        constexpr bool skip_sums = false;
-#endif
+                        const bool skip_sums = hook_nowait(a, 8u);
                         if (jb.n2 != 0u && !skip_sums) slots[jb.dst2][c] = add_slots(jb.src2, jb.n2, c);  // (read back by this very lane below)
                         float4 acc = add_slots(jb.src, skip_sums ? 1u : jb.n, c);
                         if (jb.kind == kJobLds) {
@@ -1892,28 +1881,12 @@ __global__ __launch_bounds__(256, (NB <= 2 && U <= 4) ? (MODE == 2 ? 2 : OPT == 
                         }
                     }
                     if (jb.kind == kJobPart || jb.kind == kJobRow) {
-#ifdef F2V_TEST_HOOKS
-                        if (!(a.test_nowait & 2u))
-#endif
-                        __builtin_amdgcn_s_waitcnt(0);  // the written-through bytes have been acknowledged before they are announced
+                        if (!hook_nowait(a, 2u)) __builtin_amdgcn_s_waitcnt(0);  // the written-through bytes have been acknowledged before they are announced
                         if (tl == 0u) {
-                            if (jb.kind == kJobRow) {
-#ifdef F2V_TEST_HOOKS
-                                if (jb.row != a.test_withhold_row)  // fault injection: this row is never announced
-#endif
-                                __hip_atomic_store(a.rowflag + jb.row, a.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            } else {
-#ifdef F2V_TEST_HOOKS
-                                if (a.stamps) atomicMax(a.stamps + 4 * (size_t)jb.row + 1, wall_clock64());
-                                if (jb.dst != a.test_withhold_slot)  // fault injection: this sum is never announced
-#endif
-                                __hip_atomic_store(a.ready + jb.dst, a.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            }
+                            if (jb.kind == kJobRow) announce_row(a, jb.row);
+                            else announce_slot(a, jb.dst, jb.row);
                         }
                     }
-#ifdef F2V_TEST_HOOKS
-                    if (jb.kind == kJobRow && a.stamps && tl == 0u) a.stamps[4 * (size_t)jb.row + 2] = wall_clock64();
-#endif
                 }
             }
             jc += len;
@@ -2043,22 +2016,12 @@ __global__ __launch_bounds__(256, (NB <= 2 && U <= 4) ? (MODE == 2 ? 2 : OPT == 
             } else {
 #pragma unroll
                 for (int b = 0; b < NB; ++b) slots[it.flags & kItemPieceSlot][LPI * b + t] = make_float4(Y[b][0], Y[b][1], Y[b][2], Y[b][3]);
-#ifdef F2V_TEST_HOOKS
-                if (a.stamps && t == 0u) atomicMax(a.stamps + 4 * (size_t)row, wall_clock64());
-#endif
+                if (t == 0u) hook_stamp_max(a, row, kStampPiece);
             }
         }
         if (__builtin_amdgcn_ballot_w64(!idle && direct) != 0ull) {
             __builtin_amdgcn_s_waitcnt(0);  // the wave's new rows are in memory before they are announced
-            if (!idle && direct && !wave_bad && t == 0u) {
-#ifdef F2V_TEST_HOOKS
-                if (row != a.test_withhold_row)
-#endif
-                __hip_atomic_store(a.rowflag + row, a.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifdef F2V_TEST_HOOKS
-                if (a.stamps) a.stamps[4 * (size_t)row + 2] = wall_clock64();
-#endif
-            }
+            if (!idle && direct && !wave_bad && t == 0u) announce_row(a, row);
         }
         if ((uint32_t)__builtin_amdgcn_readfirstlane((int)(it.flags & kItemPhaseEnd)) != 0u) {
             if (jc < n_jobs && job_at(jc).phase == phase) {
