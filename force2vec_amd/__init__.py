@@ -13,6 +13,9 @@ Queries: `Engine.nearest(ids=..., k=10, metric="dot" | "l2" | "cos")` returns th
 the matrix for each query (rows or caller-supplied vectors) without the matrix leaving the GPU;
 `Engine.neighbour_recall(k, metric)` is the graph-reconstruction precision@k.
 
+Exact all-pairs Force2Vec: `Engine.train(1, iters, batch)` / `algorithms.AlgoForce2Vec` run the reference's option 1, where every vertex
+is repelled by every other one (no samples, no learning rate), and `Engine.objective(1)` is its exact objective (include/f2v.h).
+
 Clustering: `Engine.kmeans(k, max_iters=300, seed=1, restarts=1)` runs Lloyd's k-means on the rows of the matrix on the GPU
 (deterministic: include/f2v.h), `Engine.modularity(labels)` scores a labelling on the input graph.
 

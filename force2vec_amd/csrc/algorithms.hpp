@@ -82,6 +82,8 @@ class algorithms {
     }
 
     // options 5 / 5 -bs 1 / 6 / 6 -bs 1 / 7 (sample/algorithms.h:86-91)
+    // option 1, the exact all-pairs method (sample/algorithms.cpp:344-445): symmetric init, no samples, no learning rate
+    std::vector<VALUETYPE> AlgoForce2Vec(INDEXTYPE IT, INDEXTYPE TH, INDEXTYPE B) { return run(1, 0, IT, B, 0, 0.0f, "Force2Vec Parallel Wall time required:"); }
     std::vector<VALUETYPE> AlgoForce2VecNS(INDEXTYPE IT, INDEXTYPE TH, INDEXTYPE B, INDEXTYPE ns, VALUETYPE lr) { return run(5, 0, IT, B, ns, lr, "Force2Vec Parallel Wall time required:"); }
     std::vector<VALUETYPE> AlgoForce2VecNSBS(INDEXTYPE IT, INDEXTYPE TH, INDEXTYPE B, INDEXTYPE ns, VALUETYPE lr) { return run(5, 1, IT, B, ns, lr, "Force2Vec Parallel Wall time required (with BS negative samples):"); }
     std::vector<VALUETYPE> AlgoForce2VecNSRW(INDEXTYPE IT, INDEXTYPE TH, INDEXTYPE B, INDEXTYPE ns, VALUETYPE lr) { return run(6, 0, IT, B, ns, lr, "Force2Vec Parallel Wall time required:"); }
@@ -398,7 +400,7 @@ class algorithms {
     std::vector<VALUETYPE> run(int option, int bs, INDEXTYPE IT, INDEXTYPE B, INDEXTYPE ns, VALUETYPE lr, const char *msg) {
         // the reference's timer spans randInit + the epoch loop (algorithms.cpp:557-558, 647)
         auto t0 = std::chrono::steady_clock::now();
-        const int math = (option == 5 || option == 8 || option == 11) ? 5 : 6;
+        const int math = (option == 1 || option == 5 || option == 8 || option == 11) ? 5 : 6;
         init(math);
         if (world > 1) {
             check(f2v_train_sharded(h, option, IT, B, ns, lr, bs, &gpu_train_seconds));

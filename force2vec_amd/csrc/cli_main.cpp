@@ -57,6 +57,7 @@ struct Variant {
     std::vector<VALUETYPE> (algorithms::*with_bs)(INDEXTYPE, INDEXTYPE, INDEXTYPE, INDEXTYPE, VALUETYPE);
 };
 const Variant kVariants[] = {
+    {1, "Force2Vec(n^2)", nullptr, nullptr},  // AlgoForce2Vec(ITERATIONS, NUMOFTHREADS, BATCHSIZE): no samples, no learning rate
     {5, "Force2Vec:t-distribution with negative sampling", &algorithms::AlgoForce2VecNS, &algorithms::AlgoForce2VecNSBS},
     {6, "Force2Vec:sigmoid with negative sampling", &algorithms::AlgoForce2VecNSRW, &algorithms::AlgoForce2VecNSRWBS},
     {7, "Force2Vec:sigmoid based random-walk", &algorithms::AlgoForce2VecNSRWEFF, nullptr},
@@ -85,10 +86,11 @@ int main(int argc, char *argv[]) {
         {"-dim", Kind::Integer, &s.dim, "<int>, size of embedding dimension, 1..512. (default:128)"},
         {"-nsamples", Kind::Integer, &s.nsamples, "<int>, number of negative samples. (default:5)"},
         {"-lr", Kind::Real, &s.lr, "<float>, learning rate of SGD. (default:0.02)"},
-        {"-gamma", Kind::Real, &s.gamma, "<float>, accepted for compatibility (unused by options 5-11)."},
+        {"-gamma", Kind::Real, &s.gamma, "<float>, accepted for compatibility (unused by options 1 and 5-11)."},
         {"-bs", Kind::Integer, &s.bs, "<int>, 1 = draw nsamples*batch negative samples per minibatch (options 5 and 6)."},
         {"-option", Kind::Integer, &s.option,
-         "<int>, 5 tForce2Vec (t-distribution + negative sampling), 6 sForce2Vec (sigmoid), 7 rForce2Vec (semi-random walk);\n"
+         "<int>, 1 Force2Vec (O(n^2) version: every vertex repelled by every other one, exact; one GPU; -nsamples and -lr are unused, -bs 1 is refused);\n"
+         "        5 tForce2Vec (t-distribution + negative sampling), 6 sForce2Vec (sigmoid), 7 rForce2Vec (semi-random walk);\n"
          "        8..11 run the same three with the reference's AVX512 output names (8,11 -> 5; 9 -> 6; 10 -> 7). (default:5)"},
         {"-device", Kind::Integer, &s.device, "<int>, HIP device ordinal. (default:0)"},
         {"-seed", Kind::Integer, &s.seed, "<int>, srand() seed. (default:1)"},
@@ -137,7 +139,7 @@ int main(int argc, char *argv[]) {
     for (const Variant &v : kVariants)
         if (v.option == s.option) variant = &v;
     if (!variant) {
-        printf("This build implements options 5 to 11 (the negative-sampling force kernels); option %ld is out of scope.\n", s.option);
+        printf("This build implements option 1 (exact all-pairs Force2Vec) and options 5 to 11 (the negative-sampling force kernels); option %ld is out of scope.\n", s.option);
         return 1;
     }
     if (s.batch <= 0 || s.dim <= 0 || s.iter < 0 || s.nsamples < 0) {
@@ -146,6 +148,14 @@ int main(int argc, char *argv[]) {
     }
     if (s.gpus < 1 || s.gpus > F2V_PUSH_MAX_RANKS) {
         printf("-gpus must be 1..%d.\n", F2V_PUSH_MAX_RANKS);
+        return 1;
+    }
+    if (s.option == 1 && s.gpus > 1) {
+        printf("-option 1 is not available with -gpus > 1 (the exact all-pairs method runs on one GPU).\n");
+        return 1;
+    }
+    if (s.option == 1 && s.bs != 0) {
+        printf("-option 1 has no -bs 1 variant (the exact all-pairs method draws no samples).\n");
         return 1;
     }
     if (s.loss < 0 || s.loss > 0x7FFFFFFF) {
@@ -160,7 +170,7 @@ int main(int argc, char *argv[]) {
         printf("-nearest must be 0..%d.\n", F2V_NEAREST_MAX_K);
         return 1;
     }
-    if (s.metric.empty()) s.metric = (s.option == 5 || s.option == 8 || s.option == 11) ? "l2" : "dot";
+    if (s.metric.empty()) s.metric = (s.option == 1 || s.option == 5 || s.option == 8 || s.option == 11) ? "l2" : "dot";
     const int metric = s.metric == "dot" ? F2V_SIM_DOT : s.metric == "l2" ? F2V_SIM_L2 : s.metric == "cos" ? F2V_SIM_COSINE : -1;
     if (metric < 0) {
         printf("-metric must be dot, l2 or cos.\n");
@@ -258,7 +268,8 @@ int main(int argc, char *argv[]) {
             if (s.gpus > 1) algo.join_ranks(rank, (int)s.gpus, meet);
             if (rank == 0) std::cout << "Running: " << variant->name << std::endl;
             auto method = (s.bs != 0 && variant->with_bs) ? variant->with_bs : variant->plain;
-            seconds = (algo.*method)((INDEXTYPE)s.iter, (INDEXTYPE)s.threads, (INDEXTYPE)s.batch, (INDEXTYPE)s.nsamples, (VALUETYPE)s.lr);
+            if (!method) seconds = algo.AlgoForce2Vec((INDEXTYPE)s.iter, (INDEXTYPE)s.threads, (INDEXTYPE)s.batch);
+            else seconds = (algo.*method)((INDEXTYPE)s.iter, (INDEXTYPE)s.threads, (INDEXTYPE)s.batch, (INDEXTYPE)s.nsamples, (VALUETYPE)s.lr);
             if (s.loss > 0 && rank == 0) {  // the reference's commented-out print (sample/algorithms.cpp:645), from the run's log
                 uint32_t count = 0;
                 if (f2v_train_losses(algo.h, nullptr, nullptr, 0, &count) != F2V_OK) throw std::runtime_error(f2v_last_error());

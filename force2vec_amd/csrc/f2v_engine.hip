@@ -37,6 +37,7 @@
 #include "f2v_logreg.hip.h"
 #include "f2v_separation.hip.h"
 #include "f2v_layout.hip.h"
+#include "f2v_exact.hip.h"
 
 using namespace f2v;
 
@@ -260,6 +261,18 @@ struct f2v_ctx {
         DevTimer timer;
         uint32_t chunk = 8192, block = 0;
     } lay;
+    // exact all-pairs Force2Vec (option 1: f2v_train, f2v_objective): the workspace f2v.h states, allocated on first use and grown for a
+    // larger minibatch; "exact_rows" (0 = automatic | 4 | 8 | 16): rows per workgroup of exact_pair_kernel; "exact_epoch": the index
+    // of the next call's first epoch (it fixes the step)
+    struct Exact {
+        DevBuf<float> d_ws;
+        DevBuf<double> d_rows, d_piece;
+        uint32_t rows = 0;
+        uint32_t quarter_min = 1024;  // "exact_quarter_min"
+        uint32_t last_rows = 0;       // "last_exact_rows"
+        bool last_quarter = false;    // "last_exact_quarter"
+        uint64_t epoch = 0;
+    } ex;
     uint32_t last_wide_width = 0;  // the layout width of the last wide-form f2v_train ("last_wide_width")
     bool last_wide_early = false;  // ... and whether it ran the kernel's EARLY form ("last_wide_early")
     int last_train_form = 0;  // how the last f2v_train launched: 0 one launch per minibatch, 1 chained, 2 chained in the wide form ("last_train_form")
@@ -2235,6 +2248,15 @@ const Param kParams[] = {
     {"trust_chunk", F2V_FIELD(lay.chunk), kValue, kKeep, in<1, 1048576>, "trust_chunk must be 1..1048576"},
     // sample rows per workgroup of trust_rank_kernel (0: 64; 128 holds where k <= 32, its thresholds live in LDS); results do not depend on it
     {"trust_block", F2V_FIELD(lay.block), kValue, kKeep, one_of<0, 64, 128>, "trust_block must be 0, 64 or 128"},
+    // rows per workgroup of exact_pair_kernel (0: from the minibatch and the spans, so that the grid fills the card); results do not depend on it
+    {"exact_rows", F2V_FIELD(ex.rows), kValue, kKeep, one_of<0, 4, 8, 16>, "exact_rows must be 0 (automatic), 4, 8 or 16"},
+    // fewest rows of a minibatch that run the quarter-wave pair kernel where D allows it (0: every minibatch); results do not depend on it
+    {"exact_quarter_min", F2V_FIELD(ex.quarter_min), kValue, kKeep, in<0, 0xFFFFFFFFll>, "exact_quarter_min out of range"},
+    // what the last minibatch of the last f2v_train(option 1) ran with: rows per workgroup, and whether the quarter-wave kernel
+    {"last_exact_rows", F2V_GET(ex.last_rows)},
+    {"last_exact_quarter", F2V_GET(ex.last_quarter)},
+    // the index e of the first epoch of the next f2v_train(option 1): STEP_e; a call of `iters` epochs advances it by `iters`
+    {"exact_epoch", F2V_FIELD(ex.epoch), kValue, kKeep, in<0, 0x7FFFFFFF>, "exact_epoch must be 0..2^31-1"},
     {"push_fused", F2V_FIELD(push.fused), kFlag},
     {"push_timeout_ms", F2V_FIELD(push.timeout_ms), kValue, kKeep, in<1, 600000>, "push_timeout_ms must be 1..600000"},
     // takes effect at the next f2v_push_export; read: what the exchange in place runs with
@@ -2268,6 +2290,9 @@ const Param *find_param(const char *name) {
 }
 
 int train_impl(f2v_ctx *c, int option, uint32_t iters, uint32_t batch, uint32_t ns, float lr, int bs_mode, double *seconds_out, bool sharded);
+int train_exact(f2v_ctx *c, uint32_t iters, uint32_t batch, int bs_mode, double *seconds_out);
+int launch_exact_objective(f2v_ctx *c, const float *X, ObjPartial *out);
+int exact_objective_prepare(f2v_ctx *c);
 
 }  // namespace
 
@@ -2551,6 +2576,7 @@ int f2v_minibatch_step(f2v_handle c, int option, uint32_t batch_lo, uint32_t bat
                        uint32_t row_hi, const uint32_t *sample_ids, uint32_t n_sample_ids, uint32_t ns, float lr,
                        int bs_mode) {
     if (!c) return fail(F2V_EINVAL, "null handle");
+    if (option == 1) return fail(F2V_EINVAL, "f2v_minibatch_step: option 1 (exact all-pairs Force2Vec) runs on a single GPU, f2v_train only");
     const int math = math_of_option(option);
     if (!math) return fail(F2V_EINVAL, "f2v_minibatch_step: option %d is outside 5..11", option);
     c->unit_degi = option == 10;
@@ -2591,6 +2617,7 @@ int f2v_upload_sample_ids(f2v_handle c, const uint32_t *ids, uint64_t count) {
 int f2v_minibatch_step_at(f2v_handle c, int option, uint32_t batch_lo, uint32_t batch_hi, uint32_t row_lo,
                           uint32_t row_hi, uint64_t ids_offset, uint32_t ns, float lr, int bs_mode) {
     if (!c) return fail(F2V_EINVAL, "null handle");
+    if (option == 1) return fail(F2V_EINVAL, "f2v_minibatch_step_at: option 1 (exact all-pairs Force2Vec) runs on a single GPU, f2v_train only");
     const int math = math_of_option(option);
     if (!math) return fail(F2V_EINVAL, "f2v_minibatch_step_at: option %d is outside 5..11", option);
     c->unit_degi = option == 10;
@@ -2698,6 +2725,11 @@ int f2v_get_stats(f2v_handle c, f2v_stats *out) {
 int f2v_train(f2v_handle c, int option, uint32_t iters, uint32_t batch, uint32_t ns, float lr, int bs_mode,
               double *seconds_out) {
     if (!c) return fail(F2V_EINVAL, "null handle");
+    if (option == 1) {  // exact all-pairs: plain launches, nothing to snapshot or recover
+        c->stats.snapshot_seconds = 0.0;
+        c->stats.recovered = 0u;
+        return train_exact(c, iters, batch, bs_mode, seconds_out);
+    }
     // A launch whose workgroups wait for each other (combine-tree nodes inside the step kernel's grid, chained minibatches)
     // counts on this process having the GPU to itself: another process that fills the card with ITS waiting workgroups can
     // keep the ones everybody waits for from starting.  Every wait is bounded, and a wait that gives up must not cost the
@@ -2772,12 +2804,14 @@ int f2v_train_marks(f2v_handle c, double *seconds_out, uint32_t cap, uint32_t *c
 
 int f2v_objective(f2v_handle c, int option, uint32_t ns, f2v_objective_t *out) {
     if (!c || !out) return fail(F2V_EINVAL, "f2v_objective: null argument");
-    if (!math_of_option(option)) return fail(F2V_EINVAL, "f2v_objective: option %d is outside 5..11", option);
+    const bool exact = option == 1;  // the all-pairs objective: ns is ignored
+    if (!exact && !math_of_option(option)) return fail(F2V_EINVAL, "f2v_objective: option %d is neither 1 nor one of 5..11", option);
     if (c->n < 2) return fail(F2V_EINVAL, "f2v_objective: the graph needs at least two vertices");
     int rc = settled_enter(c, "f2v_objective");
     if (rc != F2V_OK) return rc;
-    if ((rc = objective_prepare(c)) != F2V_OK) return rc;
-    if ((rc = launch_objective(c, c->d_X[c->cur], option, ns, c->d_obj_out + kLossLogMax)) != F2V_OK) return rc;
+    if ((rc = exact ? exact_objective_prepare(c) : objective_prepare(c)) != F2V_OK) return rc;
+    rc = exact ? launch_exact_objective(c, c->d_X[c->cur], c->d_obj_out + kLossLogMax) : launch_objective(c, c->d_X[c->cur], option, ns, c->d_obj_out + kLossLogMax);
+    if (rc != F2V_OK) return rc;
     ObjPartial r;
     HIPC(hipMemcpyAsync(&r, c->d_obj_out + kLossLogMax, sizeof r, hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
@@ -2803,6 +2837,7 @@ int f2v_train_losses(f2v_handle c, uint32_t *epochs_out, double *values_out, uin
 int f2v_train_sharded(f2v_handle c, int option, uint32_t iters, uint32_t batch, uint32_t ns, float lr, int bs_mode,
                       double *seconds_out) {
     if (!c) return fail(F2V_EINVAL, "null handle");
+    if (option == 1) return fail(F2V_EINVAL, "f2v_train_sharded: option 1 (exact all-pairs Force2Vec) runs on a single GPU, f2v_train only");
     if (c->loss_every) return fail(F2V_EINVAL, "f2v_train_sharded: \"loss_every\" is not supported (a rank does not hold the whole matrix between minibatches)");
     if (!c->push.attached) return fail(F2V_ESTATE, "f2v_train_sharded: f2v_push_attach first");
     const int math = math_of_option(option);
@@ -3256,6 +3291,197 @@ int train_impl(f2v_ctx *c, int option, uint32_t iters, uint32_t batch, uint32_t 
         }
     }
     if (exchanging) return check_push_err(c, "f2v_train_sharded");
+    return F2V_OK;
+}
+
+// ---- exact all-pairs Force2Vec, option 1 (f2v_exact.hip.h; definition in include/f2v.h) -----------------------------------------
+uint32_t exact_spans(const f2v_ctx *c) { return (c->n + kExactSpanCols - 1u) / kExactSpanCols; }
+
+// STEP_e: e multiplications from 1.0f (sample/algorithms.cpp:436, the product formed in fp64 as the reference's 0.999 is a double)
+float exact_step(uint64_t e) {
+    float step = 1.0f;
+    for (uint64_t k = 0; k < e; k++) step = (float)((double)step * 0.999);
+    return step;
+}
+
+template <int VEC, bool EXACT>
+void launch_exact_pair_t(f2v_ctx *c, const ExactArgs &a, uint32_t rows_per_wg) {
+    const uint32_t groups = (a.hi - a.lo + rows_per_wg - 1u) / rows_per_wg;
+    const dim3 grid(groups, a.spans + 1u);
+    if (rows_per_wg == 4) hipLaunchKernelGGL((exact_pair_kernel<VEC, EXACT, 1>), grid, dim3(256), 0, c->stream, a);
+    else if (rows_per_wg == 8) hipLaunchKernelGGL((exact_pair_kernel<VEC, EXACT, 2>), grid, dim3(256), 0, c->stream, a);
+    else hipLaunchKernelGGL((exact_pair_kernel<VEC, EXACT, 4>), grid, dim3(256), 0, c->stream, a);
+}
+
+// the same launch in the quarter-wave layout (D a multiple of 4 up to 256, "quarter_wave" on): one wavefront per four rows
+void launch_exact_pair_q(f2v_ctx *c, const ExactArgs &a, uint32_t rows_per_wg) {
+    const dim3 grid((a.hi - a.lo + rows_per_wg - 1u) / rows_per_wg, a.spans + 1u), block(16u * rows_per_wg);
+    if (c->D <= 64u) hipLaunchKernelGGL((exact_pair_q_kernel<1>), grid, block, 0, c->stream, a);
+    else if (c->D <= 128u) hipLaunchKernelGGL((exact_pair_q_kernel<2>), grid, block, 0, c->stream, a);
+    else hipLaunchKernelGGL((exact_pair_q_kernel<4>), grid, block, 0, c->stream, a);
+}
+
+// Rows per workgroup ("exact_rows"): more rows share a staged column, fewer rows make more workgroups.  0: the most rows that
+// still leave four workgroups per compute unit (1024 of them), from the minibatch's rows and the spans alone.
+uint32_t exact_rows_per_wg(const f2v_ctx *c, uint32_t rows) {
+    if (c->ex.rows) return c->ex.rows;
+    const uint64_t slices = (uint64_t)exact_spans(c) + 1u;
+    for (uint32_t r = 16; r > 4; r >>= 1)
+        if ((uint64_t)((rows + r - 1u) / r) * slices >= 1024u) return r;
+    return 4;
+}
+
+// One evaluation of the exact objective of matrix X (two launches, no synchronisation, no allocation once the workspace stands)
+int launch_exact_objective(f2v_ctx *c, const float *X, ObjPartial *out) {
+    ExactObjArgs a{};
+    a.X = X;
+    a.rowptr = c->d_rowptr;
+    a.colids = c->d_colids;
+    a.row_att = c->ex.d_rows;
+    a.row_rep = c->ex.d_rows + c->n;
+    a.n = c->n;
+    a.D = c->D;
+    const uint32_t wgs = (c->n + 15u) / 16u;
+    int rc = dispatch_layout(c, [&](auto V, auto E) {
+        hipLaunchKernelGGL((exact_objective_kernel<decltype(V)::value, decltype(E)::value>), dim3(wgs), dim3(256), 0, c->stream, a);
+    });
+    if (rc != F2V_OK) return rc;
+    HIPC(hipGetLastError());
+    hipLaunchKernelGGL(exact_objective_reduce_kernel, dim3(1), dim3(1024), 0, c->stream, (const double *)a.row_att, (const double *)a.row_rep, c->n,
+                       (unsigned long long)c->nnz, (double *)c->ex.d_piece, out);
+    HIPC(hipGetLastError());
+    return F2V_OK;
+}
+
+// the exact objective's workspace (2 n doubles of row sums, 2 ceil(n / 64) doubles of piece sums) and the slots of the results
+int exact_objective_prepare(f2v_ctx *c) {
+    F2VC(objective_prepare(c));
+    F2VC(c->ex.d_rows.reserve(c, 2 * (size_t)c->n, "exact objective"));
+    return c->ex.d_piece.reserve(c, 2 * (size_t)((c->n + kExactPiece - 1u) / kExactPiece), "exact objective");
+}
+
+// f2v_train with option 1: per minibatch one launch of the pair kernel and one of the finish kernel on the handle's stream.  No
+// in-grid waits (hence no snapshot and nothing to recover from), no rand() draw.
+int train_exact(f2v_ctx *c, uint32_t iters, uint32_t batch, int bs_mode, double *seconds_out) {
+    if (!c->have_x) return fail(F2V_ESTATE, "f2v_train: embeddings not initialised (f2v_init_embeddings)");
+    if (batch == 0) return fail(F2V_EINVAL, "f2v_train: batch must be positive");
+    if (bs_mode) return fail(F2V_EINVAL, "f2v_train: option 1 has no -bs 1 variant");
+    if (c->loss_every && c->n < 2) return fail(F2V_EINVAL, "f2v_train: \"loss_every\" needs a graph of at least two vertices");
+    c->loss_epochs.clear();
+    c->loss_values.clear();
+    c->last_loss_us = 0.0;
+    c->marks.clear();
+    HIPC(hipSetDevice(c->device));
+    F2VC(flush_pending(c));
+    const uint32_t n = c->n, D = c->D;
+    const uint32_t nb = (uint32_t)(((uint64_t)n + batch - 1) / batch);
+    const uint32_t spans = exact_spans(c);
+    F2VC(c->ex.d_ws.reserve(c, (size_t)std::min(batch, n) * (spans + 1u) * D, "exact training"));
+    c->stats = f2v_stats{};
+    c->last_train_form = 0;
+    c->last_wide_epochs = 1;
+    struct Events {  // destroyed on every way out of this function
+        std::vector<hipEvent_t> all;
+        int make(hipEvent_t *e) {
+            HIPC(hipEventCreateWithFlags(e, hipEventDefault));
+            all.push_back(*e);
+            return F2V_OK;
+        }
+        ~Events() { for (hipEvent_t e : all) (void)hipEventDestroy(e); }
+    } events;
+    hipEvent_t ev0, ev1;
+    F2VC(events.make(&ev0));
+    F2VC(events.make(&ev1));
+    // "loss_every" and "epoch_marks" as train_impl has them: evaluations between the epochs, bracketed by events, their time taken out
+    const uint32_t loss_k = c->loss_every;
+    const uint32_t loss_planned = loss_k ? std::min<uint32_t>(iters / loss_k + (iters % loss_k ? 1u : 0u), kLossLogMax) : 0u;
+    std::vector<hipEvent_t> loss_ev(2 * (size_t)loss_planned), mark_ev;
+    std::vector<uint32_t> loss_log;
+    std::vector<size_t> mark_loss;
+    if (loss_planned) {
+        F2VC(exact_objective_prepare(c));
+        for (auto &e : loss_ev) F2VC(events.make(&e));
+    }
+    ExactArgs a{};
+    a.X = c->d_X[c->cur];
+    a.rowptr = c->d_rowptr;
+    a.colids = c->d_colids;
+    a.ws = c->ex.d_ws;
+    a.n = n;
+    a.D = D;
+    a.spans = spans;
+    float step = exact_step(c->ex.epoch);
+    HIPC(hipEventRecord(ev0, c->stream));
+    for (uint32_t it = 0; it < iters; it++) {
+        a.step = step;
+        for (uint32_t b = 0; b < nb; b++) {
+            a.lo = b * batch;
+            a.hi = (uint32_t)std::min<uint64_t>((uint64_t)a.lo + batch, n);
+            const uint32_t rows = a.hi - a.lo, rpw = exact_rows_per_wg(c, rows);
+            // Both pair kernels give the same bits.  The quarter-wave one is the faster where a minibatch fills the card (measured
+            // 1.5 x at 16384 rows, 1.2 x at 2708), the generic one at the reference's default-sized minibatches (1.1-1.35 x at 256
+            // and 384 rows: its workgroups are always four wavefronts that share a staged piece): profiles/exact_time.txt.
+            const bool quarter = subwave_width(c) != 0u && rows >= c->ex.quarter_min;
+            c->ex.last_rows = rpw;
+            c->ex.last_quarter = quarter;
+            if (quarter) {
+                launch_exact_pair_q(c, a, rpw);
+            } else {
+                int rc = dispatch_layout(c, [&](auto V, auto E) { launch_exact_pair_t<decltype(V)::value, decltype(E)::value>(c, a, rpw); });
+                if (rc != F2V_OK) return rc;
+            }
+            HIPC(hipGetLastError());
+            hipLaunchKernelGGL(exact_finish_kernel, dim3((uint32_t)(((size_t)rows * D + 255u) / 256u)), dim3(256), 0, c->stream, a);
+            HIPC(hipGetLastError());
+            c->stats.step_launches++;
+            c->stats.rows += rows;
+            c->stats.nnz += c->rowptr[a.hi] - c->rowptr[a.lo];
+            // the columns of all n vertices and the minibatch's rows in, the span sums out and in again, the rows out
+            c->stats.algorithmic_bytes += ((uint64_t)n + 2ull * rows + 2ull * rows * (spans + 1u)) * D * sizeof(float);
+        }
+        step = (float)((double)step * 0.999);
+        if (c->mark_every && (it + 1) % c->mark_every == 0 && mark_ev.size() < 4096) {
+            hipEvent_t e;
+            F2VC(events.make(&e));
+            HIPC(hipEventRecord(e, c->stream));
+            mark_ev.push_back(e);
+            mark_loss.push_back(loss_log.size());
+        }
+        if (loss_k && ((it + 1) % loss_k == 0 || it + 1 == iters) && loss_log.size() < loss_planned) {
+            const size_t m = loss_log.size();
+            HIPC(hipEventRecord(loss_ev[2 * m], c->stream));
+            F2VC(launch_exact_objective(c, a.X, c->d_obj_out + m));
+            HIPC(hipEventRecord(loss_ev[2 * m + 1], c->stream));
+            loss_log.push_back(it + 1);
+        }
+    }
+    HIPC(hipEventRecord(ev1, c->stream));
+    HIPC(hipEventSynchronize(ev1));
+    c->ex.epoch += iters;
+    float ms = 0.f;
+    HIPC(hipEventElapsedTime(&ms, ev0, ev1));
+    std::vector<double> loss_ms(loss_log.size() + 1, 0.0);  // evaluation time before entry m: not the epoch loop's
+    for (size_t m = 0; m < loss_log.size(); m++) {
+        float em = 0.f;
+        HIPC(hipEventElapsedTime(&em, loss_ev[2 * m], loss_ev[2 * m + 1]));
+        loss_ms[m + 1] = loss_ms[m] + em;
+    }
+    c->last_loss_us = loss_ms.back() * 1e3;
+    c->stats.device_seconds = (ms - loss_ms.back()) * 1e-3;
+    if (seconds_out) *seconds_out = c->stats.device_seconds;
+    for (size_t k = 0; k < mark_ev.size(); k++) {
+        float mm = 0.f;
+        HIPC(hipEventElapsedTime(&mm, ev0, mark_ev[k]));
+        c->marks.push_back((mm - loss_ms[mark_loss[k]]) * 1e-3);
+    }
+    if (!loss_log.empty()) {
+        std::vector<ObjPartial> r(loss_log.size());
+        HIPC(hipMemcpy(r.data(), c->d_obj_out, r.size() * sizeof(ObjPartial), hipMemcpyDeviceToHost));
+        for (size_t m = 0; m < r.size(); m++) {
+            c->loss_epochs.push_back(loss_log[m]);
+            c->loss_values.insert(c->loss_values.end(), {r[m].attraction + r[m].repulsion, r[m].attraction, r[m].repulsion});
+        }
+    }
     return F2V_OK;
 }
 

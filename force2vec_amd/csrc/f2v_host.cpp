@@ -801,6 +801,11 @@ int f2v_output_name(const char *input, const char *outdir, int option, int bs_mo
     size_t pos = in.find_last_of('/');
     base = pos == std::string::npos ? in : in.substr(pos + 1);
     const char *tag;
+    if (option == 1) {  // AlgoForce2Vec takes no ns and names none (algorithms.cpp:443)
+        int w = snprintf(out, out_len, "%s%sF2V%uD%uIT%u.embd", outdir, base.c_str(), batch, dim, iters);
+        if (w < 0 || (size_t)w >= out_len) return fail(F2V_EINVAL, "f2v_output_name: buffer too small");
+        return F2V_OK;
+    }
     switch (option) {
         case 5: tag = "F2VNS"; break;             // algorithms.cpp:650 (and :752 for -bs 1)
         case 6: tag = "F2VWNS"; break;            // :930 (:1059)
@@ -809,7 +814,7 @@ int f2v_output_name(const char *input, const char *outdir, int option, int bs_mo
         case 9: tag = dim == 64 ? "F2VWNSLB64_AVXZ" : "F2VWNS_AVXZ"; break;        // :3235 / :2047
         case 10: tag = dim == 64 ? "F2VWEFFNS_AVXZ64" : "F2VWEFFNS_AVXZ"; break;   // :4047 / :2409
         case 11: tag = dim == 64 ? "F2VNSLB_AVXZ64" : "F2VNSLB_AVXZ"; break;       // :3681 / :2860
-        default: return fail(F2V_EINVAL, "f2v_output_name: option %d is outside 5..11", option);
+        default: return fail(F2V_EINVAL, "f2v_output_name: option %d is neither 1 nor one of 5..11", option);
     }
     (void)bs_mode;
     int w = snprintf(out, out_len, "%s%s%s%uD%uIT%uNS%u.embd", outdir, base.c_str(), tag, batch, dim, iters, ns);

@@ -583,13 +583,17 @@ class algorithms:
 
     def _run(self, option, bs, ITER, BATCH, ns, lr, write=True):
         t0 = time.perf_counter()
-        self.engine.init_embeddings(INIT_SYMMETRIC if option in (5, 8, 11) else INIT_UNIT)
+        self.engine.init_embeddings(INIT_SYMMETRIC if option in (1, 5, 8, 11) else INIT_UNIT)
         self.gpu_train_seconds = self.engine.train(option, ITER, BATCH, ns, lr, bs)
         sec = time.perf_counter() - t0
         self.nCoordinates = self.engine.get_embeddings()
         if write and self.filename:
             self.writeToFile(output_name(self.filename, self.outputdir, option, bs, BATCH, self.DIM, ITER, ns))
         return [sec]
+
+    def AlgoForce2Vec(self, ITERATIONS, NUMOFTHREADS, BATCHSIZE):
+        """Option 1, the exact all-pairs Force2Vec (sample/algorithms.cpp:344-445): no samples, no learning rate."""
+        return self._run(1, 0, ITERATIONS, BATCHSIZE, 0, 0.0)
 
     def AlgoForce2VecNS(self, ITERATIONS, NUMOFTHREADS, BATCHSIZE, ns, lr):
         return self._run(5, 0, ITERATIONS, BATCHSIZE, ns, lr)

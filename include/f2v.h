@@ -132,7 +132,8 @@ F2V_API int f2v_get_param(f2v_handle h, const char *name, int64_t *value_out);
  * the attraction by deg + 1, as AlgoForce2VecNSRWEFF_SREAL_D128/D64_AVXZ have it: `degi = 1.0`, sample/algorithms.cpp:2155, :3793).  bs_mode: the
  * CLI's "-bs" (1 = ns*batch samples per minibatch, row i uses samples [i, i+ns)).
  * seconds_out (may be NULL) receives the device time of the epoch loop alone (HIP events);
- * the embeddings stay in HBM (fetch with f2v_get_embeddings). */
+ * the embeddings stay in HBM (fetch with f2v_get_embeddings).  option 1 is the exact all-pairs Force2Vec (AlgoForce2Vec,
+ * sample/algorithms.cpp:344-445), which samples nothing: its definition has a section of its own below. */
 F2V_API int f2v_train(f2v_handle h, int option, uint32_t iters, uint32_t batch, uint32_t ns, float lr, int bs_mode,
               double *seconds_out);
 /* (While "recover" is on -- the default -- and the handle uses in-grid waits, f2v_train keeps a copy of the matrix and of the
@@ -293,7 +294,8 @@ typedef struct {
     uint64_t positive_pairs, negative_pairs;
 } f2v_objective_t;
 /* The objective of the current matrix (pending minibatches are committed first, as f2v_get_embeddings does).  ns = 0: repulsion 0.
- * F2V_EINVAL for an option outside 5..11 or a graph of fewer than two vertices, F2V_ESTATE without valid embeddings. */
+ * Option 1 is the exact all-pairs objective defined in its own section below (ns is ignored).
+ * F2V_EINVAL for an option that is neither 1 nor one of 5..11 or a graph of fewer than two vertices, F2V_ESTATE without valid embeddings. */
 F2V_API int f2v_objective(f2v_handle h, int option, uint32_t ns, f2v_objective_t *out);
 /* With "loss_every" = k > 0 f2v_train also evaluates the objective -- with the call's option and ns -- after its epochs k, 2k, ...
  * and after its last epoch (at most 4096 entries per call, the first ones), on the device between the epochs: no host
@@ -306,6 +308,61 @@ F2V_API int f2v_objective(f2v_handle h, int option, uint32_t ns, f2v_objective_t
  * f2v_train_sharded with "loss_every" > 0 fails with F2V_EINVAL: a rank does not hold the whole matrix between minibatches (out
  * of scope). */
 F2V_API int f2v_train_losses(f2v_handle h, uint32_t *epochs_out, double *values_out, uint32_t cap, uint32_t *count_out);
+
+/* ---- exact all-pairs Force2Vec (option 1) -------------------------------------------------------------------------------------
+ * The reference's `-option 1`, "Force2Vec (O(n^2) version)": vector<float> algorithms::AlgoForce2Vec(ITERATIONS, NUMOFTHREADS,
+ * BATCHSIZE) (sample/algorithms.cpp:344-445).  Every vertex is repelled by EVERY other vertex, not by ns samples: the method the
+ * options 5-11 approximate, and the ground truth they can be scored against.  f2v_train(h, 1, iters, batch, ns, lr, 0, seconds_out)
+ * runs it (ns and lr are ignored: AlgoForce2Vec takes neither; bs_mode must be 0), f2v_objective(h, 1, ns, out) evaluates its
+ * objective.  Defined so that the result is a function of (X, CSR, batch, epochs, first epoch) alone: bitwise identical between calls,
+ * handles and GPUs and under every tunable; no float atomics.  Every operation below is one rounded fp32 operation unless it says fp64.
+ *   minibatch   rows [lo, hi); every read sees the matrix as it was before the minibatch (Jacobi inside a batch, as for option 5),
+ *               later minibatches see its new rows.  x is that pre-batch matrix, STEP the epoch's fp32 step;
+ *   pair(i, j)  t_d = x_id - x_jd; a = the sum of t_d * t_d (rounded products) in the engine's per-pair order: the balanced
+ *               adjacent-pair tree over next_pow2(D) zero-padded terms of the step kernels (ORC_ORDER_TREE of the test oracle);
+ *   scale(v)    max(v, -5) then min(., 5), a NaN becoming -5: the rule of options 5 / 8 / 11;
+ *   attraction  A from +0 over the CSR neighbours j of i in row order, duplicates included (:378-393):
+ *               d1 = (float)(-2.0 / (1.0 + (double)a)), d2 = (float)(2.0 / ((double)a * (1.0 + (double)a))) (fp64, narrowed),
+ *               f_d = scale(t_d * d1) - scale(t_d * d2), A_d = A_d + STEP * f_d;
+ *   repulsion   the columns j = 0 .. n-1 are cut into pieces of F2V_EXACT_PIECE consecutive ids, the pieces into spans of
+ *               F2V_EXACT_SPAN consecutive pieces.  A piece is summed from +0 in ascending j, skipping j == i:
+ *               P_d = P_d + STEP * scale(t_d * d1), d1 = (float)(2.0 / ((double)a * (1.0 + (double)a))) (:395-422); a span is the
+ *               sequential sum from +0 of its piece sums in ascending order; nothing is added for a column past n - 1;
+ *   row         Y = A, then Y = Y + S_s for the spans s in ascending order; the new x_i = x_i + Y (:429-431);
+ *   epochs      STEP_0 = 1.0f, STEP_(e+1) = (float)((double)STEP_e * 0.999) (:436).  The handle parameter "exact_epoch" (default 0,
+ *               get and set) is the index e of the next call's first epoch, STEP_e formed by e such multiplications; a call of
+ *               `iters` epochs advances it by `iters`: two calls of 5 epochs equal one of 10 bit for bit, setting it to 0 starts over;
+ *   rand()      no draw is made: the handle's stream stays where it was.
+ * (The reference sums a row in one fp32 accumulator: neighbours, then j < i, then j > i.  The pieces and spans are what lets the
+ * n columns of a row be summed side by side; after a few epochs the two orders differ by some 1e-5: DESIGN.md section 14.)
+ * Launches: per minibatch one pair kernel (grid: groups of "exact_rows" rows -- 0 = automatic | 4 | 8 | 16, placement only, it never
+ * changes a bit -- times spans + 1 slices; where D is a multiple of 4 up to 256 and "quarter_wave" is on, minibatches of
+ * "exact_quarter_min" rows or more, default 1024, 0 = all, run it in the quarter-wave layout: the same bits; "last_exact_rows" and
+ * "last_exact_quarter" answer what the last minibatch ran with) and one finish kernel, plain launches on the handle's stream without in-grid waits: no
+ * snapshot is taken, nothing is recovered, "last_train_form" answers 0.  seconds_out, f2v_stats.device_seconds and "epoch_marks" keep
+ * their meaning; step_launches counts the pair kernel's launches, rows the rows updated, nnz the CSR nonzeros visited.  Workspace,
+ * allocated on first use (grown for a larger minibatch) and freed by f2v_destroy: min(batch, n) x (spans + 1) x D floats, spans =
+ * ceil(n / (F2V_EXACT_PIECE * F2V_EXACT_SPAN)) -- a row's span sums and its attraction part.
+ * Single GPU, f2v_train only: f2v_train_sharded, f2v_minibatch_step and f2v_minibatch_step_at answer option 1 with F2V_EINVAL.
+ * The objective, f2v_objective(h, 1, ns ignored, out), the reference's own loglike of this function (:387, :407, :416; EPS 1e-6):
+ *   attraction = sum over the nonzeros (i, j) of flog(1 + a),  repulsion = -sum over all ordered pairs i != j of
+ *   [flog(1e-6 + a) - flog(1 + a)],  positive_pairs = nnz, negative_pairs = n (n - 1), loss = attraction + repulsion;
+ *   a is the fp32 pair sum above, converted exactly; everything else is fp64.  flog(v), for the positive normal numbers that occur
+ *   here, is the natural logarithm computed from rounded fp64 additions, multiplications and one division in this order (fdlibm's
+ *   e_log.c without its special cases; within 1 ulp of log): v = 2^k * m with m in [1, 2); if m > 1.4142135623730951 then m = m * 0.5
+ *   and k = k + 1; f = m - 1; s = f / (2 + f); z = s * s; w = z * z; t1 = w * (L2 + w * (L4 + w * L6)); t2 = z * (L1 + w * (L3 + w *
+ *   (L5 + w * L7))); R = t2 + t1; h = (0.5 * f) * f; flog = k * 6.93147180369123816490e-01 - ((h - (s * (h + R) + k *
+ *   1.90821492927058770002e-10)) - f); L1 .. L7 = 6.666666666666735130e-01, 3.999999999940941908e-01, 2.857142874366239149e-01,
+ *   2.222219843214978396e-01, 1.818357216161805012e-01, 1.531383769920937332e-01, 1.479819860511658591e-01 -- so that a host
+ *   restatement reproduces the value bit for bit (a library's log differs from another's in the last place);
+ *   order of the fp64 sums: per row, the repulsion terms in pieces of 64 columns, each from +0 in ascending j skipping i, the piece
+ *   sums added sequentially from +0 in ascending order; the attraction terms of a row likewise in pieces of 64 neighbours in row
+ *   order; the row sums in pieces of 64 consecutive rows, each from +0, and those piece sums sequentially from +0.
+ * "loss_every" / f2v_train_losses work for option 1 with the same guarantee as for the others: equal, bit for bit, to f2v_objective
+ * after the same epochs in separate calls.  Workspace of the objective: 2 n + 2 ceil(n / 64) doubles.
+ * The two constants are part of the summation order. */
+#define F2V_EXACT_PIECE 64 /* columns per piece */
+#define F2V_EXACT_SPAN 16  /* pieces per span: 1024 columns */
 
 /* ---- nearest neighbours ---------------------------------------------------------------------------------------------------
  * Which rows of the matrix are most similar to a query?  Three similarities between a query vector q and row c of the matrix, all
