@@ -20,6 +20,7 @@ PAIR_HADAMARD, PAIR_L1, PAIR_L2, PAIR_AVERAGE = 0, 1, 2, 3
 LABEL_NONE = 0xFFFFFFFF  # F2V_LABEL_NONE: the vertex takes no part in a separation score
 SEPARATION_MAX_CLUSTERS, SEPARATION_PIECE, SEPARATION_SPAN = 1024, 64, 64
 PCA_PIECE, TRUST_MAX_DIM = 4096, 512
+FOLD_INIT_MEAN, FOLD_INIT_RANDOM, FOLD_INIT_GIVEN = 0, 1, 2
 
 u32p = C.POINTER(C.c_uint32)
 f32p = C.POINTER(C.c_float)
@@ -56,6 +57,10 @@ class PcaInfo(C.Structure):  # f2v_pca_t
 class TrustInfo(C.Structure):  # f2v_trust_t
     _fields_ = [("trustworthiness", C.c_double), ("continuity", C.c_double), ("overlap", C.c_double), ("seconds", C.c_double),
                 ("penalty_x", C.c_uint64), ("penalty_y", C.c_uint64), ("hits", C.c_uint64)]
+
+
+class FoldInfo(C.Structure):  # f2v_fold_t
+    _fields_ = [("seconds", C.c_double), ("pairs", C.c_uint64), ("resident", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 # every entry point declared in include/f2v.h: name -> (restype, argtypes)
@@ -104,6 +109,7 @@ SIGNATURES = {
     "f2v_davies_bouldin": (C.c_int, [C.c_void_p, u32p, C.c_uint32, f64p, f32p, f64p, C.POINTER(C.c_uint64), f64p]),
     "f2v_pca": (C.c_int, [C.c_void_p, C.c_uint32, f32p, f64p, f64p, f64p, C.POINTER(PcaInfo)]),
     "f2v_trustworthiness": (C.c_int, [C.c_void_p, f32p, C.c_uint32, C.c_uint32, u32p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(TrustInfo)]),
+    "f2v_fold_in": (C.c_int, [C.c_void_p, C.c_int, u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_int, f32p, C.c_uint64, C.c_uint64, f32p, C.POINTER(FoldInfo)]),
     "f2v_push_export": (C.c_int, [C.c_void_p, C.c_void_p]),
     "f2v_push_attach": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "f2v_push_selftest": (C.c_int, [C.c_void_p]),

@@ -9,7 +9,9 @@
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
+#include <fstream>
 #include <iostream>
+#include <sstream>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -349,6 +351,46 @@ class algorithms {
         printf("TrustWorthiness: %.17g Continuity: %.17g\n", t.trustworthiness, t.continuity);
         printf("Layout: d=%u neighbours=%u samples=%u :EXPLAINED-VARIANCE: %.17g :OVERLAP: %.17g :SWEEPS: %u\n", d, k, sample ? (uint32_t)ids.size() : rows,
                info.total_variance > 0 ? kept / info.total_variance : 0.0, t.overlap, info.sweeps);
+    }
+
+    // -foldin <file>: vectors for vertices that were not in the graph (f2v_fold_in).  Each line of the file is "<name> <nbr> <nbr> ..."
+    // with 1-based ids of existing vertices, in summation order; the output "<embd output name>.fold" is .embd text -- "<m> <D>", then
+    // per line the name and the vector's values with %g and a trailing space.  The negative samples are seeded by -seed.
+    void foldIn(const std::string &path, int option, uint32_t iters, INDEXTYPE ns, VALUETYPE lr, int init_kind, uint64_t seed) {
+        std::ifstream in(path);
+        if (!in) throw std::runtime_error("-foldin: cannot read " + path);
+        std::vector<std::string> names;
+        std::vector<uint32_t> rowptr{0}, colids;
+        std::string line;
+        while (std::getline(in, line)) {
+            std::istringstream fields(line);
+            std::string name;
+            if (!(fields >> name)) continue;
+            long long id;
+            while (fields >> id) {
+                if (id < 1 || id > (long long)rows) throw std::runtime_error("-foldin: " + name + " names vertex " + std::to_string(id) + " of " + std::to_string(rows));
+                colids.push_back((uint32_t)(id - 1));
+            }
+            if (!fields.eof()) throw std::runtime_error("-foldin: the line of " + name + " holds something that is not a vertex id");
+            names.push_back(name);
+            rowptr.push_back((uint32_t)colids.size());
+        }
+        const uint32_t m = (uint32_t)names.size();
+        std::vector<float> y((size_t)m * DIM);
+        f2v_fold_t info{};
+        colids.push_back(0);  // (an address where every list is empty)
+        check(f2v_fold_in(h, option, rowptr.data(), colids.data(), m, iters, ns, lr, init_kind, nullptr, seed, 0, y.data(), &info));
+        const std::string name = last_output + ".fold";
+        FILE *f = fopen(name.c_str(), "w");
+        if (!f) throw std::runtime_error("cannot write " + name);
+        fprintf(f, "%u %u\n", m, (unsigned)DIM);
+        for (uint32_t q = 0; q < m; q++) {
+            fprintf(f, "%s ", names[q].c_str());
+            for (uint32_t d = 0; d < DIM; d++) fprintf(f, "%g ", (double)y[(size_t)q * DIM + d]);
+            fputc('\n', f);
+        }
+        if (fclose(f) != 0) throw std::runtime_error("cannot write " + name);
+        printf("Fold-in: %u vertices, %u iterations, %llu interactions in %.6f s on the GPU -> %s\n", m, iters, (unsigned long long)info.pairs, info.seconds, name.c_str());
     }
 
     // writeToFile, sample/algorithms.h:118-136 (file name rule in f2v_output_name)

@@ -14,7 +14,8 @@
 // -classify <labels file> [-classify-frac <f>] [-classify-splits <s>] (after training: node-classification F1 of the embedding),
 // -separation <labels file | kmeans> [-separation-sample <n>] (after training: the labelling's silhouette and Davies-Bouldin score),
 // -layout <d> [-layout-neighbours <k>] [-layout-sample <n>] (after training: the d-dimensional principal-component layout as
-// "<embd output name>.lay" and its trustworthiness and continuity).
+// "<embd output name>.lay" and its trustworthiness and continuity), -foldin <file> [-foldin-iters <n>] [-foldin-init mean|random] (after
+// training, or on -init <file> with -iter 0: vectors for new vertices, one "<name> <nbr> <nbr> ..." line each, as "<embd output name>.fold").
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -36,7 +37,8 @@ struct Settings {
     std::string input, output, init;
     long batch = 384, iter = 1200, threads = (long)std::thread::hardware_concurrency(), dim = 128, nsamples = 5, option = 5, bs = 0;
     long device = 0, seed = 1, cache = 0, binout = 0, fastrng = 0, notext = 0, gpus = 1, samegpu = 0, loss = 0, nearest = 0, cluster = 0, cluster_iters = 300, cluster_restarts = 10;
-    std::string metric, classify, separation;
+    std::string metric, classify, separation, foldin, foldin_init = "mean";
+    long foldin_iters = 300;
     long classify_splits = 10, separation_sample = 0, layout = 0, layout_neighbours = 5, layout_sample = 0;
     double gamma = 1.0, lr = 0.02, classify_frac = 0.1;
 };
@@ -114,6 +116,9 @@ int main(int argc, char *argv[]) {
         {"-layout", Kind::Integer, &s.layout, "<int>, d in 1..dim: after training write <output file>.lay, one line per vertex \"v y1 ... yd\" (1-based ids): the matrix projected onto its first d principal components on the GPU, and print \"TrustWorthiness: <t> Continuity: <c>\" of that picture and its explained-variance share (one GPU). (default:0)"},
         {"-layout-neighbours", Kind::Integer, &s.layout_neighbours, "<int>, k in 1..128, below half the number of vertices: the neighbourhood size of the -layout scores. (default:5)"},
         {"-layout-sample", Kind::Integer, &s.layout_sample, "<int>, score the -layout over that many vertices chosen by -seed, each ranked against all vertices; 0 = every vertex (O(N^2 dim) work). (default:0)"},
+        {"-foldin", Kind::Text, &s.foldin, "<string>, a file of lines \"<name> <nbr> <nbr> ...\" (1-based ids of existing vertices): after training -- or on -init <file> with -iter 0 -- give every line's new vertex a vector by running the option's update for it against the finished matrix on the GPU, and write <output file>.fold: \"<m> <dim>\", then per line the name and the vector (options 5, 6, 8, 9, 11; one GPU; samples seeded by -seed; -nsamples and -lr as in training)."},
+        {"-foldin-iters", Kind::Integer, &s.foldin_iters, "<int>, epochs of a -foldin vertex. (default:300)"},
+        {"-foldin-init", Kind::Text, &s.foldin_init, "<string>, initial vector of a -foldin vertex: mean (of its neighbours' vectors) | random. Under the sigmoid options (6, 9) a random start moves slowly: keep mean. (default:mean)"},
         {"-metric", Kind::Text, &s.metric, "<string>, similarity of -nearest: dot | l2 | cos. (default: l2 for options 5, 8, 11, dot for the sigmoid options)"},
     };
     const size_t nflags = sizeof flags / sizeof flags[0];
@@ -236,6 +241,23 @@ int main(int argc, char *argv[]) {
         printf("-layout is not available with -gpus > 1 (it projects and scores one GPU's matrix).\n");
         return 1;
     }
+    const int foldin_init = s.foldin_init == "mean" ? F2V_FOLD_INIT_MEAN : s.foldin_init == "random" ? F2V_FOLD_INIT_RANDOM : -1;
+    if (!s.foldin.empty() && foldin_init < 0) {
+        printf("-foldin-init must be mean or random.\n");
+        return 1;
+    }
+    if (!s.foldin.empty() && (s.foldin_iters < 0 || s.foldin_iters > 0x7FFFFFFF)) {
+        printf("-foldin-iters must be a non-negative number of epochs.\n");
+        return 1;
+    }
+    if (!s.foldin.empty() && (s.option == 1 || s.option == 7 || s.option == 10)) {
+        printf("-foldin is available with options 5, 6, 8, 9 and 11 (a new vertex has no walks, and option 1 repels it from every vertex).\n");
+        return 1;
+    }
+    if (!s.foldin.empty() && s.gpus > 1) {
+        printf("-foldin is not available with -gpus > 1 (it reads one GPU's matrix).\n");
+        return 1;
+    }
     std::vector<VALUETYPE> seconds;
     int rank = 0;
     std::string meet;  // directory the ranks of a -gpus run meet in
@@ -283,6 +305,7 @@ int main(int argc, char *argv[]) {
             if (!s.classify.empty() && rank == 0) algo.classify(s.classify, s.classify_frac, (uint32_t)s.classify_splits, (uint64_t)s.seed);
             if (!s.separation.empty() && rank == 0) algo.separation(s.separation, (uint32_t)s.separation_sample, (uint64_t)s.seed);
             if (s.layout > 0 && rank == 0) algo.layout((uint32_t)s.layout, (uint32_t)s.layout_neighbours, (uint32_t)s.layout_sample, (uint64_t)s.seed);
+            if (!s.foldin.empty() && rank == 0) algo.foldIn(s.foldin, (int)s.option, (uint32_t)s.foldin_iters, (INDEXTYPE)s.nsamples, (VALUETYPE)s.lr, foldin_init, (uint64_t)s.seed);
             const double t = algo.gpu_train_seconds;
             if (rank == 0 && s.gpus == 1)
                 printf("GPU epoch loop: %.6f s, %.4g nnz/s, %.1f GB/s algorithmic\n", t, t > 0 ? algo.stats.nnz / t : 0.0,

@@ -38,6 +38,7 @@
 #include "f2v_separation.hip.h"
 #include "f2v_layout.hip.h"
 #include "f2v_exact.hip.h"
+#include "f2v_foldin.hip.h"
 
 using namespace f2v;
 
@@ -273,6 +274,15 @@ struct f2v_ctx {
         bool last_quarter = false;    // "last_exact_quarter"
         uint64_t epoch = 0;
     } ex;
+    // fold-in (f2v_fold_in): the workspace f2v.h states, allocated on first use and grown for a larger call; "fold_chunk": vertices per
+    // launch, "fold_resident" (-1 = automatic | 0): the form that keeps a workgroup's lists in LDS was measured slower and is not built
+    struct Fold {
+        DevBuf<uint32_t> d_rowptr, d_ids, d_order;
+        DevBuf<float> d_in, d_out;
+        DevTimer timer;
+        uint32_t chunk = 65536;
+        int resident = -1;
+    } fold;
     uint32_t last_wide_width = 0;  // the layout width of the last wide-form f2v_train ("last_wide_width")
     bool last_wide_early = false;  // ... and whether it ran the kernel's EARLY form ("last_wide_early")
     int last_train_form = 0;  // how the last f2v_train launched: 0 one launch per minibatch, 1 chained, 2 chained in the wide form ("last_train_form")
@@ -2257,6 +2267,10 @@ const Param kParams[] = {
     {"last_exact_quarter", F2V_GET(ex.last_quarter)},
     // the index e of the first epoch of the next f2v_train(option 1): STEP_e; a call of `iters` epochs advances it by `iters`
     {"exact_epoch", F2V_FIELD(ex.epoch), kValue, kKeep, in<0, 0x7FFFFFFF>, "exact_epoch must be 0..2^31-1"},
+    // new vertices per launch of f2v_fold_in: bounds its workspace (two chunk x D matrices); results do not depend on it
+    {"fold_chunk", F2V_FIELD(fold.chunk), kValue, kKeep, in<1, 1048576>, "fold_chunk must be 1..1048576"},
+    // f2v_fold_in: 0 = every epoch gathers a vertex's list rows from the caches, -1 = automatic (the same); 1, rows staged in LDS once, was measured slower and is not built
+    {"fold_resident", F2V_FIELD(fold.resident), kValue, kKeep, in<-1, 0>, "fold_resident must be -1 (automatic) or 0: the resident form measured slower and is not part of this build"},
     {"push_fused", F2V_FIELD(push.fused), kFlag},
     {"push_timeout_ms", F2V_FIELD(push.timeout_ms), kValue, kKeep, in<1, 600000>, "push_timeout_ms must be 1..600000"},
     // takes effect at the next f2v_push_export; read: what the exchange in place runs with
@@ -4237,6 +4251,126 @@ int f2v_davies_bouldin(f2v_handle c, const uint32_t *labels, uint32_t n_clusters
     double seconds = 0.0;
     F2VC(sp.timer.seconds(&seconds));
     if (seconds_out) *seconds_out = seconds;
+    return F2V_OK;
+}
+
+}  // extern "C"
+
+// ---- fold-in (f2v_foldin.hip.h; definition in include/f2v.h) ---------------------------------------------------------------------
+namespace {
+
+int launch_fold_q(f2v_ctx *c, int math, uint32_t width, const FoldArgs &a, uint32_t blocks, size_t lds) {
+    const uint32_t threads = 64u * (uint32_t)c->waves_per_block;
+    F2VC((dispatch_subwave<16, false>(c, math, width, [&](auto O, auto L, auto N, auto, auto FL) {
+        hipLaunchKernelGGL((fold_q_kernel<decltype(O)::value, decltype(L)::value, decltype(N)::value, decltype(FL)::value>), dim3(blocks), dim3(threads), lds,
+                           c->stream, a);
+    })));
+    HIPC(hipGetLastError());
+    return F2V_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int f2v_fold_in(f2v_handle c, int option, const uint32_t *q_rowptr, const uint32_t *q_colids, uint32_t m, uint32_t iters, uint32_t ns, float lr, int init_kind,
+                const float *init, uint64_t seed, uint64_t index_base, float *y_out, f2v_fold_t *info) {
+    if (!c) return fail(F2V_EINVAL, "f2v_fold_in: null argument");
+    const int math = math_of_option(option);
+    if (math != 5 && math != 6) return fail(F2V_EINVAL, "f2v_fold_in: option %d (options 5, 8, 11 and 6, 9 fold in)", option);
+    if (init_kind != F2V_FOLD_INIT_MEAN && init_kind != F2V_FOLD_INIT_RANDOM && init_kind != F2V_FOLD_INIT_GIVEN)
+        return fail(F2V_EINVAL, "f2v_fold_in: unknown init_kind %d", init_kind);
+    if (init_kind == F2V_FOLD_INIT_GIVEN && !init && m) return fail(F2V_EINVAL, "f2v_fold_in: F2V_FOLD_INIT_GIVEN without init");
+    if (c->n < 1) return fail(F2V_EINVAL, "f2v_fold_in: no vertex to sample");
+    const unsigned __int128 counters = ((unsigned __int128)index_base + m) * iters, counter_limit = (unsigned __int128)1 << 62;
+    if (ns != 0 && (counters >= counter_limit || counters * ns >= counter_limit))
+        return fail(F2V_EINVAL, "f2v_fold_in: (index_base + m) * iters * ns reaches 2^62");
+    if (info) *info = f2v_fold_t{};
+    if (m == 0 && c->have_x) return F2V_OK;
+    if (m && (!q_rowptr || !y_out)) return fail(F2V_EINVAL, "f2v_fold_in: null argument");
+    for (uint32_t q = 0; q < m; q++)
+        if (q_rowptr[q + 1] < q_rowptr[q]) return fail(F2V_EINVAL, "f2v_fold_in: q_rowptr descends at vertex %u", q);
+    const uint32_t base = m ? q_rowptr[0] : 0u, total = m ? q_rowptr[m] - base : 0u;
+    if (total && !q_colids) return fail(F2V_EINVAL, "f2v_fold_in: null argument");
+    for (uint32_t k = 0; k < total; k++)
+        if (q_colids[base + k] >= c->n) return fail(F2V_EINVAL, "f2v_fold_in: q_colids[%u] = %u is not one of the %u vertices", base + k, q_colids[base + k], c->n);
+    F2VC(settled_enter(c, "f2v_fold_in"));
+    if (m == 0) return F2V_OK;
+
+    f2v_ctx::Fold &w = c->fold;
+    const uint32_t n = c->n, D = c->D, chunk = std::min(w.chunk, m);
+    const uint32_t width = subwave_width(c), wpb = (uint32_t)c->waves_per_block;
+    const uint32_t ipb = items_per_wave(width) * wpb;  // vertices per workgroup
+    const size_t table_bytes = math == 5 ? 0 : kSmTableSize * sizeof(float);  // the quarter-wave kernel's dynamic LDS: the sigmoid table
+
+    // the lists, rebased to 0; per chunk the vertices by descending list length (stable: placement only, and the same every call)
+    std::vector<uint32_t> rowptr(m + 1), order(m);
+    for (uint32_t q = 0; q <= m; q++) rowptr[q] = q_rowptr[q] - base;
+    uint64_t pairs = 0;
+    for (uint32_t q0 = 0; q0 < m; q0 += chunk) {
+        const uint32_t cq = std::min(chunk, m - q0);
+        uint32_t *o = order.data() + q0;
+        for (uint32_t r = 0; r < cq; r++) o[r] = q0 + r;
+        std::stable_sort(o, o + cq, [&](uint32_t x, uint32_t y) { return rowptr[x + 1] - rowptr[x] > rowptr[y + 1] - rowptr[y]; });
+    }
+    for (uint32_t q = 0; q < m; q++) pairs += ((uint64_t)(rowptr[q + 1] - rowptr[q]) + ns) * iters;
+
+    const char *what = "fold-in";
+    F2VC(w.d_rowptr.reserve(c, (size_t)m + 1, what));
+    F2VC(w.d_ids.reserve(c, total, what));
+    F2VC(w.d_order.reserve(c, m, what));
+    F2VC(w.d_in.reserve(c, (size_t)chunk * D, what));
+    F2VC(w.d_out.reserve(c, (size_t)chunk * D, what));
+    HIPC(hipMemcpyAsync(w.d_rowptr, rowptr.data(), ((size_t)m + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (total) HIPC(hipMemcpyAsync(w.d_ids, q_colids + base, (size_t)total * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(w.d_order, order.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+
+    FoldArgs a{};
+    a.X = c->d_X[c->cur];
+    a.rowptr = w.d_rowptr;
+    a.ids = w.d_ids;
+    a.Y0 = w.d_in;
+    a.Y = w.d_out;
+    a.sm_table = c->d_table;
+    a.seed_mix = mix64_host(seed);
+    a.index_base = index_base;
+    a.n = n;
+    a.D = D;
+    a.iters = iters;
+    a.ns = ns;
+    a.lr = lr;
+    double seconds = 0.0;
+    for (uint32_t q0 = 0; q0 < m; q0 += chunk) {
+        const uint32_t cq = std::min(chunk, m - q0);
+        a.q0 = q0;
+        a.count = cq;
+        if (init_kind == F2V_FOLD_INIT_GIVEN)
+            HIPC(hipMemcpyAsync(w.d_in, init + (size_t)q0 * D, (size_t)cq * D * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        F2VC(w.timer.start(c->stream));
+        if (init_kind != F2V_FOLD_INIT_GIVEN) {
+            hipLaunchKernelGGL(fold_init_kernel, dim3((uint32_t)(((size_t)cq * D + 255) / 256)), dim3(256), 0, c->stream, a, init_kind, math == 5 ? 0 : 1);
+            HIPC(hipGetLastError());
+        }
+        if (iters > 0 && width != 0) {
+            a.order = w.d_order + q0;
+            F2VC(launch_fold_q(c, math, width, a, (cq + ipb - 1) / ipb, table_bytes));
+        } else if (iters > 0) {
+            a.order = w.d_order + q0;
+            F2VC(dispatch_math_layout(c, math, [&](auto O, auto V, auto E) {
+                hipLaunchKernelGGL((fold_kernel<decltype(O)::value, decltype(V)::value, decltype(E)::value>), dim3((cq + wpb - 1) / wpb), dim3(64 * wpb), 0, c->stream, a);
+            }));
+            HIPC(hipGetLastError());
+        }
+        F2VC(w.timer.stop(c->stream));
+        HIPC(hipMemcpyAsync(y_out + (size_t)q0 * D, iters > 0 ? w.d_out : w.d_in, (size_t)cq * D * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+        F2VC(w.timer.seconds(&seconds));
+    }
+    if (info) {
+        info->seconds = seconds;
+        info->pairs = pairs;
+        info->resident = 0;  // (the form is not built: "fold_resident")
+    }
     return F2V_OK;
 }
 

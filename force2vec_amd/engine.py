@@ -31,6 +31,11 @@ PcaInfo = namedtuple("PcaInfo", "total_variance seconds sweeps converged")
 Trust = namedtuple("Trust", "trustworthiness continuity overlap penalty_x penalty_y hits seconds samples_x samples_y")
 
 
+# Engine.fold_in (include/f2v.h: fold-in)
+FoldInfo = namedtuple("FoldInfo", "seconds pairs resident")
+FOLD_INITS = {"mean": _lib.FOLD_INIT_MEAN, "random": _lib.FOLD_INIT_RANDOM}
+
+
 # Engine.logreg_fit / Engine.classify / Engine.link_predict (include/f2v.h: logistic regression)
 LogregModel = namedtuple("LogregModel", "weights feature loss gnorm_inf iterations evaluations converged seconds")
 F1 = namedtuple("F1", "micro macro")
@@ -78,6 +83,7 @@ class Engine:
         self.last_nearest_seconds = self.last_kmeans_seconds = self.last_logreg_seconds = 0.0  # device time of the last query / clustering / regression call
         self.last_separation_seconds = 0.0  # ... / silhouette or Davies-Bouldin call
         self.last_layout_seconds = 0.0  # ... / pca or trustworthiness call
+        self.last_fold_seconds = 0.0  # ... / fold_in call
 
     def _ck(self, rc):
         check(rc, self._L)  # the error text lives in the library that returned the code
@@ -397,6 +403,47 @@ class Engine:
         self._ck(self._L.f2v_trustworthiness(self._h, _f32(Y), Y.shape[1], k, _u32(q) if q is not None else None, nq, u64(px), u64(py), C.byref(out)))
         self.last_layout_seconds = out.seconds
         return Trust(out.trustworthiness, out.continuity, out.overlap, out.penalty_x, out.penalty_y, out.hits, out.seconds, px, py)
+
+    # -- fold-in (include/f2v.h: definition; a function of the matrix, the lists, option, iters, ns, lr, init, seed and index_base alone) --
+    def fold_in(self, rowptr, colids=None, option=5, iters=300, ns=5, lr=0.02, init="mean", seed=1, index_base=0, details=False):
+        """Vectors for m new vertices whose neighbours are existing vertices, on the GPU: `iters` epochs of the option's row update
+        against the matrix as it stands, every existing row held fixed -> float32 [m, dim], or with details=True (that,
+        FoldInfo(seconds, pairs, resident)).  The lists are CSR-like (rowptr uint32 [m + 1], colids: 0-based ids below n, in summation
+        order, duplicates kept), or `rowptr` is a list of m id lists and colids None.  init: "mean" (the neighbours' mean; a vertex
+        without neighbours starts random), "random", or float32 [m, dim] of the caller's own.  Vertex q draws its negative samples as
+        vertex index_base + q of `seed`: a call cut into pieces with matching index_base returns the same bits.  `last_fold_seconds`
+        keeps the device time."""
+        if colids is None:
+            lists = [np.asarray(l, dtype=np.uint32).reshape(-1) for l in rowptr]
+            rowptr = np.zeros(len(lists) + 1, dtype=np.uint32)
+            if lists:
+                rowptr[1:] = np.cumsum([len(l) for l in lists])
+            colids = np.concatenate(lists) if lists else np.zeros(0, dtype=np.uint32)
+        rowptr = np.ascontiguousarray(rowptr, dtype=np.uint32).reshape(-1)
+        colids = np.ascontiguousarray(colids, dtype=np.uint32).reshape(-1)
+        if len(rowptr) < 1:
+            raise ValueError("fold_in: rowptr holds m + 1 offsets")
+        m = len(rowptr) - 1
+        if m and len(colids) < int(rowptr[-1]):
+            raise ValueError("fold_in: rowptr names %d ids, colids holds %d" % (int(rowptr[-1]), len(colids)))
+        y0 = None
+        if isinstance(init, str):
+            if init not in FOLD_INITS:
+                raise ValueError("fold_in: init must be one of %s or an array [m, dim]" % sorted(FOLD_INITS))
+            kind = FOLD_INITS[init]
+        else:
+            y0 = np.ascontiguousarray(init, dtype=np.float32)
+            if y0.shape != (m, self.dim):
+                raise ValueError("fold_in: init must be [%d, %d]" % (m, self.dim))
+            kind = _lib.FOLD_INIT_GIVEN
+        if len(colids) == 0:
+            colids = np.zeros(1, dtype=np.uint32)  # (an address for the library's null check: no id is read)
+        y = np.empty((m, self.dim), dtype=np.float32)
+        info = _lib.FoldInfo()
+        self._ck(self._L.f2v_fold_in(self._h, option, _u32(rowptr), _u32(colids), m, iters, ns, lr, kind, _f32(y0) if y0 is not None else None,
+                                     seed, index_base, _f32(y), C.byref(info)))
+        self.last_fold_seconds = info.seconds
+        return (y, FoldInfo(info.seconds, info.pairs, bool(info.resident))) if details else y
 
     # -- logistic regression (include/f2v.h: definition; a function of the matrix, the samples, the targets and the weights alone) --
     def _samples(self, ids, pairs, feature):

@@ -648,6 +648,75 @@ F2V_API int f2v_trustworthiness(f2v_handle h, const float *Y /* n x d2 */, uint3
                         uint32_t nq, uint64_t *penalty_x_out /* per sample, may be NULL */, uint64_t *penalty_y_out /* per sample, may be NULL */,
                         f2v_trust_t *out);
 
+/* ---- fold-in ---------------------------------------------------------------------------------------------------------------
+ * What is the vector of a vertex that was not in the graph when it was trained?  A new vertex whose neighbours are all existing
+ * vertices is a row whose update reads only frozen rows, so the training rule itself answers: f2v_fold_in runs `iters` epochs of the
+ * step kernels' row update for each of m new vertices against the matrix X as it stands, every other row held fixed.  New vertices do
+ * not see each other, so each is independent of the others and all its epochs run inside one launch.  The result is a function of
+ * (X, the lists, option, iters, ns, lr, init, seed, index_base) alone: bitwise identical between calls, handles and GPUs and under
+ * every tunable; no float atomics, no in-grid waits.  Every operation below is one rounded fp32 operation unless it says fp64.
+ *   matrix      X as f2v_get_embeddings would return it (pending minibatches are committed first); the call runs on the handle's stream
+ *               and changes neither the matrices nor the rand() stream nor any later training result; on a handle attached to a push
+ *               exchange it reads this rank's replica;
+ *   lists       vertex q of the call has the neighbours q_colids[q_rowptr[q] .. q_rowptr[q + 1]), ids of the n existing vertices, in the
+ *               caller's order -- the summation order --, duplicates kept, deg(q) counting them; an empty list is legal.  Q = index_base
+ *               + q is the vertex's index for every random draw: a call cut into several calls with matching index_base gives the
+ *               same bits;
+ *   pair(y, j)  the pair sum a over t_d (below) in the engine's per-pair order: the balanced adjacent-pair tree over next_pow2(D)
+ *               zero-padded terms of the step kernels (ORC_ORDER_TREE of the test oracle);
+ *   scale(v)    max(v, -5) then min(., 5), a NaN becoming -5;
+ *   negatives   s(Q, e, k) = mix64(mix64(seed) ^ ((Q * iters + e) * ns + k)) % n for k = 0 .. ns-1, mix64 the splitmix64 finaliser of
+ *               the objective above, 64-bit wrapping arithmetic: computed in the kernel, nothing is uploaded and nothing is drawn from
+ *               the handle's stream; self-samples cannot occur (the vertex is not among the n);
+ *   epoch       y^(e+1) from y = y^e, e = 0 .. iters-1: what the step kernels compute for a row whose pre-batch value is y, whose CSR
+ *               row is the list, with "hub_chunk" = 0 (one sequential pass in list order) and the negatives s(Q, e, .), at the call's lr:
+ *     t-distribution options (5, 8, 11; sample/algorithms.cpp:588-639): F from +0; for every list entry j in order t_d = y_d - x_jd,
+ *               a = the pair sum of t_d * t_d, d1 = (float)(-2.0 / (1.0 + (double)a)) (fp64, narrowed), F_d = F_d + lr * scale(t_d * d1);
+ *               then for every negative j = s(Q, e, k) in order the same with d1 = (float)(2.0 / ((double)a * (1.0 + (double)a)));
+ *               y^(e+1)_d = y_d + F_d;
+ *     sigmoid options (6, 9; :833-921): degi = (float)(1.0 / (double)(deg(q) + 1)), c0 = (double)(lr * degi); P = y; for every list
+ *               entry j in order a = the pair sum of y_d * x_jd, sm = the 2048-entry table's sigmoid of a (f2v_sm_table; 1 above 6, 0
+ *               below -6), coef = (1.0 - (double)sm) * c0 (fp64), P_d = (float)((double)x_jd * coef + (double)P_d); then for every
+ *               negative in order w = lr * sm, P_d = P_d - w * x_jd; y^(e+1) = P.  (Both are `oracle.row` of the test oracle with
+ *               ORDER_TREE and chunk 0 on the graph with the vertex appended as row n.)
+ *               Every other option (1, 2-4, 7, 10) is F2V_EINVAL: walks for a vertex outside the CSR are out of scope;
+ *   initial     F2V_FOLD_INIT_GIVEN: the caller's rows.  F2V_FOLD_INIT_RANDOM: y_d = v for the sigmoid options, 2v - 1 for the t options,
+ *               v = (mix64(mix64(seed) ^ (2^63 | (Q * D + d))) >> 40) * 2^-24 (both exact in fp32).  F2V_FOLD_INIT_MEAN (the default):
+ *               y_d = (float)(S_d / (double)deg), S_d the sequential fp64 sum from +0 of (double)x_jd in list order; a vertex with an
+ *               empty list gets the RANDOM rule.  iters = 0 returns the initial vectors.
+ *               (Why the mean: cora, option 5, one tenth of the vertices held out and folded in for 600 epochs, classified by a model
+ *               fitted on the others: 0.83 from the mean, 0.76 from a random start, 0.87 trained jointly.  Under option 6 a random
+ *               start reaches 0.25 only -- the sigmoid attraction is divided by deg + 1 and moves a vector slowly -- where the mean
+ *               start gives 0.59 and the mean alone, iters = 0, 0.76 in the CPU experiment: DESIGN.md section 15.)
+ * Launches: the vertices run in chunks of "fold_chunk" (default 65536), per chunk one kernel for the initial vectors (MEAN, RANDOM) and
+ * one or two for the epochs, a chunk's vertices placed by descending list length (placement only).  Where D is a multiple of 4 up to
+ * 256 and "quarter_wave" is on, a vertex is a quarter-wave of the step kernels' layout, else a wavefront; all epochs run inside the
+ * launch with the vector in registers, the list's rows gathered four (a wavefront: eight) at a time and read again through the caches
+ * every epoch.  "fold_resident" (-1 = automatic, the default | 0; both select that form): a resident form, which staged a workgroup's
+ * list rows once in LDS and reread them there, was built and measured 7-11 % slower where it applies (DESIGN.md section 15,
+ * profiles/foldin_time.txt); it is not part of the library, 1 is F2V_EINVAL and info->resident is always 0.  A vertex's epochs and
+ * list entries are one sequential chain (about 0.25 us per entry and epoch at D = 128): a call lasts at least as long as its longest
+ * list.  info->pairs: the (vertex, other row) interactions evaluated,
+ * sum over q of (deg(q) + ns) * iters; info->seconds: device time between events around the call's own launches.  Workspace,
+ * allocated on first use (grown for a larger call) and freed by f2v_destroy: the lists (m + 1 offsets, the ids), m words of
+ * placement, and two chunk x D float matrices (initial vectors, results).
+ * m = 0 is F2V_OK and touches nothing.  F2V_ESTATE without valid embeddings; F2V_EINVAL for a null pointer, an option that does not
+ * fold in, a list id >= n, a descending q_rowptr, an unknown init_kind, GIVEN without init, n < 1, and where (index_base + m) * iters *
+ * ns would reach 2^62.
+ * Making folded vertices permanent: build a new engine on the grown CSR and f2v_set_embeddings the concatenated matrix; growing a live
+ * handle's graph is out of scope. */
+#define F2V_FOLD_INIT_MEAN 0   /* default */
+#define F2V_FOLD_INIT_RANDOM 1
+#define F2V_FOLD_INIT_GIVEN 2  /* `init` holds m x D floats */
+typedef struct {
+    double seconds;
+    uint64_t pairs;
+    uint32_t resident, reserved;
+} f2v_fold_t;
+F2V_API int f2v_fold_in(f2v_handle h, int option, const uint32_t *q_rowptr /* m + 1 */, const uint32_t *q_colids /* ids < n */, uint32_t m,
+                uint32_t iters, uint32_t ns, float lr, int init_kind, const float *init /* m x D or NULL */, uint64_t seed, uint64_t index_base,
+                float *y_out /* m x D */, f2v_fold_t *info /* may be NULL */);
+
 /* ---- host-side I/O of the drop-in boundary (no device needed) ----------------------------
  * f2v_read_mtx replaces SetInputMatricesAsCSR (sample/commonutility.h:44-54 -> ReadASCII
  * sample/IO.h:59-156, CSC sample/CSC.h:146-188, CSR sample/CSR.h:154-186): MatrixMarket
