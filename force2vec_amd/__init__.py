@@ -28,7 +28,10 @@ Looking at it: `Engine.pca(d=2)` is the principal-component projection of the ma
 image continuity, and the overlap of the two neighbourhoods.
 
 Vertices that arrive after training: `Engine.fold_in(rowptr, colids, option=5, iters=300)` returns their vectors -- the training rule run
-for each new vertex against the frozen matrix, all epochs in one launch (deterministic, include/f2v.h) -- without training again."""
+for each new vertex against the frozen matrix, all epochs in one launch (deterministic, include/f2v.h) -- without training again.
+
+Link prediction: `Engine.link_pairs(ratio=2, seed=1)` builds the reference's pair set on the GPU (every edge once, twice as many
+non-neighbours per vertex, shuffled; deterministic, include/f2v.h) and `Engine.link_predict()` scores the embedding on it."""
 from . import _lib  # noqa: F401
 from ._lib import F2VError  # noqa: F401
 from ._lib import KMEANS_MAX_K, KMEANS_PIECE  # noqa: F401
@@ -37,7 +40,7 @@ from ._lib import PCA_PIECE, TRUST_MAX_DIM  # noqa: F401
 from ._lib import FOLD_INIT_GIVEN, FOLD_INIT_MEAN, FOLD_INIT_RANDOM  # noqa: F401
 from ._lib import LOGREG_BLOCK, LOGREG_MAX_CLASSES, PAIR_AVERAGE, PAIR_HADAMARD, PAIR_L1, PAIR_L2  # noqa: F401
 from ._lib import NEAREST_EXCLUDE_NEIGHBOURS, NEAREST_EXCLUDE_SELF, NEAREST_MAX_K, NEAREST_PAD_ID, SIM_COSINE, SIM_DOT, SIM_L2  # noqa: F401
-from .engine import FoldInfo, Pca, Trust  # noqa: F401
+from .engine import FoldInfo, LinkInfo, Pca, Trust  # noqa: F401
 from .engine import Engine, KMeans, LogregModel, Modularity, algorithms, output_name, push_masks, read_embd, read_embd_bin, sm_table, write_embd, write_embd_bin  # noqa: F401
 from .graph import read_csr_bin, read_mtx, rmat_csr, write_csr_bin  # noqa: F401
 

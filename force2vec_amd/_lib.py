@@ -63,6 +63,10 @@ class FoldInfo(C.Structure):  # f2v_fold_t
     _fields_ = [("seconds", C.c_double), ("pairs", C.c_uint64), ("resident", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class LinkInfo(C.Structure):  # f2v_link_t
+    _fields_ = [("seconds", C.c_double), ("positives", C.c_uint64), ("negatives", C.c_uint64), ("candidates", C.c_uint64), ("capped", C.c_uint64)]
+
+
 # every entry point declared in include/f2v.h: name -> (restype, argtypes)
 SIGNATURES = {
     "f2v_last_error": (C.c_char_p, []),
@@ -110,6 +114,7 @@ SIGNATURES = {
     "f2v_pca": (C.c_int, [C.c_void_p, C.c_uint32, f32p, f64p, f64p, f64p, C.POINTER(PcaInfo)]),
     "f2v_trustworthiness": (C.c_int, [C.c_void_p, f32p, C.c_uint32, C.c_uint32, u32p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(TrustInfo)]),
     "f2v_fold_in": (C.c_int, [C.c_void_p, C.c_int, u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_int, f32p, C.c_uint64, C.c_uint64, f32p, C.POINTER(FoldInfo)]),
+    "f2v_link_pairs": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, u32p, u32p, u8p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(LinkInfo)]),
     "f2v_push_export": (C.c_int, [C.c_void_p, C.c_void_p]),
     "f2v_push_attach": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "f2v_push_selftest": (C.c_int, [C.c_void_p]),

@@ -393,6 +393,55 @@ class algorithms {
         printf("Fold-in: %u vertices, %u iterations, %llu interactions in %.6f s on the GPU -> %s\n", m, iters, (unsigned long long)info.pairs, info.seconds, name.c_str());
     }
 
+    // -linkpredict <feature>: link prediction as the reference scores it (performancescores/runlinkpredict.py).  The pair set is
+    // f2v_link_pairs(ratio, seed): every edge once, `ratio` times as many non-neighbours per vertex, shuffled; f2v_logreg_fit (lambda 1,
+    // tol 1e-4, 100 iterations) on the first int(M * frac) pairs with the feature, z > 0 predicts an edge for the others.  Prints the
+    // reference's line -- accuracy and the macro and micro F1 over the labels that occur among the predictions, as fractions of 1 --
+    // and returns the three in percent, computed as Engine.link_predict computes them.
+    struct LinkScores {
+        double accuracy, f1_macro, f1_micro;
+    };
+    LinkScores linkPredict(int feature, double frac, uint32_t ratio, uint64_t seed) {
+        static const char *const names[] = {"Hadamard", "L1", "L2", "Average"};
+        uint64_t M = 0;
+        check(f2v_link_pairs(h, ratio, seed, nullptr, nullptr, nullptr, 0, &M, nullptr));
+        if (M > 0xFFFFFFFFull) throw std::runtime_error("-linkpredict: more than 2^32 - 1 pairs");
+        const size_t cv = (size_t)((double)M * frac);
+        if (cv == 0 || cv == M) throw std::runtime_error("-linkpredict: the split leaves no training or no test pair");
+        std::vector<uint32_t> u(M), v(M);
+        std::vector<uint8_t> y(M);
+        check(f2v_link_pairs(h, ratio, seed, u.data(), v.data(), y.data(), M, &M, nullptr));
+        const size_t tests = M - cv;
+        std::vector<double> W((size_t)DIM + 1), z(tests);
+        f2v_logreg_t info{};
+        check(f2v_logreg_fit(h, u.data(), v.data(), (uint32_t)cv, feature, y.data(), 1, 1.0, 1e-4, 100, W.data(), &info));
+        check(f2v_logreg_decision(h, u.data() + cv, v.data() + cv, (uint32_t)tests, feature, W.data(), 1, z.data(), nullptr));
+        double tp[2] = {0, 0}, fp[2] = {0, 0}, fn[2] = {0, 0}, hits = 0;
+        for (size_t i = 0; i < tests; i++) {
+            const int pred = z[i] > 0, truth = y[cv + i] != 0;
+            hits += pred == truth;
+            for (int c = 0; c < 2; c++) {
+                tp[c] += truth == c && pred == c;
+                fp[c] += truth != c && pred == c;
+                fn[c] += truth == c && pred != c;
+            }
+        }
+        double tps = 0.0, fps = 0.0, fns = 0.0, per = 0.0, classes = 0.0;
+        for (int c = 0; c < 2; c++) {
+            if (tp[c] + fp[c] == 0) continue;  // the label does not occur among the predictions
+            classes += 1;
+            tps += tp[c];
+            fps += fp[c];
+            fns += fn[c];
+            const double den = 2 * tp[c] + fp[c] + fn[c];
+            per += den > 0 ? 2 * tp[c] / den : 0.0;
+        }
+        const double den = 2 * tps + fps + fns;
+        const LinkScores s{100.0 * (hits / (double)tests), 100.0 * (per / classes), 100.0 * (den > 0 ? 2 * tps / den : 0.0)};
+        printf("Link predictions(%s): %g :Accuracy: %.17g F1-macro: %.17g F1-micro: %.17g\n", names[feature], frac, s.accuracy / 100.0, s.f1_macro / 100.0, s.f1_micro / 100.0);
+        return s;
+    }
+
     // writeToFile, sample/algorithms.h:118-136 (file name rule in f2v_output_name)
     void writeToFile(int option, int bs, INDEXTYPE B, INDEXTYPE IT, INDEXTYPE ns) {
         char name[4096];

@@ -15,7 +15,9 @@
 // -separation <labels file | kmeans> [-separation-sample <n>] (after training: the labelling's silhouette and Davies-Bouldin score),
 // -layout <d> [-layout-neighbours <k>] [-layout-sample <n>] (after training: the d-dimensional principal-component layout as
 // "<embd output name>.lay" and its trustworthiness and continuity), -foldin <file> [-foldin-iters <n>] [-foldin-init mean|random] (after
-// training, or on -init <file> with -iter 0: vectors for new vertices, one "<name> <nbr> <nbr> ..." line each, as "<embd output name>.fold").
+// training, or on -init <file> with -iter 0: vectors for new vertices, one "<name> <nbr> <nbr> ..." line each, as "<embd output name>.fold"),
+// -linkpredict <hadamard|l1|l2|average> [-linkpredict-frac <f>] [-linkpredict-ratio <r>] (after training, or on -init <file> with -iter 0:
+// the reference's link-prediction scores of the embedding on the pair set f2v_link_pairs builds from the graph).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -39,6 +41,9 @@ struct Settings {
     long device = 0, seed = 1, cache = 0, binout = 0, fastrng = 0, notext = 0, gpus = 1, samegpu = 0, loss = 0, nearest = 0, cluster = 0, cluster_iters = 300, cluster_restarts = 10;
     std::string metric, classify, separation, foldin, foldin_init = "mean";
     long foldin_iters = 300;
+    std::string linkpredict;
+    long linkpredict_ratio = 2;
+    double linkpredict_frac = 0.5;
     long classify_splits = 10, separation_sample = 0, layout = 0, layout_neighbours = 5, layout_sample = 0;
     double gamma = 1.0, lr = 0.02, classify_frac = 0.1;
 };
@@ -119,6 +124,9 @@ int main(int argc, char *argv[]) {
         {"-foldin", Kind::Text, &s.foldin, "<string>, a file of lines \"<name> <nbr> <nbr> ...\" (1-based ids of existing vertices): after training -- or on -init <file> with -iter 0 -- give every line's new vertex a vector by running the option's update for it against the finished matrix on the GPU, and write <output file>.fold: \"<m> <dim>\", then per line the name and the vector (options 5, 6, 8, 9, 11; one GPU; samples seeded by -seed; -nsamples and -lr as in training)."},
         {"-foldin-iters", Kind::Integer, &s.foldin_iters, "<int>, epochs of a -foldin vertex. (default:300)"},
         {"-foldin-init", Kind::Text, &s.foldin_init, "<string>, initial vector of a -foldin vertex: mean (of its neighbours' vectors) | random. Under the sigmoid options (6, 9) a random start moves slowly: keep mean. (default:mean)"},
+        {"-linkpredict", Kind::Text, &s.linkpredict, "<string>, hadamard | l1 | l2 | average: after training -- or on -init <file> with -iter 0 -- score link prediction as the reference does: the pair set (every edge once, -linkpredict-ratio times as many non-neighbours per vertex, shuffled by -seed) is built on the GPU, a logistic regression on that pair feature is fitted on its first part and predicts the rest; prints \"Link predictions(<Feature>): <frac> :Accuracy: <a> F1-macro: <m> F1-micro: <i>\", fractions of 1 (one GPU)."},
+        {"-linkpredict-frac", Kind::Real, &s.linkpredict_frac, "<float>, above 0 and below 1: the share of the pair set that trains the -linkpredict model. (default:0.5)"},
+        {"-linkpredict-ratio", Kind::Integer, &s.linkpredict_ratio, "<int>, 1..16: negatives per positive of a vertex in the -linkpredict pair set. (default:2)"},
         {"-metric", Kind::Text, &s.metric, "<string>, similarity of -nearest: dot | l2 | cos. (default: l2 for options 5, 8, 11, dot for the sigmoid options)"},
     };
     const size_t nflags = sizeof flags / sizeof flags[0];
@@ -258,6 +266,19 @@ int main(int argc, char *argv[]) {
         printf("-foldin is not available with -gpus > 1 (it reads one GPU's matrix).\n");
         return 1;
     }
+    const int linkpredict_feature = s.linkpredict == "hadamard" ? F2V_PAIR_HADAMARD : s.linkpredict == "l1" ? F2V_PAIR_L1 : s.linkpredict == "l2" ? F2V_PAIR_L2 : s.linkpredict == "average" ? F2V_PAIR_AVERAGE : -1;
+    if (!s.linkpredict.empty() && linkpredict_feature < 0) {
+        printf("-linkpredict must be hadamard, l1, l2 or average.\n");
+        return 1;
+    }
+    if (!s.linkpredict.empty() && !(s.linkpredict_frac > 0.0 && s.linkpredict_frac < 1.0)) {
+        printf("-linkpredict-frac must be above 0 and below 1.\n");
+        return 1;
+    }
+    if (!s.linkpredict.empty() && (s.linkpredict_ratio < 1 || s.linkpredict_ratio > 16)) {
+        printf("-linkpredict-ratio must be 1..16.\n");
+        return 1;
+    }
     std::vector<VALUETYPE> seconds;
     int rank = 0;
     std::string meet;  // directory the ranks of a -gpus run meet in
@@ -306,6 +327,7 @@ int main(int argc, char *argv[]) {
             if (!s.separation.empty() && rank == 0) algo.separation(s.separation, (uint32_t)s.separation_sample, (uint64_t)s.seed);
             if (s.layout > 0 && rank == 0) algo.layout((uint32_t)s.layout, (uint32_t)s.layout_neighbours, (uint32_t)s.layout_sample, (uint64_t)s.seed);
             if (!s.foldin.empty() && rank == 0) algo.foldIn(s.foldin, (int)s.option, (uint32_t)s.foldin_iters, (INDEXTYPE)s.nsamples, (VALUETYPE)s.lr, foldin_init, (uint64_t)s.seed);
+            if (!s.linkpredict.empty() && rank == 0) algo.linkPredict(linkpredict_feature, s.linkpredict_frac, (uint32_t)s.linkpredict_ratio, (uint64_t)s.seed);
             const double t = algo.gpu_train_seconds;
             if (rank == 0 && s.gpus == 1)
                 printf("GPU epoch loop: %.6f s, %.4g nnz/s, %.1f GB/s algorithmic\n", t, t > 0 ? algo.stats.nnz / t : 0.0,

@@ -39,6 +39,7 @@
 #include "f2v_layout.hip.h"
 #include "f2v_exact.hip.h"
 #include "f2v_foldin.hip.h"
+#include "f2v_linkpairs.hip.h"
 
 using namespace f2v;
 
@@ -283,6 +284,15 @@ struct f2v_ctx {
         uint32_t chunk = 65536;
         int resident = -1;
     } fold;
+    // link prediction pairs (f2v_link_pairs): the workspace f2v.h states, allocated on first use and grown for a larger call;
+    // "link_short_max": the most negatives of a vertex that one wavefront draws (longer lists take a workgroup and a table)
+    struct Link {
+        DevBuf<uint32_t> d_p, d_total, d_order, d_u, d_v, d_table;
+        DevBuf<uint8_t> d_y;
+        DevBuf<unsigned long long> d_offset, d_tile, d_sums, d_table_at;
+        DevTimer timer;
+        uint32_t short_max = 256;
+    } link;
     uint32_t last_wide_width = 0;  // the layout width of the last wide-form f2v_train ("last_wide_width")
     bool last_wide_early = false;  // ... and whether it ran the kernel's EARLY form ("last_wide_early")
     int last_train_form = 0;  // how the last f2v_train launched: 0 one launch per minibatch, 1 chained, 2 chained in the wide form ("last_train_form")
@@ -2271,6 +2281,8 @@ const Param kParams[] = {
     {"fold_chunk", F2V_FIELD(fold.chunk), kValue, kKeep, in<1, 1048576>, "fold_chunk must be 1..1048576"},
     // f2v_fold_in: 0 = every epoch gathers a vertex's list rows from the caches, -1 = automatic (the same); 1, rows staged in LDS once, was measured slower and is not built
     {"fold_resident", F2V_FIELD(fold.resident), kValue, kKeep, in<-1, 0>, "fold_resident must be -1 (automatic) or 0: the resident form measured slower and is not part of this build"},
+    // f2v_link_pairs: a vertex with at most this many negatives is one wavefront's (its accepted set a list in LDS), a longer one a workgroup's (a table); placement only
+    {"link_short_max", F2V_FIELD(link.short_max), kValue, kKeep, in<0, kLinkShortLimit>, "link_short_max must be 0..1024"},
     {"push_fused", F2V_FIELD(push.fused), kFlag},
     {"push_timeout_ms", F2V_FIELD(push.timeout_ms), kValue, kKeep, in<1, 600000>, "push_timeout_ms must be 1..600000"},
     // takes effect at the next f2v_push_export; read: what the exchange in place runs with
@@ -4370,6 +4382,150 @@ int f2v_fold_in(f2v_handle c, int option, const uint32_t *q_rowptr, const uint32
         info->seconds = seconds;
         info->pairs = pairs;
         info->resident = 0;  // (the form is not built: "fold_resident")
+    }
+    return F2V_OK;
+}
+
+}  // extern "C"
+
+// ---- link prediction pairs (f2v_linkpairs.hip.h; definition in include/f2v.h) ---------------------------------------------------
+extern "C" {
+
+int f2v_link_pairs(f2v_handle c, uint32_t ratio, uint64_t seed, uint32_t *u_out, uint32_t *v_out, uint8_t *y_out, uint64_t cap, uint64_t *count_out,
+                   f2v_link_t *info) {
+    if (!c || !count_out) return fail(F2V_EINVAL, "f2v_link_pairs: null argument");
+    const bool fill = u_out || v_out || y_out;
+    if (fill && !(u_out && v_out && y_out)) return fail(F2V_EINVAL, "f2v_link_pairs: u_out, v_out and y_out are given together or not at all");
+    if (ratio < 1 || ratio > 16) return fail(F2V_EINVAL, "f2v_link_pairs: ratio = %u is outside 1..16", ratio);
+    if (!rows_ascending(c)) return fail(F2V_EINVAL, "f2v_link_pairs: the CSR's column ids are not ascending inside every row (needed to search a row)");
+    HIPC(hipSetDevice(c->device));
+    *count_out = 0;
+    if (info) *info = f2v_link_t{};
+    const uint32_t n = c->n;
+    if (n == 0) return F2V_OK;
+
+    f2v_ctx::Link &w = c->link;
+    const char *what = "link pairs";
+    const uint32_t tiles = (uint32_t)(((uint64_t)n + kLinkScanTile - 1) / kLinkScanTile), rows = std::min((n + 3) / 4, 8192u);
+    F2VC(w.d_p.reserve(c, n, what));
+    F2VC(w.d_total.reserve(c, n, what));
+    F2VC(w.d_offset.reserve(c, n, what));
+    F2VC(w.d_tile.reserve(c, tiles, what));
+    F2VC(w.d_sums.reserve(c, 4, what));
+    LinkArgs a{};
+    a.rowptr = c->d_rowptr;
+    a.colids = c->d_colids;
+    a.p = w.d_p;
+    a.total = w.d_total;
+    a.offset = w.d_offset;
+    a.tile = w.d_tile;
+    a.sums = w.d_sums;
+    a.n = n;
+    a.ratio = ratio;
+    a.s1 = mix64_host(seed);
+    a.s2 = mix64_host(a.s1);
+    HIPC(hipMemsetAsync(w.d_sums, 0, 4 * sizeof(unsigned long long), c->stream));
+    double seconds = 0.0;
+    F2VC(w.timer.start(c->stream));
+    hipLaunchKernelGGL(link_count_kernel, dim3(rows), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(link_scan_tile_kernel, dim3(tiles), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(link_scan_top_kernel, dim3(1), dim3(256), 0, c->stream, a, tiles);
+    hipLaunchKernelGGL(link_scan_apply_kernel, dim3(tiles), dim3(256), 0, c->stream, a);
+    HIPC(hipGetLastError());
+    F2VC(w.timer.stop(c->stream));
+    unsigned long long sums[4];
+    HIPC(hipMemcpyAsync(sums, w.d_sums, sizeof sums, hipMemcpyDeviceToHost, c->stream));
+    std::vector<uint32_t> total(fill ? n : 0);
+    if (fill) HIPC(hipMemcpyAsync(total.data(), w.d_total, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    F2VC(w.timer.seconds(&seconds));
+    const uint64_t M = sums[0] + sums[1];
+    *count_out = M;
+    if (info) {
+        info->seconds = seconds;
+        info->positives = sums[0];
+        info->negatives = sums[1];
+        info->capped = sums[2];
+    }
+    if (fill && cap < M) return fail(F2V_EINVAL, "f2v_link_pairs: the set has %llu pairs, the arrays hold %llu", (unsigned long long)M, (unsigned long long)cap);
+    if (!fill || M == 0) return F2V_OK;
+
+    // placement: the vertices that draw negatives by descending total(u), ties in id order (a counting sort: total(u) < n / 2) -- the
+    // first `nw` of them with tables in the workspace, up to `nl` a workgroup each, the others a wavefront each
+    uint32_t most = 0;
+    for (uint32_t v = 0; v < n; v++) most = std::max(most, total[v]);
+    if (most > (1u << 29)) return fail(F2V_EINVAL, "f2v_link_pairs: a vertex with more than 2^29 negatives");
+    std::vector<uint32_t> first((size_t)most + 2, 0), order;
+    for (uint32_t v = 0; v < n; v++)
+        if (total[v]) first[most - total[v] + 1]++;
+    for (uint32_t k = 0; k <= most; k++) first[k + 1] += first[k];
+    order.resize(first[(size_t)most + 1]);
+    for (uint32_t v = 0; v < n; v++)
+        if (total[v]) order[first[most - total[v]]++] = v;
+    const uint32_t cnt = (uint32_t)order.size();
+    uint32_t nw = 0, nl = 0;
+    std::vector<unsigned long long> table_at;
+    uint64_t words = 0;
+    while (nl < cnt && total[order[nl]] > w.short_max) nl++;
+    while (nw < nl && link_slots(total[order[nw]]) > kLinkLdsSlots) {
+        table_at.push_back(words);
+        words += link_slots(total[order[nw++]]);
+    }
+    F2VC(w.d_order.reserve(c, cnt, what));
+    F2VC(w.d_table_at.reserve(c, nw, what));
+    F2VC(w.d_table.reserve(c, 2 * words, what));
+    F2VC(w.d_u.reserve(c, M, what));
+    F2VC(w.d_v.reserve(c, M, what));
+    F2VC(w.d_y.reserve(c, M, what));
+    if (cnt) HIPC(hipMemcpyAsync(w.d_order, order.data(), (size_t)cnt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (nw) {
+        HIPC(hipMemcpyAsync(w.d_table_at, table_at.data(), (size_t)nw * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
+        HIPC(hipMemsetAsync(w.d_table, 0xFF, 2 * words * sizeof(uint32_t), c->stream));  // kLinkEmpty
+    }
+    a.u_out = w.d_u;
+    a.v_out = w.d_v;
+    a.y_out = w.d_y;
+    a.keys = w.d_table;
+    a.table_words = words;
+    a.table_at = w.d_table_at;
+    a.M = M;
+    uint32_t bits = 2;
+    while (bits < 64 && ((uint64_t)1 << bits) < M) bits += 2;
+    a.half = bits / 2;
+    a.mask = ((uint64_t)1 << a.half) - 1;
+    // link_long_kernel: the wavefronts' counts of two rounds, in front of an LDS table
+    const size_t counts_bytes = 2 * (kLinkLongThreads / 64) * sizeof(uint32_t), wide_counts_bytes = 2 * (kLinkWideThreads / 64) * sizeof(uint32_t);
+    F2VC(w.timer.start(c->stream));
+    if (nw) {  // the longest lists first: their workgroups run longest
+        a.order = w.d_order;
+        hipLaunchKernelGGL(link_long_kernel<true>, dim3(nw), dim3(kLinkWideThreads), wide_counts_bytes, c->stream, a);
+    }
+    for (uint32_t i = nw, j; i < nl; i = j) {  // one launch per table size
+        a.slots = (uint32_t)link_slots(total[order[i]]);
+        for (j = i + 1; j < nl && j - i < (1u << 30) && link_slots(total[order[j]]) == a.slots; j++) {}
+        const size_t lds = counts_bytes + 2 * (size_t)a.slots * sizeof(uint32_t);
+        F2VC(allow_lds(c, reinterpret_cast<const void *>(&link_long_kernel<false>), lds));
+        a.order = w.d_order + i;
+        hipLaunchKernelGGL(link_long_kernel<false>, dim3(j - i), dim3(kLinkLongThreads), lds, c->stream, a);
+    }
+    if (nl < cnt) {
+        a.order = w.d_order + nl;
+        a.count = cnt - nl;
+        a.short_max = total[order[nl]];  // the longest list of the launch
+        hipLaunchKernelGGL(link_short_kernel, dim3(std::min((a.count + 3) / 4, 16384u)), dim3(256), 4 * (size_t)a.short_max * sizeof(uint32_t), c->stream, a);
+    }
+    hipLaunchKernelGGL(link_positive_kernel, dim3(rows), dim3(256), 0, c->stream, a);
+    HIPC(hipGetLastError());
+    F2VC(w.timer.stop(c->stream));
+    HIPC(hipMemcpyAsync(u_out, w.d_u, M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipMemcpyAsync(v_out, w.d_v, M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipMemcpyAsync(y_out, w.d_y, M * sizeof(uint8_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipMemcpyAsync(sums, w.d_sums, sizeof sums, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    F2VC(w.timer.seconds(&seconds));
+    if (info) {
+        info->seconds = seconds;
+        info->candidates = sums[3];
     }
     return F2V_OK;
 }

@@ -36,6 +36,10 @@ FoldInfo = namedtuple("FoldInfo", "seconds pairs resident")
 FOLD_INITS = {"mean": _lib.FOLD_INIT_MEAN, "random": _lib.FOLD_INIT_RANDOM}
 
 
+# Engine.link_pairs (include/f2v.h: link prediction pairs)
+LinkInfo = namedtuple("LinkInfo", "seconds positives negatives candidates capped")
+
+
 # Engine.logreg_fit / Engine.classify / Engine.link_predict (include/f2v.h: logistic regression)
 LogregModel = namedtuple("LogregModel", "weights feature loss gnorm_inf iterations evaluations converged seconds")
 F1 = namedtuple("F1", "micro macro")
@@ -84,6 +88,7 @@ class Engine:
         self.last_separation_seconds = 0.0  # ... / silhouette or Davies-Bouldin call
         self.last_layout_seconds = 0.0  # ... / pca or trustworthiness call
         self.last_fold_seconds = 0.0  # ... / fold_in call
+        self.last_link_seconds = 0.0  # ... / link_pairs call (its count and its fill together)
 
     def _ck(self, rc):
         check(rc, self._L)  # the error text lives in the library that returned the code
@@ -535,10 +540,32 @@ class Engine:
             pred[r, order[r, :int(true[r].sum())]] = 1
         return _f1(true, pred, np.arange(classes))
 
-    def link_predict(self, u, v, y, train_frac=0.5, feature="hadamard", lam=1.0, tol=1e-4, max_iter=100):
+    # -- link prediction pairs (include/f2v.h: definition; a function of the CSR, ratio and seed alone) --
+    def link_pairs(self, ratio=2, seed=1, details=False):
+        """The reference's link-prediction pair set (makeLinkPredictionData, performancescores/runlinkpredict.py:51-107) built on the
+        GPU: every edge once as a positive, `ratio` times as many non-neighbours per vertex as negatives, shuffled by a keyed
+        bijection -> (u uint32 [M], v uint32 [M], y uint8 [M]), or with details=True (u, v, y, LinkInfo(seconds, positives, negatives,
+        candidates, capped)).  Needs no embeddings.  `last_link_seconds` keeps the device time."""
+        count, info = C.c_uint64(), _lib.LinkInfo()
+        self._ck(self._L.f2v_link_pairs(self._h, ratio, seed, None, None, None, 0, C.byref(count), C.byref(info)))
+        m, seconds = count.value, info.seconds
+        u, v, y = np.empty(m, dtype=np.uint32), np.empty(m, dtype=np.uint32), np.empty(m, dtype=np.uint8)
+        if m:
+            self._ck(self._L.f2v_link_pairs(self._h, ratio, seed, _u32(u), _u32(v), y.ctypes.data_as(_lib.u8p), m, C.byref(count), C.byref(info)))
+            seconds += info.seconds
+        self.last_link_seconds = seconds
+        return (u, v, y, LinkInfo(seconds, info.positives, info.negatives, info.candidates, info.capped)) if details else (u, v, y)
+
+    def link_predict(self, u=None, v=None, y=None, train_frac=0.5, feature="hadamard", lam=1.0, tol=1e-4, max_iter=100, ratio=2, seed=1):
         """Link prediction as the reference scores it (performancescores/runlinkpredict.py:127-140): fits on the first
         int(m * train_frac) pairs (u, v) with 0/1 targets y, predicts z > 0 on the rest -> LinkScores(accuracy, f1_macro, f1_micro)
-        in percent, the F1 values over the labels that occur among the predictions."""
+        in percent, the F1 values over the labels that occur among the predictions.  Without u, v and y the pair set is
+        link_pairs(ratio, seed)."""
+        given = [x is not None for x in (u, v, y)]
+        if any(given) and not all(given):
+            raise ValueError("link_predict: give u, v and y together, or none of them")
+        if not any(given):
+            u, v, y = self.link_pairs(ratio=ratio, seed=seed)
         u, v, y = np.asarray(u, dtype=np.uint32), np.asarray(v, dtype=np.uint32), np.asarray(y, dtype=np.uint8).reshape(-1)
         cv = int(len(y) * train_frac)
         model = self.logreg_fit(pairs=(u[:cv], v[:cv]), y=y[:cv].reshape(-1, 1), feature=feature, lam=lam, tol=tol, max_iter=max_iter)

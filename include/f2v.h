@@ -717,6 +717,58 @@ F2V_API int f2v_fold_in(f2v_handle h, int option, const uint32_t *q_rowptr /* m 
                 uint32_t iters, uint32_t ns, float lr, int init_kind, const float *init /* m x D or NULL */, uint64_t seed, uint64_t index_base,
                 float *y_out /* m x D */, f2v_fold_t *info /* may be NULL */);
 
+/* ---- link prediction pairs ----------------------------------------------------------------------------------------------------
+ * The pair set that the reference's link-prediction score is computed on (makeLinkPredictionData, performancescores/
+ * runlinkpredict.py:51-107): every edge once as a positive, `ratio` times as many non-neighbours per vertex as negatives, shuffled;
+ * f2v_logreg_fit on the first int(M * frac) pairs and f2v_logreg_decision on the others is the score.  The set is a function of (the
+ * CSR, ratio, seed) alone: bitwise identical between calls, handles and GPUs and under every tunable; no float is involved.
+ *   graph       N(u) = the distinct ids of CSR row u other than u itself: duplicates collapse, a self-loop is dropped.  Rows must be
+ *               ascending (checked once per handle).  The call needs no embeddings; it runs on the handle's stream and touches neither
+ *               the matrices nor the rand() stream nor any later result;
+ *   positives   for u ascending, the v in N(u) with v > u, ascending; p(u) is their number.  On the symmetric CSRs of f2v_read_mtx
+ *               that is every undirected edge once; a nonzero stored in one direction only counts where its row names it: (u, v)
+ *               with v > u present in row u alone is a positive, present in row v alone it is none (and v is no neighbour of u);
+ *   how many    A(u) = n - 1 - |N(u)|, total(u) = min(ratio * p(u), A(u) / 2) negatives, integer division; 1 <= ratio <= 16, the
+ *               default everywhere is 2.  This is the reference's rule (:76-80) with its dense-vertex case -- (n - |N(u)|) / 2 for a
+ *               vertex with more than n / 2 neighbours -- turned into a cap: the reference's loop does not end for a vertex of degree
+ *               n / 2 whose neighbours are all higher; under the cap at least half of the admissible vertices stay free, a candidate
+ *               is accepted with probability above A(u) / (2 n), and the expected number of candidates per vertex is below n.
+ *               `capped` counts the vertices with A(u) / 2 < ratio * p(u);
+ *   which       S1 = mix64(seed) (mix64: the splitmix64 finaliser of the objective above, 64-bit wrapping arithmetic); candidate
+ *               c(u, t) = mix64(mix64(S1 ^ u) + t) % n for t = 0, 1, 2, ...; a candidate is accepted if it is not u, is not in N(u)
+ *               and equals no earlier accepted candidate of u; u's negatives are its first total(u) accepted candidates, in order of
+ *               t.  (The reference admits u itself as a negative; this definition does not.)  `candidates` = the sum over the
+ *               vertices with total(u) > 0 of (the t of u's last accepted candidate + 1);
+ *   order       item index i runs over u ascending: u's positives, then u's negatives in acceptance order; M = sum p(u) + sum total(u);
+ *   shuffle     a keyed bijection, not a sort.  b = the smallest even number >= 2 with 2^b >= M, half = b / 2, mask = 2^half - 1,
+ *               S2 = mix64(S1).  perm(i): x = i; repeat { L = x >> half, R = x & mask; for r = 0 .. 3: (L, R) = (R, L ^ (mix64(S2 ^
+ *               (r * 2^32 + R)) & mask)); x = (L << half) | R } until x < M.  (A four-round Feistel network is a bijection of [0, 2^b)
+ *               for any round function; walking its cycle until the value is below M makes it one of [0, M), and 2^b < 4 M keeps
+ *               the walk short.)  Item i = (u, v, y) is written to place perm(i) of u_out / v_out / y_out, y = 1 for a positive
+ *               and 0 for a negative.  The reference's split is then "the first int(M * frac) places train".
+ * Calling: with u_out, v_out and y_out all NULL only *count_out = M and info are filled (info->candidates stays 0: nothing is
+ * drawn); with the three given, `cap` is the number of pairs each holds: cap < M is F2V_EINVAL with *count_out = M written.  M = 0 is
+ * F2V_OK.  F2V_EINVAL also for a null handle or count_out, one or two of the three outputs, a ratio outside 1..16, rows that are
+ * not ascending, and a vertex with more than 2^29 negatives.  info->seconds: device time between events around the call's own launches.
+ * Launches: |N(u)|, p(u) and total(u) by one wavefront per row ("distinct" is "differs from its predecessor"), three launches of a
+ * 64-bit exclusive prefix sum for the items' offsets, then the vertices that draw negatives in the order of descending total(u)
+ * (placement only): a vertex with at most "link_short_max" (0..1024, default 256) negatives is one wavefront's, 64 candidates a round,
+ * its accepted set a list in LDS; a longer one a workgroup's, its accepted set an open-addressing table: in LDS, 256 candidates a
+ * round, up to 3072 negatives, and in the workspace, 1024 candidates a round, above.  Every item is stored straight to its place.  Neither "link_short_max" nor
+ * the round widths change a bit of the result.
+ * Workspace, allocated on first use (grown for a larger call) and freed by f2v_destroy: per vertex p(u), total(u) (4 bytes each) and
+ * the offset (8), 8 bytes per 1024 vertices of the prefix sum, 4 per vertex that draws negatives (placement), M x 9 bytes of
+ * results, and per vertex with more than 3072 negatives a table of 8 bytes x the smallest power of two >= 2 total(u) + 2048, plus 8
+ * bytes for its position.  The pairs travel to the host (9 M bytes) and, as id lists of f2v_logreg_*, back. */
+typedef struct {
+    double seconds;            /* device time between events around the call's own launches */
+    uint64_t positives, negatives;
+    uint64_t candidates;       /* candidates drawn in all: sum over u of (index of u's last accepted candidate + 1) */
+    uint64_t capped;           /* vertices whose negatives were limited by the cap */
+} f2v_link_t;
+F2V_API int f2v_link_pairs(f2v_handle h, uint32_t ratio, uint64_t seed, uint32_t *u_out, uint32_t *v_out, uint8_t *y_out /* all three NULL: count only */,
+                   uint64_t cap, uint64_t *count_out, f2v_link_t *info /* may be NULL */);
+
 /* ---- host-side I/O of the drop-in boundary (no device needed) ----------------------------
  * f2v_read_mtx replaces SetInputMatricesAsCSR (sample/commonutility.h:44-54 -> ReadASCII
  * sample/IO.h:59-156, CSC sample/CSC.h:146-188, CSR sample/CSR.h:154-186): MatrixMarket
