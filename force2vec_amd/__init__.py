@@ -36,7 +36,7 @@ from . import _lib  # noqa: F401
 from ._lib import F2VError  # noqa: F401
 from ._lib import KMEANS_MAX_K, KMEANS_PIECE  # noqa: F401
 from ._lib import LABEL_NONE, SEPARATION_MAX_CLUSTERS, SEPARATION_PIECE, SEPARATION_SPAN  # noqa: F401
-from ._lib import PCA_PIECE, TRUST_MAX_DIM  # noqa: F401
+from ._lib import PCA_PIECE, TRUST_MAX_DIM, TSNE_PIECE, TSNE_SPAN  # noqa: F401
 from ._lib import FOLD_INIT_GIVEN, FOLD_INIT_MEAN, FOLD_INIT_RANDOM  # noqa: F401
 from ._lib import LOGREG_BLOCK, LOGREG_MAX_CLASSES, PAIR_AVERAGE, PAIR_HADAMARD, PAIR_L1, PAIR_L2  # noqa: F401
 from ._lib import NEAREST_EXCLUDE_NEIGHBOURS, NEAREST_EXCLUDE_SELF, NEAREST_MAX_K, NEAREST_PAD_ID, SIM_COSINE, SIM_DOT, SIM_L2  # noqa: F401

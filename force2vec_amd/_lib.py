@@ -21,6 +21,7 @@ LABEL_NONE = 0xFFFFFFFF  # F2V_LABEL_NONE: the vertex takes no part in a separat
 SEPARATION_MAX_CLUSTERS, SEPARATION_PIECE, SEPARATION_SPAN = 1024, 64, 64
 PCA_PIECE, TRUST_MAX_DIM = 4096, 512
 FOLD_INIT_MEAN, FOLD_INIT_RANDOM, FOLD_INIT_GIVEN = 0, 1, 2
+TSNE_PIECE, TSNE_SPAN = 64, 16
 
 u32p = C.POINTER(C.c_uint32)
 f32p = C.POINTER(C.c_float)
@@ -57,6 +58,16 @@ class PcaInfo(C.Structure):  # f2v_pca_t
 class TrustInfo(C.Structure):  # f2v_trust_t
     _fields_ = [("trustworthiness", C.c_double), ("continuity", C.c_double), ("overlap", C.c_double), ("seconds", C.c_double),
                 ("penalty_x", C.c_uint64), ("penalty_y", C.c_uint64), ("hits", C.c_uint64)]
+
+
+class TsneParams(C.Structure):  # f2v_tsne_params
+    _fields_ = [("perplexity", C.c_double), ("exaggeration", C.c_double), ("learning_rate", C.c_double), ("iters", C.c_uint32),
+                ("exaggeration_iters", C.c_uint32), ("kl_every", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class TsneInfo(C.Structure):  # f2v_tsne_t
+    _fields_ = [("kl", C.c_double), ("z", C.c_double), ("learning_rate", C.c_double), ("seconds", C.c_double), ("nnz", C.c_uint64),
+                ("k", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class FoldInfo(C.Structure):  # f2v_fold_t
@@ -113,6 +124,9 @@ SIGNATURES = {
     "f2v_davies_bouldin": (C.c_int, [C.c_void_p, u32p, C.c_uint32, f64p, f32p, f64p, C.POINTER(C.c_uint64), f64p]),
     "f2v_pca": (C.c_int, [C.c_void_p, C.c_uint32, f32p, f64p, f64p, f64p, C.POINTER(PcaInfo)]),
     "f2v_trustworthiness": (C.c_int, [C.c_void_p, f32p, C.c_uint32, C.c_uint32, u32p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(TrustInfo)]),
+    "f2v_tsne_affinities": (C.c_int, [C.c_void_p, u32p, C.c_uint32, C.c_double, u32p, u32p, f64p, C.c_uint64, C.POINTER(C.c_uint64), f64p]),
+    "f2v_tsne": (C.c_int, [C.c_void_p, u32p, C.c_uint32, C.c_uint32, C.POINTER(TsneParams), u32p, u32p, f64p, f64p, f32p, C.POINTER(TsneInfo)]),
+    "f2v_tsne_kl_log": (C.c_int, [C.c_void_p, u32p, f64p, C.c_uint32, u32p]),
     "f2v_fold_in": (C.c_int, [C.c_void_p, C.c_int, u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_int, f32p, C.c_uint64, C.c_uint64, f32p, C.POINTER(FoldInfo)]),
     "f2v_link_pairs": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, u32p, u32p, u8p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(LinkInfo)]),
     "f2v_push_export": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -322,11 +322,21 @@ class algorithms {
     // prints for its picture, extended by the mirror score: f2v_trustworthiness of the layout with k neighbours.  sample > 0: over
     // that many vertices, the first of the order key(v) = mix64(mix64(seed) ^ v) ascending, ties by id (as -separation-sample), each
     // ranked against all vertices; 0: over every vertex.
-    void layout(uint32_t d, uint32_t k, uint32_t sample, uint64_t seed) {
+    // tsne (-layout-method tsne): the coordinates are f2v_tsne's over every vertex (d = 2 or 3) with the PCA start, and the second
+    // line reports the run instead of the explained variance.
+    void layout(uint32_t d, uint32_t k, uint32_t sample, uint64_t seed, bool tsne = false, double perplexity = 30.0, uint32_t iters = 1000) {
         std::vector<float> y((size_t)rows * d);
         std::vector<double> var(d);
         f2v_pca_t info{};
-        check(f2v_pca(h, d, y.data(), nullptr, nullptr, var.data(), &info));
+        f2v_tsne_t run{};
+        if (tsne) {
+            f2v_tsne_params par{};
+            par.perplexity = perplexity;
+            par.iters = iters;
+            check(f2v_tsne(h, nullptr, rows, d, &par, nullptr, nullptr, nullptr, nullptr, y.data(), &run));
+        } else {
+            check(f2v_pca(h, d, y.data(), nullptr, nullptr, var.data(), &info));
+        }
         const std::string name = last_output + ".lay";
         FILE *f = fopen(name.c_str(), "w");
         if (!f) throw std::runtime_error("cannot write " + name);
@@ -349,6 +359,11 @@ class algorithms {
         double kept = 0.0;
         for (uint32_t c = 0; c < d; c++) kept += var[c];
         printf("TrustWorthiness: %.17g Continuity: %.17g\n", t.trustworthiness, t.continuity);
+        if (tsne) {
+            printf("Layout: d=%u neighbours=%u samples=%u :METHOD: tsne :PERPLEXITY: %g :ITERATIONS: %u :KL: %.17g :OVERLAP: %.17g\n", d, k,
+                   sample ? (uint32_t)ids.size() : rows, perplexity, iters, run.kl, t.overlap);
+            return;
+        }
         printf("Layout: d=%u neighbours=%u samples=%u :EXPLAINED-VARIANCE: %.17g :OVERLAP: %.17g :SWEEPS: %u\n", d, k, sample ? (uint32_t)ids.size() : rows,
                info.total_variance > 0 ? kept / info.total_variance : 0.0, t.overlap, info.sweeps);
     }

@@ -13,7 +13,7 @@
 // [-cluster-restarts <r>] (after training: k-means on the embedding as "<embd output name>.clu" and its modularity on the graph),
 // -classify <labels file> [-classify-frac <f>] [-classify-splits <s>] (after training: node-classification F1 of the embedding),
 // -separation <labels file | kmeans> [-separation-sample <n>] (after training: the labelling's silhouette and Davies-Bouldin score),
-// -layout <d> [-layout-neighbours <k>] [-layout-sample <n>] (after training: the d-dimensional principal-component layout as
+// -layout <d> [-layout-method pca|tsne] [-layout-perplexity <p>] [-layout-iters <n>] [-layout-neighbours <k>] [-layout-sample <n>] (after training: the d-dimensional principal-component -- or exact t-SNE -- layout as
 // "<embd output name>.lay" and its trustworthiness and continuity), -foldin <file> [-foldin-iters <n>] [-foldin-init mean|random] (after
 // training, or on -init <file> with -iter 0: vectors for new vertices, one "<name> <nbr> <nbr> ..." line each, as "<embd output name>.fold"),
 // -linkpredict <hadamard|l1|l2|average> [-linkpredict-frac <f>] [-linkpredict-ratio <r>] (after training, or on -init <file> with -iter 0:
@@ -39,7 +39,9 @@ struct Settings {
     std::string input, output, init;
     long batch = 384, iter = 1200, threads = (long)std::thread::hardware_concurrency(), dim = 128, nsamples = 5, option = 5, bs = 0;
     long device = 0, seed = 1, cache = 0, binout = 0, fastrng = 0, notext = 0, gpus = 1, samegpu = 0, loss = 0, nearest = 0, cluster = 0, cluster_iters = 300, cluster_restarts = 10;
-    std::string metric, classify, separation, foldin, foldin_init = "mean";
+    std::string metric, classify, separation, foldin, foldin_init = "mean", layout_method = "pca";
+    long layout_iters = 1000;
+    double layout_perplexity = 30.0;
     long foldin_iters = 300;
     std::string linkpredict;
     long linkpredict_ratio = 2;
@@ -121,6 +123,9 @@ int main(int argc, char *argv[]) {
         {"-layout", Kind::Integer, &s.layout, "<int>, d in 1..dim: after training write <output file>.lay, one line per vertex \"v y1 ... yd\" (1-based ids): the matrix projected onto its first d principal components on the GPU, and print \"TrustWorthiness: <t> Continuity: <c>\" of that picture and its explained-variance share (one GPU). (default:0)"},
         {"-layout-neighbours", Kind::Integer, &s.layout_neighbours, "<int>, k in 1..128, below half the number of vertices: the neighbourhood size of the -layout scores. (default:5)"},
         {"-layout-sample", Kind::Integer, &s.layout_sample, "<int>, score the -layout over that many vertices chosen by -seed, each ranked against all vertices; 0 = every vertex (O(N^2 dim) work). (default:0)"},
+        {"-layout-method", Kind::Text, &s.layout_method, "<string>, pca or tsne: what -layout writes. tsne is the exact t-SNE of the matrix in d = 2 or 3 dimensions on the GPU (deterministic; started from the principal components as scikit-learn's init=\"pca\"; O(N^2) per iteration, at most 131072 vertices -- Engine.tsne(ids=...) lays out a subset of a larger graph). (default:pca)"},
+        {"-layout-perplexity", Kind::Real, &s.layout_perplexity, "<float>, above 1 and at most 42, and 3 x perplexity below the number of vertices: the perplexity of -layout-method tsne. (default:30)"},
+        {"-layout-iters", Kind::Integer, &s.layout_iters, "<int>, iterations of -layout-method tsne, the first 250 with early exaggeration. (default:1000)"},
         {"-foldin", Kind::Text, &s.foldin, "<string>, a file of lines \"<name> <nbr> <nbr> ...\" (1-based ids of existing vertices): after training -- or on -init <file> with -iter 0 -- give every line's new vertex a vector by running the option's update for it against the finished matrix on the GPU, and write <output file>.fold: \"<m> <dim>\", then per line the name and the vector (options 5, 6, 8, 9, 11; one GPU; samples seeded by -seed; -nsamples and -lr as in training)."},
         {"-foldin-iters", Kind::Integer, &s.foldin_iters, "<int>, epochs of a -foldin vertex. (default:300)"},
         {"-foldin-init", Kind::Text, &s.foldin_init, "<string>, initial vector of a -foldin vertex: mean (of its neighbours' vectors) | random. Under the sigmoid options (6, 9) a random start moves slowly: keep mean. (default:mean)"},
@@ -245,6 +250,23 @@ int main(int argc, char *argv[]) {
         printf("-layout-sample must be a non-negative number of vertices.\n");
         return 1;
     }
+    if (s.layout_method != "pca" && s.layout_method != "tsne") {
+        printf("-layout-method must be pca or tsne.\n");
+        return 1;
+    }
+    const bool tsne = s.layout_method == "tsne";
+    if (tsne && s.layout != 0 && s.layout != 2 && s.layout != 3) {
+        printf("-layout with -layout-method tsne must be 2 or 3.\n");
+        return 1;
+    }
+    if (tsne && !(s.layout_perplexity > 1.0 && 3.0 * s.layout_perplexity < F2V_NEAREST_MAX_K + 1.0)) {
+        printf("-layout-perplexity must be above 1 with at most %d neighbours (3 x perplexity).\n", F2V_NEAREST_MAX_K);
+        return 1;
+    }
+    if (tsne && (s.layout_iters < 1 || s.layout_iters > 0x7FFFFFFF)) {
+        printf("-layout-iters must be at least 1.\n");
+        return 1;
+    }
     if (s.layout > 0 && s.gpus > 1) {
         printf("-layout is not available with -gpus > 1 (it projects and scores one GPU's matrix).\n");
         return 1;
@@ -285,6 +307,8 @@ int main(int argc, char *argv[]) {
     try {
         CSRGraph graph;
         SetInputMatricesAsCSR(graph, s.input, s.cache != 0);  // host only: read once, inherited by the forked ranks
+        if (tsne && s.layout > 0 && graph.rows > 131072)
+            throw std::runtime_error("-layout-method tsne lays out at most 131072 vertices (every iteration visits all pairs): lay out a subset with Engine.tsne(ids=...), or use -layout-method pca");
         std::vector<pid_t> kids;
         if (s.gpus > 1) {
             char tmpl[] = "/tmp/f2v_ranks_XXXXXX";
@@ -325,7 +349,8 @@ int main(int argc, char *argv[]) {
             if (s.cluster > 0 && rank == 0) algo.writeClusters((uint32_t)s.cluster, (uint32_t)s.cluster_iters, (uint32_t)s.cluster_restarts, (uint64_t)s.seed);
             if (!s.classify.empty() && rank == 0) algo.classify(s.classify, s.classify_frac, (uint32_t)s.classify_splits, (uint64_t)s.seed);
             if (!s.separation.empty() && rank == 0) algo.separation(s.separation, (uint32_t)s.separation_sample, (uint64_t)s.seed);
-            if (s.layout > 0 && rank == 0) algo.layout((uint32_t)s.layout, (uint32_t)s.layout_neighbours, (uint32_t)s.layout_sample, (uint64_t)s.seed);
+            if (s.layout > 0 && rank == 0)
+                algo.layout((uint32_t)s.layout, (uint32_t)s.layout_neighbours, (uint32_t)s.layout_sample, (uint64_t)s.seed, tsne, s.layout_perplexity, (uint32_t)s.layout_iters);
             if (!s.foldin.empty() && rank == 0) algo.foldIn(s.foldin, (int)s.option, (uint32_t)s.foldin_iters, (INDEXTYPE)s.nsamples, (VALUETYPE)s.lr, foldin_init, (uint64_t)s.seed);
             if (!s.linkpredict.empty() && rank == 0) algo.linkPredict(linkpredict_feature, s.linkpredict_frac, (uint32_t)s.linkpredict_ratio, (uint64_t)s.seed);
             const double t = algo.gpu_train_seconds;

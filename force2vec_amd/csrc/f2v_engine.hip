@@ -40,6 +40,7 @@
 #include "f2v_exact.hip.h"
 #include "f2v_foldin.hip.h"
 #include "f2v_linkpairs.hip.h"
+#include "f2v_tsne.hip.h"
 
 using namespace f2v;
 
@@ -293,6 +294,18 @@ struct f2v_ctx {
         DevTimer timer;
         uint32_t short_max = 256;
     } link;
+    // t-SNE layout (f2v_tsne_affinities, f2v_tsne): the workspace f2v.h states, allocated on first use and grown for a larger call;
+    // "tsne_rows" (0 = automatic | 64 | 128 | 256): rows per workgroup of tsne_pair_kernel, "tsne_slices" (0 = automatic): spans per
+    // workgroup of it -- placement only
+    struct Tsne {
+        DevBuf<float> d_G, d_dist, d_yf;  // the gathered rows, the neighbours' scores, yf twice
+        DevBuf<uint32_t> d_sid, d_nbr, d_prow, d_pcol;
+        DevBuf<double> d_cond, d_pval, d_state, d_ws, d_part, d_out;  // d_state: Y, update, gains; d_out: Z, then the KL values
+        DevTimer timer;
+        uint32_t rows = 0, slices = 0;
+        std::vector<uint32_t> kl_iters;  // f2v_tsne_kl_log
+        std::vector<double> kl_values;
+    } ts;
     uint32_t last_wide_width = 0;  // the layout width of the last wide-form f2v_train ("last_wide_width")
     bool last_wide_early = false;  // ... and whether it ran the kernel's EARLY form ("last_wide_early")
     int last_train_form = 0;  // how the last f2v_train launched: 0 one launch per minibatch, 1 chained, 2 chained in the wide form ("last_train_form")
@@ -2268,6 +2281,10 @@ const Param kParams[] = {
     {"trust_chunk", F2V_FIELD(lay.chunk), kValue, kKeep, in<1, 1048576>, "trust_chunk must be 1..1048576"},
     // sample rows per workgroup of trust_rank_kernel (0: 64; 128 holds where k <= 32, its thresholds live in LDS); results do not depend on it
     {"trust_block", F2V_FIELD(lay.block), kValue, kKeep, one_of<0, 64, 128>, "trust_block must be 0, 64 or 128"},
+    // rows per workgroup of tsne_pair_kernel (0: 64 below 4096 points, else 256) and spans per workgroup of it (0: one); results do
+    // not depend on them
+    {"tsne_rows", F2V_FIELD(ts.rows), kValue, kKeep, one_of<0, 64, 128, 256>, "tsne_rows must be 0 (automatic), 64, 128 or 256"},
+    {"tsne_slices", F2V_FIELD(ts.slices), kValue, kKeep, in<0, 65536>, "tsne_slices must be 0 (automatic) ... 65536"},
     // rows per workgroup of exact_pair_kernel (0: from the minibatch and the spans, so that the grid fills the card); results do not depend on it
     {"exact_rows", F2V_FIELD(ex.rows), kValue, kKeep, one_of<0, 4, 8, 16>, "exact_rows must be 0 (automatic), 4, 8 or 16"},
     // fewest rows of a minibatch that run the quarter-wave pair kernel where D allows it (0: every minibatch); results do not depend on it
@@ -3525,11 +3542,13 @@ int launch_nearest_t(f2v_ctx *c, const NnArgs &a, uint32_t qblocks, uint32_t spl
 // or the host vectors `vecs`; they are run in chunks of "nearest_chunk" queries, each chunk as gather / norms / nearest_kernel /
 // merge (/ count) on the handle's stream between two events.  ids_out / scores_out may be nullptr (the recall count needs neither).
 // `X`: the n x D matrix that is searched -- the handle's, or f2v_trustworthiness's second matrix (row queries, no cosine, no CSR flag);
-// `d_ids_dst` (may be nullptr): device array that also receives the ids, nq x k.
+// `d_ids_dst` (may be nullptr): device array that also receives the ids, nq x k; `d_scores_dst`: the same for the scores; `n_rows`
+// (0: n): the rows of `X` where it is not a matrix over the vertices (f2v_tsne_affinities' gathered sample).
 int nearest_run_on(f2v_ctx *c, const float *X, uint32_t D, const uint32_t *qids, bool all, const float *vecs, uint32_t nq, uint32_t k, int metric,
-                   uint32_t flags, uint32_t *ids_out, float *scores_out, uint64_t *recall_out, double *seconds_out, uint32_t *d_ids_dst) {
+                   uint32_t flags, uint32_t *ids_out, float *scores_out, uint64_t *recall_out, double *seconds_out, uint32_t *d_ids_dst,
+                   float *d_scores_dst = nullptr, uint32_t n_rows = 0) {
     f2v_ctx::Nearest &w = c->nn;
-    const uint32_t n = c->n;
+    const uint32_t n = n_rows ? n_rows : c->n;
     const bool rows = qids || all, cosine = metric == F2V_SIM_COSINE;
     const char *what = "nearest-neighbour";
     F2VC(w.d_counts.reserve(c, 2, what));
@@ -3593,6 +3612,7 @@ int nearest_run_on(f2v_ctx *c, const float *X, uint32_t D, const uint32_t *qids,
                                (const uint32_t *)c->d_rowptr, (const uint32_t *)c->d_colids, w.d_counts);
         HIPC(hipGetLastError());
         if (d_ids_dst) HIPC(hipMemcpyAsync(d_ids_dst + (size_t)done * k, w.d_ids, slots * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+        if (d_scores_dst) HIPC(hipMemcpyAsync(d_scores_dst + (size_t)done * k, w.d_scores, slots * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
         F2VC(w.timer.stop(c->stream));
         if (ids_out) HIPC(hipMemcpyAsync(ids_out + (size_t)done * k, w.d_ids, slots * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         if (scores_out) HIPC(hipMemcpyAsync(scores_out + (size_t)done * k, w.d_scores, slots * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -4527,6 +4547,282 @@ int f2v_link_pairs(f2v_handle c, uint32_t ratio, uint64_t seed, uint32_t *u_out,
         info->seconds = seconds;
         info->candidates = sums[3];
     }
+    return F2V_OK;
+}
+
+}  // extern "C"
+
+// ---- t-SNE layout (f2v_tsne.hip.h; definition in include/f2v.h) -------------------------------------------------------------------
+namespace {
+
+// The two calls' checks on the sample -- `sid` receives it, every vertex where sample_ids is NULL -- then settled_enter
+int tsne_enter(f2v_ctx *c, const char *who, const uint32_t *sample_ids, uint32_t m, std::vector<uint32_t> &sid) {
+    const uint32_t n = c->n;
+    if (!sample_ids) m = n;
+    if (m < 8) return fail(F2V_EINVAL, "%s: %u points are fewer than 8", who, m);
+    if (m > n) return fail(F2V_EINVAL, "%s: %u samples of %u vertices hold a duplicate", who, m, n);
+    sid.resize(m);
+    std::vector<bool> seen(n, false);
+    for (uint32_t i = 0; i < m; i++) {
+        const uint32_t v = sample_ids ? sample_ids[i] : i;
+        if (v >= n) return fail(F2V_EINVAL, "%s: sample %u names vertex %u of %u", who, i, v, n);
+        if (seen[v]) return fail(F2V_EINVAL, "%s: sample %u names vertex %u a second time", who, i, v);
+        seen[v] = true;
+        sid[i] = v;
+    }
+    return settled_enter(c, who);
+}
+
+// k = floor(3 perplexity) and its range
+int tsne_neighbours(const char *who, double perplexity, uint32_t m, uint32_t *k) {
+    if (!(perplexity > 1.0)) return fail(F2V_EINVAL, "%s: the perplexity must be a number above 1", who);
+    const double k3 = std::floor(3.0 * perplexity);
+    if (k3 > (double)F2V_NEAREST_MAX_K) return fail(F2V_EINVAL, "%s: floor(3 x perplexity) is above %d neighbours", who, F2V_NEAREST_MAX_K);
+    if (k3 >= (double)m) return fail(F2V_EINVAL, "%s: floor(3 x perplexity) = %u neighbours need more than %u points", who, (uint32_t)k3, m);
+    *k = (uint32_t)k3;
+    return F2V_OK;
+}
+
+// The symmetric P of the sample on the host: the rows gathered, their k nearest among themselves by the nearest-neighbour kernels as
+// they are, the conditional affinities on the device, the symmetric sum on the host.  *seconds += the device time of the launches.
+int tsne_affinities_host(f2v_ctx *c, const std::vector<uint32_t> &sid, uint32_t k, double perplexity, std::vector<uint32_t> &rowptr,
+                         std::vector<uint32_t> &colids, std::vector<double> &values, double *seconds) {
+    f2v_ctx::Tsne &w = c->ts;
+    const uint32_t m = (uint32_t)sid.size(), D = c->D;
+    const size_t slots = (size_t)m * k;
+    const char *what = "t-SNE";
+    F2VC(w.d_sid.reserve(c, m, what));
+    F2VC(w.d_G.reserve(c, (size_t)m * D, what));
+    F2VC(w.d_nbr.reserve(c, slots, what));
+    F2VC(w.d_dist.reserve(c, slots, what));
+    F2VC(w.d_cond.reserve(c, slots, what));
+    HIPC(hipMemcpyAsync(w.d_sid, sid.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    F2VC(w.timer.start(c->stream));
+    hipLaunchKernelGGL(nearest_gather_kernel, dim3(std::min<size_t>(((size_t)m * D + 255) / 256, 4096)), dim3(256), 0, c->stream, (const float *)c->d_X[c->cur],
+                       (const uint32_t *)w.d_sid, m, D, w.d_G);
+    HIPC(hipGetLastError());
+    F2VC(w.timer.stop(c->stream));
+    std::vector<uint32_t> nbr(slots);
+    double sec = 0.0;
+    F2VC(nearest_run_on(c, w.d_G, D, nullptr, true, nullptr, m, k, F2V_SIM_L2, F2V_NEAREST_EXCLUDE_SELF, nbr.data(), nullptr, nullptr, &sec, w.d_nbr, w.d_dist, m));
+    *seconds += sec;
+    F2VC(w.timer.seconds(seconds));  // (the queries have synchronised the stream)
+    F2VC(w.timer.start(c->stream));
+    hipLaunchKernelGGL(tsne_calibrate_kernel, dim3((m + 255) / 256), dim3(256), 0, c->stream, (const float *)w.d_dist, m, k, perplexity, w.d_cond);
+    HIPC(hipGetLastError());
+    F2VC(w.timer.stop(c->stream));
+    std::vector<double> cond(slots);
+    HIPC(hipMemcpyAsync(cond.data(), w.d_cond, slots * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    F2VC(check_kernel_err(c, "t-SNE affinities"));
+    F2VC(w.timer.seconds(seconds));
+    for (size_t e = 0; e < slots; e++)
+        if (nbr[e] >= m) return fail(F2V_EINVAL, "t-SNE affinities: point %zu has fewer than %u neighbours", e / k, k);
+    tsne_symmetrize_host(nbr.data(), cond.data(), m, k, rowptr, colids, values);
+    return F2V_OK;
+}
+
+template <int D2, int ROWS>
+void launch_tsne_pair_t(f2v_ctx *c, const TsnePairArgs &a, uint32_t slices) {
+    hipLaunchKernelGGL((tsne_pair_kernel<D2, ROWS>), dim3((a.m + ROWS - 1) / ROWS, slices), dim3(ROWS), 0, c->stream, a);
+}
+
+template <int D2>
+void launch_tsne_pair(f2v_ctx *c, const TsnePairArgs &a, uint32_t rows, uint32_t slices) {
+    if (rows == 64) launch_tsne_pair_t<D2, 64>(c, a, slices);
+    else if (rows == 128) launch_tsne_pair_t<D2, 128>(c, a, slices);
+    else launch_tsne_pair_t<D2, 256>(c, a, slices);
+}
+
+}  // namespace
+
+extern "C" {
+
+int f2v_tsne_affinities(f2v_handle c, const uint32_t *sample_ids, uint32_t m, double perplexity, uint32_t *rowptr_out, uint32_t *colids_out,
+                        double *values_out, uint64_t cap, uint64_t *nnz_out, double *seconds_out) {
+    if (!c || !rowptr_out || !colids_out || !values_out || !nnz_out) return fail(F2V_EINVAL, "f2v_tsne_affinities: null argument");
+    if (!sample_ids) m = c->n;
+    uint32_t k = 0;
+    if (m >= 8) F2VC(tsne_neighbours("f2v_tsne_affinities", perplexity, m, &k));
+    std::vector<uint32_t> sid, rowptr, colids;
+    std::vector<double> values;
+    F2VC(tsne_enter(c, "f2v_tsne_affinities", sample_ids, m, sid));
+    double seconds = 0.0;
+    F2VC(tsne_affinities_host(c, sid, k, perplexity, rowptr, colids, values, &seconds));
+    *nnz_out = colids.size();
+    if (seconds_out) *seconds_out = seconds;
+    if (colids.size() > cap) return fail(F2V_EINVAL, "f2v_tsne_affinities: %zu entries need more room than cap = %llu", colids.size(), (unsigned long long)cap);
+    memcpy(rowptr_out, rowptr.data(), rowptr.size() * sizeof(uint32_t));
+    memcpy(colids_out, colids.data(), colids.size() * sizeof(uint32_t));
+    memcpy(values_out, values.data(), values.size() * sizeof(double));
+    return F2V_OK;
+}
+
+int f2v_tsne(f2v_handle c, const uint32_t *sample_ids, uint32_t m, uint32_t d2, const f2v_tsne_params *params, const uint32_t *p_rowptr,
+             const uint32_t *p_colids, const double *p_values, const double *y_init, float *y_out, f2v_tsne_t *info) {
+    const char *who = "f2v_tsne";
+    if (!c || !y_out || !info) return fail(F2V_EINVAL, "f2v_tsne: null argument");
+    if (d2 != 2 && d2 != 3) return fail(F2V_EINVAL, "f2v_tsne: d2 = %u is neither 2 nor 3", d2);
+    f2v_tsne_params p{};
+    if (params) p = *params;
+    if (!(p.perplexity >= 0.0) || !(p.exaggeration >= 0.0) || !(p.learning_rate >= 0.0) || p.exaggeration > 1e300 || p.learning_rate > 1e300)
+        return fail(F2V_EINVAL, "f2v_tsne: a parameter is negative or not a number");
+    if (p.perplexity == 0.0) p.perplexity = 30.0;
+    if (p.exaggeration == 0.0) p.exaggeration = 12.0;
+    if (p.iters == 0) p.iters = 1000;
+    if (p.exaggeration_iters == 0) p.exaggeration_iters = 250;
+    const bool given = p_rowptr || p_colids || p_values;
+    if (given && !(p_rowptr && p_colids && p_values)) return fail(F2V_EINVAL, "f2v_tsne: P is given in part (row pointers, column ids and values go together)");
+    if (!sample_ids) m = c->n;
+    uint32_t k = 0;
+    if (!given && m >= 8) F2VC(tsne_neighbours(who, p.perplexity, m, &k));
+    if (given && m >= 8) {
+        if (p_rowptr[0] != 0) return fail(F2V_EINVAL, "f2v_tsne: P's row pointers do not start at 0");
+        for (uint32_t i = 0; i < m; i++) {
+            if (p_rowptr[i + 1] < p_rowptr[i]) return fail(F2V_EINVAL, "f2v_tsne: P's row pointers descend at row %u", i);
+            for (uint32_t e = p_rowptr[i]; e < p_rowptr[i + 1]; e++) {
+                if (p_colids[e] >= m) return fail(F2V_EINVAL, "f2v_tsne: row %u of P names column %u of %u", i, p_colids[e], m);
+                if (e > p_rowptr[i] && p_colids[e] <= p_colids[e - 1]) return fail(F2V_EINVAL, "f2v_tsne: the column ids of row %u of P do not ascend", i);
+                if (!(p_values[e] >= 2.2250738585072014e-308 && p_values[e] <= 1.7976931348623157e308))
+                    return fail(F2V_EINVAL, "f2v_tsne: entry %u of P is not a positive normal number", e);
+            }
+        }
+    }
+    std::vector<uint32_t> sid, rowptr, colids;
+    std::vector<double> values;
+    F2VC(tsne_enter(c, who, sample_ids, m, sid));
+    f2v_ctx::Tsne &w = c->ts;
+    w.kl_iters.clear();
+    w.kl_values.clear();
+    const uint32_t n = c->n;
+    double seconds = 0.0;
+    if (!given) {
+        F2VC(tsne_affinities_host(c, sid, k, p.perplexity, rowptr, colids, values, &seconds));
+        p_rowptr = rowptr.data();
+        p_colids = colids.data();
+        p_values = values.data();
+    }
+    const size_t nnz = p_rowptr[m], cells = (size_t)m * d2;
+    // the start: Y, update = 0, gains = 1 and yf
+    std::vector<double> state(3 * cells, 0.0);
+    if (y_init) {
+        memcpy(state.data(), y_init, cells * sizeof(double));
+    } else {
+        std::vector<float> proj((size_t)n * d2);
+        double var[3] = {0.0, 0.0, 0.0};
+        f2v_pca_t pi{};
+        F2VC(f2v_pca(c, d2, proj.data(), nullptr, nullptr, var, &pi));
+        if (!(var[0] > 0.0)) return fail(F2V_EINVAL, "f2v_tsne: the matrix's first principal component has no variance: give y_init");
+        const double scale = 1e-4 / std::sqrt(var[0]);
+        for (uint32_t i = 0; i < m; i++)
+            for (uint32_t d = 0; d < d2; d++) state[(size_t)i * d2 + d] = (double)proj[(size_t)sid[i] * d2 + d] * scale;
+    }
+    std::vector<float> yf(cells);
+    for (size_t i = 0; i < cells; i++) {
+        yf[i] = (float)state[i];
+        state[2 * cells + i] = 1.0;
+    }
+    const double lr = p.learning_rate > 0.0 ? p.learning_rate : std::max((double)m / p.exaggeration / 4.0, 50.0);
+    const uint32_t spans = (m + kTsneSpanCols - 1) / kTsneSpanCols, pieces = (m + kTsnePiece - 1) / kTsnePiece;
+    const uint32_t logged = p.kl_every ? p.iters / p.kl_every : 0;
+    const char *what = "t-SNE";
+    F2VC(w.d_prow.reserve(c, (size_t)m + 1, what));
+    F2VC(w.d_pcol.reserve(c, nnz, what));
+    F2VC(w.d_pval.reserve(c, nnz, what));
+    F2VC(w.d_state.reserve(c, 3 * cells, what));
+    F2VC(w.d_yf.reserve(c, 2 * cells, what));
+    F2VC(w.d_ws.reserve(c, (size_t)spans * (1 + d2) * m, what));
+    F2VC(w.d_part.reserve(c, pieces, what));
+    F2VC(w.d_out.reserve(c, (size_t)logged + 2, what));
+    HIPC(hipMemcpyAsync(w.d_prow, p_rowptr, ((size_t)m + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(w.d_pcol, p_colids, nnz * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(w.d_pval, p_values, nnz * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(w.d_state, state.data(), 3 * cells * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(w.d_yf, yf.data(), cells * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    // placement (tools/tsne_time.py): 256 rows per workgroup from 4096 points on, and one span per workgroup -- the most wavefronts;
+    // several spans per workgroup were slower at every size measured
+    const uint32_t rows = w.rows ? w.rows : (m < 4096 ? 64u : 256u);
+    const uint32_t per_slice = std::min(spans, w.slices ? w.slices : 1u);
+    const uint32_t slices = (spans + per_slice - 1) / per_slice;
+    float *yfb[2] = {w.d_yf, w.d_yf + cells};
+    double *Z = w.d_out;  // d_out: Z, the logged KL values, the final KL
+    auto pair_z = [&](const float *y) {
+        TsnePairArgs a{y, w.d_ws, m, spans, per_slice};
+        if (d2 == 2) launch_tsne_pair<2>(c, a, rows, slices);
+        else launch_tsne_pair<3>(c, a, rows, slices);
+        hipLaunchKernelGGL(tsne_zpiece_kernel, dim3(pieces), dim3(64), 0, c->stream, (const double *)w.d_ws, m, spans, d2, w.d_part);
+        hipLaunchKernelGGL(tsne_seqsum_kernel, dim3(1), dim3(64), 0, c->stream, (const double *)w.d_part, pieces, Z);
+    };
+    auto kl = [&](const float *y, double *out) {
+        TsneKlArgs a{Z, w.d_prow, w.d_pcol, w.d_pval, y, w.d_part, m};
+        if (d2 == 2) hipLaunchKernelGGL(tsne_kl_kernel<2>, dim3(pieces), dim3(64), 0, c->stream, a);
+        else hipLaunchKernelGGL(tsne_kl_kernel<3>, dim3(pieces), dim3(64), 0, c->stream, a);
+        hipLaunchKernelGGL(tsne_seqsum_kernel, dim3(1), dim3(64), 0, c->stream, (const double *)w.d_part, pieces, out);
+    };
+    F2VC(w.timer.start(c->stream));
+    int cur = 0;
+    bool fresh = false;  // the span sums and Z are those of yfb[cur]
+    for (uint32_t it = 0; it < p.iters; it++) {
+        if (!fresh) pair_z(yfb[cur]);
+        const bool early = it < p.exaggeration_iters;
+        TsneStepArgs a{};
+        a.ws = w.d_ws;
+        a.Z = Z;
+        a.rowptr = w.d_prow;
+        a.colids = w.d_pcol;
+        a.values = w.d_pval;
+        a.yf_in = yfb[cur];
+        a.yf_out = yfb[cur ^ 1];
+        a.y = w.d_state;
+        a.update = w.d_state + cells;
+        a.gains = w.d_state + 2 * cells;
+        a.m = m;
+        a.spans = spans;
+        a.ex = early ? p.exaggeration : 1.0;
+        a.momentum = early ? 0.5 : 0.8;
+        a.lr = lr;
+        if (d2 == 2) hipLaunchKernelGGL(tsne_step_kernel<2>, dim3((m + 3) / 4), dim3(256), 0, c->stream, a);
+        else hipLaunchKernelGGL(tsne_step_kernel<3>, dim3((m + 3) / 4), dim3(256), 0, c->stream, a);
+        cur ^= 1;
+        fresh = false;
+        const bool last = it + 1 == p.iters, log = p.kl_every && (it + 1) % p.kl_every == 0;
+        if (last || log) {
+            pair_z(yfb[cur]);
+            fresh = true;
+            if (log) {
+                kl(yfb[cur], w.d_out + 1 + w.kl_iters.size());
+                w.kl_iters.push_back(it + 1);
+            }
+            if (last) kl(yfb[cur], w.d_out + 1 + logged);
+        }
+        HIPC(hipGetLastError());
+    }
+    F2VC(w.timer.stop(c->stream));
+    std::vector<double> out((size_t)logged + 2);
+    HIPC(hipMemcpyAsync(out.data(), w.d_out, out.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipMemcpyAsync(y_out, yfb[cur], cells * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    F2VC(check_kernel_err(c, who));
+    F2VC(w.timer.seconds(&seconds));
+    w.kl_values.assign(out.begin() + 1, out.begin() + 1 + w.kl_iters.size());
+    info->kl = out[1 + logged];
+    info->z = out[0];
+    info->learning_rate = lr;
+    info->seconds = seconds;
+    info->nnz = nnz;
+    info->k = k;
+    info->reserved = 0;
+    return F2V_OK;
+}
+
+int f2v_tsne_kl_log(f2v_handle c, uint32_t *iterations_out, double *values_out, uint32_t cap, uint32_t *count_out) {
+    if (!c || !count_out || (cap && (!iterations_out || !values_out))) return fail(F2V_EINVAL, "f2v_tsne_kl_log: null argument");
+    const uint32_t count = (uint32_t)c->ts.kl_values.size();  // (empty after a call that failed)
+    for (uint32_t i = 0; i < count && i < cap; i++) {
+        iterations_out[i] = c->ts.kl_iters[i];
+        values_out[i] = c->ts.kl_values[i];
+    }
+    *count_out = count;
     return F2V_OK;
 }
 

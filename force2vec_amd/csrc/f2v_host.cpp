@@ -201,6 +201,45 @@ void pca_jacobi_host(double *A, double *V, uint32_t D, uint32_t *sweeps, uint32_
     }
 }
 
+// The symmetric affinities of f2v.h's t-SNE definition from the conditional ones: row i's own entries (nbr, cond: m x k, a row's ids
+// distinct) and the entries that name i, equal columns added, divided by 2 m, entries below the smallest normal double dropped.
+void tsne_symmetrize_host(const uint32_t *nbr, const double *cond, uint32_t m, uint32_t k, std::vector<uint32_t> &rowptr, std::vector<uint32_t> &colids,
+                          std::vector<double> &values) {
+    std::vector<uint32_t> start(m + 1, 0);  // the transpose: who names j
+    for (size_t e = 0; e < (size_t)m * k; e++) start[nbr[e] + 1]++;
+    for (uint32_t j = 0; j < m; j++) start[j + 1] += start[j];
+    std::vector<uint32_t> from((size_t)m * k), fill(start.begin(), start.end() - 1);
+    std::vector<double> fval((size_t)m * k);
+    for (uint32_t i = 0; i < m; i++)
+        for (uint32_t q = 0; q < k; q++) {
+            const size_t e = (size_t)i * k + q;
+            const uint32_t at = fill[nbr[e]]++;
+            from[at] = i;
+            fval[at] = cond[e];
+        }
+    const double denom = 2.0 * (double)m;
+    rowptr.assign(m + 1, 0);
+    colids.clear();
+    values.clear();
+    std::vector<std::pair<uint32_t, double>> row;
+    for (uint32_t i = 0; i < m; i++) {
+        row.clear();
+        for (uint32_t q = 0; q < k; q++) row.push_back({nbr[(size_t)i * k + q], cond[(size_t)i * k + q]});
+        for (uint32_t e = start[i]; e < start[i + 1]; e++) row.push_back({from[e], fval[e]});
+        std::sort(row.begin(), row.end(), [](const std::pair<uint32_t, double> &a, const std::pair<uint32_t, double> &b) { return a.first < b.first; });
+        for (size_t e = 0; e < row.size(); e++) {
+            double sum = row[e].second;
+            if (e + 1 < row.size() && row[e + 1].first == row[e].first) sum = sum + row[++e].second;
+            const double p = sum / denom;
+            if (!(p < 2.2250738585072014e-308)) {
+                colids.push_back(row[e].first);
+                values.push_back(p);
+            }
+        }
+        rowptr[i + 1] = (uint32_t)colids.size();
+    }
+}
+
 void walks_host(Rand &g, const uint32_t *rp, const uint32_t *ci, uint32_t n, uint64_t nnz, uint32_t *walks) {
     constexpr uint32_t L = (uint32_t)kWalkLength, SMAX = 64, RING = 1024, MASK = RING - 1;
     static_assert(RING >= 2 * SMAX * L && (RING & MASK) == 0, "the ring holds every draw a walk in flight may ask for");

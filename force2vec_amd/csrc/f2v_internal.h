@@ -3,6 +3,7 @@
 #define F2V_INTERNAL_H_
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 namespace f2v {
 
@@ -47,6 +48,11 @@ void walks_host(Rand &g, const uint32_t *rowptr, const uint32_t *colids, uint32_
 // its diagonal); V receives the eigenvectors as columns.  Plain fp64, one rounding per operation (f2v_host.cpp is built without
 // contraction).  *sweeps: sweeps run, the last one without a rotation included; *converged: 0 after 64 sweeps that all rotated.
 void pca_jacobi_host(double *A, double *V, uint32_t D, uint32_t *sweeps, uint32_t *converged);
+
+// The symmetric sparse P of the t-SNE definition (f2v.h) from the k neighbour ids and conditional affinities of each of m points: a
+// CSR whose column ids ascend inside a row.  Plain fp64, built without contraction like pca_jacobi_host.
+void tsne_symmetrize_host(const uint32_t *nbr, const double *cond, uint32_t m, uint32_t k, std::vector<uint32_t> &rowptr, std::vector<uint32_t> &colids,
+                          std::vector<double> &values);
 
 }  // namespace f2v
 #endif

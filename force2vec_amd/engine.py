@@ -409,6 +409,58 @@ class Engine:
         self.last_layout_seconds = out.seconds
         return Trust(out.trustworthiness, out.continuity, out.overlap, out.penalty_x, out.penalty_y, out.hits, out.seconds, px, py)
 
+    # -- t-SNE layout (include/f2v.h: definition; a function of the matrix, the sample, the parameters and P / the start where given) --
+    def _tsne_sample(self, ids):
+        q = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        return q, self.n if q is None else len(q)
+
+    def tsne_affinities(self, perplexity=30, ids=None):
+        """The symmetric sparse affinity matrix P of t-SNE over the rows `ids` (None: every vertex), on the GPU -> (rowptr uint32
+        [m + 1], colids uint32 [nnz], values float64 [nnz]); indices are positions in `ids`, column ids ascend inside a row."""
+        q, m = self._tsne_sample(ids)
+        p = float(perplexity)
+        cap = 2 * m * (int(min(max(3.0 * p, 1.0), float(_lib.NEAREST_MAX_K))) if p == p else 1)  # 2 m k always suffices
+        rowptr, colids, values = np.empty(m + 1, dtype=np.uint32), np.empty(max(cap, 1), dtype=np.uint32), np.empty(max(cap, 1), dtype=np.float64)
+        nnz, sec = C.c_uint64(), C.c_double()
+        self._ck(self._L.f2v_tsne_affinities(self._h, _u32(q) if q is not None else None, m, p, _u32(rowptr), _u32(colids),
+                                             values.ctypes.data_as(_lib.f64p), cap, C.byref(nnz), C.byref(sec)))
+        self.last_layout_seconds = sec.value
+        return rowptr, colids[: nnz.value].copy(), values[: nnz.value].copy()
+
+    def tsne(self, d=2, perplexity=30, iters=1000, ids=None, P=None, init=None, exaggeration=12, exaggeration_iters=250, learning_rate=None,
+             kl_every=0, details=False):
+        """The exact t-SNE layout of the rows `ids` (None: every vertex) in d = 2 or 3 dimensions, on the GPU, deterministic -> Y float32
+        [m, d], or with details=True (Y, info dict: kl, z, learning_rate, seconds, nnz, k, kl_iters uint32 [..], kl_values float64
+        [..]: the divergence after every `kl_every`-th iteration).  P: (rowptr, colids, values) as tsne_affinities returns it (None:
+        computed from `perplexity`); init: float64 [m, d] (None: scikit-learn's init="pca", the PCA of the whole matrix scaled to a
+        standard deviation of 1e-4).  Zero for a parameter selects its default.  `last_layout_seconds` keeps the device time."""
+        q, m = self._tsne_sample(ids)
+        par = _lib.TsneParams(float(perplexity), float(exaggeration), float(learning_rate or 0.0), int(iters), int(exaggeration_iters), int(kl_every), 0)
+        f64 = lambda a: a.ctypes.data_as(_lib.f64p)  # noqa: E731
+        pr = pc = pv = y0 = None
+        if P is not None:
+            pr, pc, pv = (np.ascontiguousarray(P[0], dtype=np.uint32), np.ascontiguousarray(P[1], dtype=np.uint32), np.ascontiguousarray(P[2], dtype=np.float64))
+            if len(pr) != m + 1 or len(pc) != len(pv) or int(pr[-1]) != len(pc):
+                raise ValueError("tsne: P must be (rowptr [m + 1], colids [nnz], values [nnz])")
+        if init is not None:
+            y0 = np.ascontiguousarray(init, dtype=np.float64)
+            if y0.shape != (m, d):
+                raise ValueError("tsne: init must be [%d, %d]" % (m, d))
+        y = np.empty((m, d), dtype=np.float32)
+        info = _lib.TsneInfo()
+        self._ck(self._L.f2v_tsne(self._h, _u32(q) if q is not None else None, m, d, C.byref(par), _u32(pr) if pr is not None else None,
+                                  _u32(pc) if pc is not None else None, f64(pv) if pv is not None else None, f64(y0) if y0 is not None else None,
+                                  _f32(y), C.byref(info)))
+        self.last_layout_seconds = info.seconds
+        if not details:
+            return y
+        count = C.c_uint32()
+        self._ck(self._L.f2v_tsne_kl_log(self._h, None, None, 0, C.byref(count)))
+        its, vals = np.zeros(max(count.value, 1), dtype=np.uint32), np.zeros(max(count.value, 1), dtype=np.float64)
+        self._ck(self._L.f2v_tsne_kl_log(self._h, _u32(its), f64(vals), count.value, C.byref(count)))
+        return y, dict(kl=info.kl, z=info.z, learning_rate=info.learning_rate, seconds=info.seconds, nnz=info.nnz, k=info.k,
+                       kl_iters=its[: count.value], kl_values=vals[: count.value])
+
     # -- fold-in (include/f2v.h: definition; a function of the matrix, the lists, option, iters, ns, lr, init, seed and index_base alone) --
     def fold_in(self, rowptr, colids=None, option=5, iters=300, ns=5, lr=0.02, init="mean", seed=1, index_base=0, details=False):
         """Vectors for m new vertices whose neighbours are existing vertices, on the GPU: `iters` epochs of the option's row update

@@ -648,7 +648,85 @@ F2V_API int f2v_trustworthiness(f2v_handle h, const float *Y /* n x d2 */, uint3
                         uint32_t nq, uint64_t *penalty_x_out /* per sample, may be NULL */, uint64_t *penalty_y_out /* per sample, may be NULL */,
                         f2v_trust_t *out);
 
-/* ---- fold-in ---------------------------------------------------------------------------------------------------------------
+/* ---- t-SNE layout ---------------------------------------------------------------------------------------------------------------
+ * The picture performancescores/runvisualization.py itself draws (:15, :177-181): exact t-SNE (van der Maaten and Hinton 2008, as
+ * scikit-learn runs it with init = "pca") over a sparse neighbour affinity matrix, every order of summation fixed.  The result is a
+ * function of (X, samples, parameters, P or y_init where given) alone: never of a tunable ("tsne_rows", rows per workgroup of the pair
+ * kernel, 0 = automatic | 64 | 128 | 256; "tsne_slices", spans per workgroup of it, 0 = one; the "nearest_*" tunables), of launch
+ * shapes, of the handle or of the order in which workgroups run; no float atomics, no in-grid waits.
+ *
+ *   points      the laid-out points are rows sample_ids[0 .. m) of X in that order (NULL: every vertex, m = n); everything below
+ *               speaks of positions 0 .. m-1.  A subset is laid out exactly as a handle holding only those rows would be.
+ *   neighbours  k = floor(3 * perplexity); N(i) is the result order of f2v_nearest_rows with F2V_SIM_L2 and F2V_NEAREST_EXCLUDE_SELF
+ *               over the m points alone; d_ij = the negated score (the fp32 fma chain of squared differences), converted exactly to fp64.
+ *   conditional affinities (scikit-learn's _binary_search_perplexity, all fp64)   per point beta = 1, lo = -inf, hi = +inf; one
+ *               evaluation: p_j = exp(-beta * d_ij), S = sum p_j and T = sum d_ij * p_j over N(i) in result order, each from +0; S == 0: S =
+ *               1e-8; H = log(S) + (beta * T) / S; diff = H - log(perplexity).  |diff| <= 1e-5 or the 100th evaluation ends the search; else
+ *               diff > 0: lo = beta, beta = hi infinite ? beta * 2 : (beta + hi) / 2; otherwise hi = beta, beta = lo infinite ? beta / 2 :
+ *               (beta + lo) / 2.  p_(j|i) = p_j / S of the last evaluation.  exp and log are the device library's: this is the one place
+ *               where a host restatement agrees to a tolerance and not bit for bit -- which is why f2v_tsne accepts P.
+ *   P           p_ij = (p_(j|i) + p_(i|j)) / (2.0 * m) for every pair where either term exists (an absent term is +0); an entry below the
+ *               smallest normal double is dropped; a CSR whose column ids ascend inside a row.  (Host code, built without contraction.)
+ *   start       without y_init: y_ic = (double)(the f2v_pca projection of the handle's WHOLE matrix, d2 components, at row sample_ids[i],
+ *               component c) * (1e-4 / sqrt(variance_out[0] of that call)) -- scikit-learn's init = "pca" scaling, sqrt correctly rounded;
+ *               update = 0, gains = 1.
+ *   state       Y, update and gains are m x d2 doubles; pair arithmetic reads yf = (float)y.
+ *   pair(i, j)  t_d = yf_id - yf_jd, a = (t_0 * t_0 + t_1 * t_1) [+ t_2 * t_2], w = 1.0f / (1.0f + a): every product, sum and the
+ *               division one correctly rounded fp32 operation, no contraction.
+ *   repulsion   the columns j = 0 .. m-1 are cut into pieces of F2V_TSNE_PIECE consecutive ids, the pieces grouped into spans of
+ *               F2V_TSNE_SPAN pieces.  A piece is summed in fp32 from +0 in ascending j, j == i left out: z += w, r_d += (w * w) * t_d
+ *               (rounded products); the piece sums are converted to fp64 and added sequentially from +0 inside their span; the span sums
+ *               are added sequentially from +0 in ascending order: Z_i and R_id.  Z = the Z_i summed in pieces of 64 consecutive rows,
+ *               each from +0, the piece sums added sequentially from +0.
+ *   attraction  fp64, over the nonzeros of row i of P in column order in pieces of 64 entries, each piece from +0, the pieces added
+ *               sequentially from +0: A_id += ((ex * p_ij) * (double)w) * (double)t_d; ex = exaggeration in iterations (0-based) below
+ *               exaggeration_iters and 1.0 from there on.
+ *   step        (scikit-learn's _gradient_descent; fp64, one rounded operation each) g = 4.0 * (A_id - R_id / Z); update * g < 0: gains
+ *               += 0.2, otherwise gains *= 0.8; gains = max(gains, 0.01); g *= gains; update = momentum * update - lr * g; y += update.
+ *               momentum = 0.5 in iterations below exaggeration_iters and 0.8 from there on; learning_rate 0: lr = max((double)m /
+ *               exaggeration / 4.0, 50.0).  Exactly `iters` iterations: there is no early stop.
+ *   KL          = the sum over the nonzeros of p_ij * (flog(p_ij) - (flog((double)w) - flog(Z))) with P unexaggerated, flog the logarithm
+ *               of "exact all-pairs Force2Vec" above, w and Z those of the Y the sum is asked for; a row's entries in pieces of 64 as in
+ *               the attraction, the row sums in pieces of 64 rows as in Z.  Evaluated after the last iteration (info->kl, info->z) and
+ *               after every kl_every-th (f2v_tsne_kl_log, 1-based iteration numbers).
+ *
+ * f2v_tsne_affinities returns P: rowptr_out m + 1 words, colids_out and values_out `cap` entries (2 m k always suffice); *nnz_out
+ * answers also where cap is too small (F2V_EINVAL then).  f2v_tsne runs the iteration from P -- the caller's (all three arrays; its
+ * values positive normal doubles) or, with all three NULL, the one f2v_tsne_affinities would return -- and from y_init (m x d2 doubles)
+ * or the PCA start, and writes y_out = (float)Y, m x d2.  Zeros in f2v_tsne_params select the defaults: perplexity 30, iters 1000,
+ * exaggeration 12, exaggeration_iters 250, learning_rate automatic, kl_every never; params NULL: all defaults.  A P that is given
+ * makes perplexity unused.
+ * Evaluation rules as for f2v_pca: pending minibatches are committed first, the calls run on the handle's stream (plain launches, no
+ * host synchronisation inside the iteration loop) and change neither the matrices nor the rand() stream nor any later training result; on
+ * an attached handle they read this rank's replica.  Workspace, allocated on first use (grown on demand) and freed by f2v_destroy:
+ * the m gathered rows, the nearest-neighbour workspace, m k ids, scores and conditionals, P, 3 m d2 doubles and 2 m d2 floats of state
+ * and m x ceil(m / 1024) x (d2 + 1) doubles of span sums (the largest: 402 MB at m = 131072, d2 = 2).  Cost: m^2 pairs per iteration.
+ * F2V_ESTATE without valid embeddings; F2V_EINVAL for a null output, d2 not 2 or 3 (or, for the PCA start, above D), m < 8, a sample id
+ * >= n or a duplicate sample id, perplexity <= 1 or NaN, k = floor(3 * perplexity) > F2V_NEAREST_MAX_K or >= m, a negative or NaN
+ * parameter, a P given in part, a P whose row pointers do not start at 0 and ascend, whose column ids do not ascend inside a row or
+ * reach m or whose values are not positive normal numbers, a PCA start on a matrix whose first component has variance 0, cap too small. */
+#define F2V_TSNE_PIECE 64
+#define F2V_TSNE_SPAN 16
+typedef struct {
+    double perplexity, exaggeration, learning_rate;
+    uint32_t iters, exaggeration_iters, kl_every, reserved;
+} f2v_tsne_params;
+typedef struct {
+    double kl, z, learning_rate, seconds;  /* kl, z: of the final Y; learning_rate: the one used; seconds: device time of the iteration loop */
+    uint64_t nnz;
+    uint32_t k, reserved;  /* k: 0 where P was given */
+} f2v_tsne_t;
+F2V_API int f2v_tsne_affinities(f2v_handle h, const uint32_t *sample_ids /* NULL: every vertex */, uint32_t m, double perplexity,
+                        uint32_t *rowptr_out /* m + 1 */, uint32_t *colids_out, double *values_out, uint64_t cap, uint64_t *nnz_out,
+                        double *seconds_out /* may be NULL */);
+F2V_API int f2v_tsne(f2v_handle h, const uint32_t *sample_ids /* NULL: every vertex */, uint32_t m, uint32_t d2, const f2v_tsne_params *params /* may be NULL */,
+             const uint32_t *p_rowptr, const uint32_t *p_colids, const double *p_values /* all NULL: computed as above */,
+             const double *y_init /* m x d2, or NULL: the PCA start */, float *y_out /* m x d2 */, f2v_tsne_t *info);
+/* The last f2v_tsne's "kl_every" log: iterations_out (1-based) and values_out receive up to `cap` entries, *count_out the number logged
+ * (both arrays may be NULL with cap = 0: count only). */
+F2V_API int f2v_tsne_kl_log(f2v_handle h, uint32_t *iterations_out, double *values_out, uint32_t cap, uint32_t *count_out);
+
+/* ---- fold-in---------------------------------------------------------------------------------------------------------------
  * What is the vector of a vertex that was not in the graph when it was trained?  A new vertex whose neighbours are all existing
  * vertices is a row whose update reads only frozen rows, so the training rule itself answers: f2v_fold_in runs `iters` epochs of the
  * step kernels' row update for each of m new vertices against the matrix X as it stands, every other row held fixed.  New vertices do
