@@ -22,6 +22,7 @@ SEPARATION_MAX_CLUSTERS, SEPARATION_PIECE, SEPARATION_SPAN = 1024, 64, 64
 PCA_PIECE, TRUST_MAX_DIM = 4096, 512
 FOLD_INIT_MEAN, FOLD_INIT_RANDOM, FOLD_INIT_GIVEN = 0, 1, 2
 TSNE_PIECE, TSNE_SPAN = 64, 16
+LOUVAIN_PHASES, AGREEMENT_MAX_CELLS, AGREEMENT_PIECE = 8, 1 << 26, 1024
 
 u32p = C.POINTER(C.c_uint32)
 f32p = C.POINTER(C.c_float)
@@ -78,6 +79,21 @@ class LinkInfo(C.Structure):  # f2v_link_t
     _fields_ = [("seconds", C.c_double), ("positives", C.c_uint64), ("negatives", C.c_uint64), ("candidates", C.c_uint64), ("capped", C.c_uint64)]
 
 
+class LouvainLevel(C.Structure):  # f2v_louvain_level_t
+    _fields_ = [("nodes", C.c_uint32), ("communities", C.c_uint32), ("sweeps", C.c_uint32), ("reserved", C.c_uint32), ("moves", C.c_uint64),
+                ("qnum", C.c_int64)]
+
+
+class LouvainInfo(C.Structure):  # f2v_louvain_t
+    _fields_ = [("modularity", C.c_double), ("seconds", C.c_double), ("edges", C.c_uint64), ("communities", C.c_uint32), ("levels", C.c_uint32)]
+
+
+class AgreementInfo(C.Structure):  # f2v_agreement_t
+    _fields_ = [("nmi", C.c_double), ("ari", C.c_double), ("mi", C.c_double), ("entropy_a", C.c_double), ("entropy_b", C.c_double),
+                ("seconds", C.c_double), ("n", C.c_uint64), ("sum_comb", C.c_uint64), ("sum_a", C.c_uint64), ("sum_b", C.c_uint64),
+                ("total", C.c_uint64), ("rows", C.c_uint32), ("cols", C.c_uint32)]
+
+
 # every entry point declared in include/f2v.h: name -> (restype, argtypes)
 SIGNATURES = {
     "f2v_last_error": (C.c_char_p, []),
@@ -129,6 +145,8 @@ SIGNATURES = {
     "f2v_tsne_kl_log": (C.c_int, [C.c_void_p, u32p, f64p, C.c_uint32, u32p]),
     "f2v_fold_in": (C.c_int, [C.c_void_p, C.c_int, u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_int, f32p, C.c_uint64, C.c_uint64, f32p, C.POINTER(FoldInfo)]),
     "f2v_link_pairs": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, u32p, u32p, u8p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(LinkInfo)]),
+    "f2v_louvain": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, u32p, u32p, C.POINTER(LouvainLevel), C.POINTER(LouvainInfo)]),
+    "f2v_partition_agreement": (C.c_int, [C.c_void_p, u32p, C.c_uint32, u32p, C.c_uint32, C.POINTER(AgreementInfo)]),
     "f2v_push_export": (C.c_int, [C.c_void_p, C.c_void_p]),
     "f2v_push_attach": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "f2v_push_selftest": (C.c_int, [C.c_void_p]),

@@ -190,6 +190,50 @@ class algorithms {
         printf("Clusters:%u :MODULARITY: %.17g :INERTIA: %.17g :ITERATIONS: %u :RESTART: %u\n", k, q, info.inertia, info.iterations, info.restart);
     }
 
+    // -communities 1: the communities of the graph itself (f2v_louvain; at most `levels` levels, seeded by `seed`) as "<embd output
+    // name>.com", one line "v label" per vertex (0-based ids, the format of .clu), then the reference's "Modularity: <algo> = <q>" line
+    // (performancescores/runvisualization.py:152).  Beside -cluster the agreement of the k-means clusters with the communities, and
+    // beside a single-label ground truth (`truth`: a labels file as -separation reads it, or empty) its agreement with them.
+    // "Agreement(<what>, louvain): NMI <x> ARI <y>", or that it was skipped where the contingency table would pass the cap
+    void printAgreement(const char *what, const std::vector<uint32_t> &a, uint32_t ka, const std::vector<uint32_t> &b, uint32_t kb) {
+        if ((uint64_t)ka * kb > F2V_AGREEMENT_MAX_CELLS) {
+            printf("Agreement(%s, louvain): skipped, %u x %u cells are more than %u\n", what, ka, kb, F2V_AGREEMENT_MAX_CELLS);
+            return;
+        }
+        f2v_agreement_t ag{};
+        check(f2v_partition_agreement(h, a.data(), ka, b.data(), kb, &ag));
+        printf("Agreement(%s, louvain): NMI %.17g ARI %.17g\n", what, ag.nmi, ag.ari);
+    }
+    void writeCommunities(uint32_t levels, uint64_t seed, const std::string &truth) {
+        std::vector<uint32_t> labels(rows, 0);
+        f2v_louvain_t info{};
+        check(f2v_louvain(h, seed, levels, 64, labels.data(), nullptr, nullptr, &info));
+        const std::string name = last_output + ".com";
+        FILE *f = fopen(name.c_str(), "w");
+        if (!f) throw std::runtime_error("cannot write " + name);
+        for (uint32_t v = 0; v < rows; v++) fprintf(f, "%u %u\n", v, labels[v]);
+        if (fclose(f) != 0) throw std::runtime_error("cannot write " + name);
+        printf("Modularity: Louvain = %.17g Communities: %u Levels: %u\n", info.modularity, info.communities, info.levels);
+        const uint32_t K = std::max(info.communities, 1u);
+        if (!cluster_labels.empty()) {
+            uint32_t k = 0;
+            for (uint32_t l : cluster_labels) k = std::max(k, l + 1);
+            printAgreement("kmeans", cluster_labels, k, labels, K);
+        }
+        if (!truth.empty()) {
+            std::vector<bool> seen;
+            const std::vector<std::vector<uint32_t>> all = readLabels(truth, F2V_SEPARATION_MAX_CLUSTERS, "-communities", seen);
+            std::vector<uint32_t> given(rows, F2V_LABEL_NONE);
+            uint32_t k = 1;
+            for (uint32_t v = 0; v < rows; v++)
+                if (!all[v].empty()) {
+                    given[v] = all[v][0];
+                    k = std::max(k, given[v] + 1);
+                }
+            printAgreement("labels", given, k, labels, K);
+        }
+    }
+
     // -classify <labels file>: node classification as the reference scores it (performancescores/runnodeclassclust.py).  The file holds
     // lines "vertex label" with 1-based vertex ids; a vertex may have several lines; labels are 0 .. C - 1, C <= 64.  For split
     // s = 0 .. splits - 1 the labelled vertices are ordered by key(v) = mix64(mix64(seed + s) ^ v) ascending (mix64: the splitmix64

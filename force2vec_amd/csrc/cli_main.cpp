@@ -17,7 +17,9 @@
 // "<embd output name>.lay" and its trustworthiness and continuity), -foldin <file> [-foldin-iters <n>] [-foldin-init mean|random] (after
 // training, or on -init <file> with -iter 0: vectors for new vertices, one "<name> <nbr> <nbr> ..." line each, as "<embd output name>.fold"),
 // -linkpredict <hadamard|l1|l2|average> [-linkpredict-frac <f>] [-linkpredict-ratio <r>] (after training, or on -init <file> with -iter 0:
-// the reference's link-prediction scores of the embedding on the pair set f2v_link_pairs builds from the graph).
+// the reference's link-prediction scores of the embedding on the pair set f2v_link_pairs builds from the graph),
+// -communities 1 [-communities-levels <L>] [-communities-seed <s>] (after training, or on -init <file> with -iter 0: the communities of the
+// graph itself as "<embd output name>.com", their modularity, and their agreement with the -cluster clusters and the ground truth).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -44,6 +46,7 @@ struct Settings {
     double layout_perplexity = 30.0;
     long foldin_iters = 300;
     std::string linkpredict;
+    long communities = 0, communities_levels = 32, communities_seed = 1;
     long linkpredict_ratio = 2;
     double linkpredict_frac = 0.5;
     long classify_splits = 10, separation_sample = 0, layout = 0, layout_neighbours = 5, layout_sample = 0;
@@ -130,6 +133,9 @@ int main(int argc, char *argv[]) {
         {"-foldin-iters", Kind::Integer, &s.foldin_iters, "<int>, epochs of a -foldin vertex. (default:300)"},
         {"-foldin-init", Kind::Text, &s.foldin_init, "<string>, initial vector of a -foldin vertex: mean (of its neighbours' vectors) | random. Under the sigmoid options (6, 9) a random start moves slowly: keep mean. (default:mean)"},
         {"-linkpredict", Kind::Text, &s.linkpredict, "<string>, hadamard | l1 | l2 | average: after training -- or on -init <file> with -iter 0 -- score link prediction as the reference does: the pair set (every edge once, -linkpredict-ratio times as many non-neighbours per vertex, shuffled by -seed) is built on the GPU, a logistic regression on that pair feature is fitted on its first part and predicts the rest; prints \"Link predictions(<Feature>): <frac> :Accuracy: <a> F1-macro: <m> F1-micro: <i>\", fractions of 1 (one GPU)."},
+        {"-communities", Kind::Integer, &s.communities, "<int>, 1: after training (or on -init <file> with -iter 0) find the communities of the graph itself with the Louvain method on the GPU (integers only: the same result on every run), write <output file>.com, one line per vertex \"v label\" (0-based), and print \"Modularity: Louvain = <Q> Communities: <K> Levels: <L>\"; with -cluster also \"Agreement(kmeans, louvain): NMI <x> ARI <y>\", with -classify <labels> or -separation <labels file> also \"Agreement(labels, louvain): ...\" (a vertex's first label counts; one GPU; the graph must be symmetric). (default:0)"},
+        {"-communities-levels", Kind::Integer, &s.communities_levels, "<int>, 1..65535: most levels of a -communities run. (default:32)"},
+        {"-communities-seed", Kind::Integer, &s.communities_seed, "<int>, non-negative: the seed of the -communities sub-round classes. (default:1)"},
         {"-linkpredict-frac", Kind::Real, &s.linkpredict_frac, "<float>, above 0 and below 1: the share of the pair set that trains the -linkpredict model. (default:0.5)"},
         {"-linkpredict-ratio", Kind::Integer, &s.linkpredict_ratio, "<int>, 1..16: negatives per positive of a vertex in the -linkpredict pair set. (default:2)"},
         {"-metric", Kind::Text, &s.metric, "<string>, similarity of -nearest: dot | l2 | cos. (default: l2 for options 5, 8, 11, dot for the sigmoid options)"},
@@ -301,6 +307,22 @@ int main(int argc, char *argv[]) {
         printf("-linkpredict-ratio must be 1..16.\n");
         return 1;
     }
+    if (s.communities < 0 || s.communities > 1) {
+        printf("-communities must be 0 or 1.\n");
+        return 1;
+    }
+    if (s.communities && (s.communities_levels < 1 || s.communities_levels > 65535)) {
+        printf("-communities-levels must be 1..65535.\n");
+        return 1;
+    }
+    if (s.communities && s.communities_seed < 0) {
+        printf("-communities-seed must be a non-negative number.\n");
+        return 1;
+    }
+    if (s.communities && s.gpus > 1) {
+        printf("-communities is not available with -gpus > 1 (it runs on one GPU's copy of the graph).\n");
+        return 1;
+    }
     std::vector<VALUETYPE> seconds;
     int rank = 0;
     std::string meet;  // directory the ranks of a -gpus run meet in
@@ -353,6 +375,9 @@ int main(int argc, char *argv[]) {
                 algo.layout((uint32_t)s.layout, (uint32_t)s.layout_neighbours, (uint32_t)s.layout_sample, (uint64_t)s.seed, tsne, s.layout_perplexity, (uint32_t)s.layout_iters);
             if (!s.foldin.empty() && rank == 0) algo.foldIn(s.foldin, (int)s.option, (uint32_t)s.foldin_iters, (INDEXTYPE)s.nsamples, (VALUETYPE)s.lr, foldin_init, (uint64_t)s.seed);
             if (!s.linkpredict.empty() && rank == 0) algo.linkPredict(linkpredict_feature, s.linkpredict_frac, (uint32_t)s.linkpredict_ratio, (uint64_t)s.seed);
+            if (s.communities && rank == 0)
+                algo.writeCommunities((uint32_t)s.communities_levels, (uint64_t)s.communities_seed,
+                                      !s.separation.empty() && s.separation != "kmeans" ? s.separation : s.classify);
             const double t = algo.gpu_train_seconds;
             if (rank == 0 && s.gpus == 1)
                 printf("GPU epoch loop: %.6f s, %.4g nnz/s, %.1f GB/s algorithmic\n", t, t > 0 ? algo.stats.nnz / t : 0.0,

@@ -40,6 +40,7 @@
 #include "f2v_exact.hip.h"
 #include "f2v_foldin.hip.h"
 #include "f2v_linkpairs.hip.h"
+#include "f2v_louvain.hip.h"
 #include "f2v_tsne.hip.h"
 
 using namespace f2v;
@@ -294,6 +295,19 @@ struct f2v_ctx {
         DevTimer timer;
         uint32_t short_max = 256;
     } link;
+    // communities (f2v_louvain, f2v_partition_agreement): the workspace f2v.h states, allocated on first use and grown for a larger call;
+    // "louvain_short_max": the longest row of a unit that 16 lanes gather, "louvain_lds_slots": the largest table kept in LDS --
+    // placement only.  rows_symmetric: -1 not checked yet (checked once per handle, on the device)
+    struct Louvain {
+        DevBuf<uint32_t> d_k[2], d_loop[2], d_rowbeg[2], d_rowend[2], d_cols[2], d_wts[2];  // a level's graph: level l in set l & 1
+        DevBuf<uint32_t> d_c, d_next, d_tot, d_size, d_kept, d_newid, d_ccount, d_members, d_units, d_table, d_vlabel, d_tile, d_flag;
+        DevBuf<uint32_t> d_a, d_b, d_cells;
+        DevBuf<unsigned long long> d_table_at, d_sums, d_bins;
+        DevBuf<double> d_pieces;
+        DevTimer timer;
+        uint32_t short_max = 32, lds_slots = 4096;
+        int rows_symmetric = -1;
+    } lv;
     // t-SNE layout (f2v_tsne_affinities, f2v_tsne): the workspace f2v.h states, allocated on first use and grown for a larger call;
     // "tsne_rows" (0 = automatic | 64 | 128 | 256): rows per workgroup of tsne_pair_kernel, "tsne_slices" (0 = automatic): spans per
     // workgroup of it -- placement only
@@ -2300,6 +2314,10 @@ const Param kParams[] = {
     {"fold_resident", F2V_FIELD(fold.resident), kValue, kKeep, in<-1, 0>, "fold_resident must be -1 (automatic) or 0: the resident form measured slower and is not part of this build"},
     // f2v_link_pairs: a vertex with at most this many negatives is one wavefront's (its accepted set a list in LDS), a longer one a workgroup's (a table); placement only
     {"link_short_max", F2V_FIELD(link.short_max), kValue, kKeep, in<0, kLinkShortLimit>, "link_short_max must be 0..1024"},
+    // f2v_louvain: a unit whose rows hold at most this many nonzeros is gathered by 16 lanes (table in LDS), a longer one by a workgroup; placement only
+    {"louvain_short_max", F2V_FIELD(lv.short_max), kValue, kKeep, in<0, kLouvainShortLimit>, "louvain_short_max must be 0..256"},
+    // f2v_louvain: the largest table (slots) a workgroup keeps in LDS; a longer one lies in the workspace; placement only
+    {"louvain_lds_slots", F2V_FIELD(lv.lds_slots), kValue, kKeep, in<0, kLouvainLdsLimit>, "louvain_lds_slots must be 0..8192"},
     {"push_fused", F2V_FIELD(push.fused), kFlag},
     {"push_timeout_ms", F2V_FIELD(push.timeout_ms), kValue, kKeep, in<1, 600000>, "push_timeout_ms must be 1..600000"},
     // takes effect at the next f2v_push_export; read: what the exchange in place runs with
@@ -4547,6 +4565,360 @@ int f2v_link_pairs(f2v_handle c, uint32_t ratio, uint64_t seed, uint32_t *u_out,
         info->seconds = seconds;
         info->candidates = sums[3];
     }
+    return F2V_OK;
+}
+
+}  // extern "C"
+
+// ---- communities and the agreement of two labellings (f2v_louvain.hip.h; definition in include/f2v.h) ---------------------------
+namespace {
+
+constexpr const char *kLouvainWhat = "communities";
+
+inline dim3 louvain_grid(uint64_t threads) { return dim3((unsigned)std::max<uint64_t>(1, (threads + 255) / 256)); }
+
+// Is every nonzero (u, v), u != v, matched by (v, u)?  Checked once per handle, on the device (rows ascending: rows_ascending first).
+int rows_symmetric(f2v_ctx *c, bool *yes) {
+    f2v_ctx::Louvain &w = c->lv;
+    if (w.rows_symmetric < 0) {
+        F2VC(w.d_flag.reserve(c, 1, kLouvainWhat));
+        HIPC(hipMemsetAsync(w.d_flag, 0, sizeof(uint32_t), c->stream));
+        hipLaunchKernelGGL(louvain_symmetry_kernel, dim3(std::max(1u, std::min((c->n + 15) / 16, 16384u))), dim3(256), 0, c->stream, c->d_rowptr, c->d_colids, c->n,
+                           (uint32_t *)w.d_flag);
+        HIPC(hipGetLastError());
+        uint32_t bad = 0;
+        HIPC(hipMemcpyAsync(&bad, w.d_flag, sizeof bad, hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+        w.rows_symmetric = bad ? 0 : 1;
+    }
+    *yes = w.rows_symmetric == 1;
+    return F2V_OK;
+}
+
+// exclusive prefix sums of x[0 .. count) in place, the total to x[count]
+int louvain_scan(f2v_ctx *c, uint32_t *x, uint64_t count) {
+    f2v_ctx::Louvain &w = c->lv;
+    const uint32_t tiles = (uint32_t)std::max<uint64_t>(1, (count + kLouvainScanTile - 1) / kLouvainScanTile);
+    F2VC(w.d_tile.reserve(c, tiles, kLouvainWhat));
+    hipLaunchKernelGGL(louvain_scan_tile_kernel, dim3(tiles), dim3(256), 0, c->stream, (const uint32_t *)x, count, (uint32_t *)w.d_tile);
+    hipLaunchKernelGGL(louvain_scan_top_kernel, dim3(1), dim3(256), 0, c->stream, (uint32_t *)w.d_tile, tiles, x + count);
+    hipLaunchKernelGGL(louvain_scan_apply_kernel, dim3(tiles), dim3(256), 0, c->stream, x, count, (const uint32_t *)w.d_tile);
+    HIPC(hipGetLastError());
+    return F2V_OK;
+}
+
+// The lists of `count` units by (class, form): counted, read back (32 words), filled.  cnt[0..23]: units per list, a.start: their places.
+int louvain_place(f2v_ctx *c, LouvainArgs &a, uint32_t count, bool agg, unsigned long long cnt[32]) {
+    f2v_ctx::Louvain &w = c->lv;
+    HIPC(hipMemsetAsync(w.d_bins, 0, 64 * sizeof(unsigned long long), c->stream));
+    a.count = count;
+    a.agg = agg ? 1u : 0u;
+    a.bins = w.d_bins;
+    hipLaunchKernelGGL(louvain_bin_kernel<false>, louvain_grid(count), dim3(256), 0, c->stream, a);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(cnt, w.d_bins, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    uint64_t units = 0, words = 0;
+    for (uint32_t b = 0; b < kLouvainBins; b++) {
+        a.start[b] = (uint32_t)units;
+        units += cnt[b];
+    }
+    for (uint32_t p = 0; p < F2V_LOUVAIN_PHASES; p++) words = std::max<uint64_t>(words, cnt[kLouvainBins + p]);  // sub-rounds follow one another: one table space
+    F2VC(w.d_units.reserve(c, units, kLouvainWhat));
+    F2VC(w.d_table_at.reserve(c, units, kLouvainWhat));
+    F2VC(w.d_table.reserve(c, words, kLouvainWhat));
+    a.units = w.d_units;
+    a.table_at = w.d_table_at;
+    a.table = w.d_table;
+    if (units) hipLaunchKernelGGL(louvain_bin_kernel<true>, louvain_grid(count), dim3(256), 0, c->stream, a);
+    HIPC(hipGetLastError());
+    return F2V_OK;
+}
+
+// the three forms of class `cls`
+template <bool AGG>
+int louvain_gather(f2v_ctx *c, LouvainArgs a, const unsigned long long *cnt, uint32_t cls) {
+    f2v_ctx::Louvain &w = c->lv;
+    for (uint32_t form = 0; form < 3; form++) {
+        const uint32_t bin = cls * 3 + form;
+        if (!cnt[bin]) continue;
+        a.units = w.d_units + a.start[bin];
+        a.table_at = w.d_table_at + a.start[bin];
+        a.count = (uint32_t)cnt[bin];
+        if (form == 0) {
+            a.slots = louvain_slots(a.short_max);
+            const size_t lds = (kLouvainHeader + 32 * (size_t)a.slots) * sizeof(uint32_t);
+            F2VC(allow_lds(c, reinterpret_cast<const void *>(&louvain_gather_kernel<0, AGG>), lds));
+            hipLaunchKernelGGL((louvain_gather_kernel<0, AGG>), dim3(std::min((a.count + 15) / 16, 16384u)), dim3(256), lds, c->stream, a);
+        } else if (form == 1) {
+            const size_t lds = (kLouvainHeader + 2 * (size_t)a.lds_slots) * sizeof(uint32_t);
+            F2VC(allow_lds(c, reinterpret_cast<const void *>(&louvain_gather_kernel<1, AGG>), lds));
+            hipLaunchKernelGGL((louvain_gather_kernel<1, AGG>), dim3(std::min(a.count, 65536u)), dim3(256), lds, c->stream, a);
+        } else {
+            hipLaunchKernelGGL((louvain_gather_kernel<2, AGG>), dim3(std::min(a.count, 65536u)), dim3(kLouvainWideThreads), kLouvainHeader * sizeof(uint32_t), c->stream, a);
+        }
+    }
+    HIPC(hipGetLastError());
+    return F2V_OK;
+}
+
+// Qnum of the labelling c: the two sums, then in2 * 2m - sum tot^2
+int louvain_qnum(f2v_ctx *c, const LouvainArgs &a, const unsigned long long *cnt, unsigned long long sums[3]) {
+    hipLaunchKernelGGL(louvain_qnum_kernel, dim3(std::max(1u, std::min((a.N + 15) / 16, 16384u))), dim3(256), 0, c->stream, a);
+    for (uint32_t p = 0; p < F2V_LOUVAIN_PHASES; p++) {  // the rows it leaves out: the third list of every class
+        if (!cnt[3 * p + 2]) continue;
+        LouvainArgs wide = a;
+        wide.units = c->lv.d_units + a.start[3 * p + 2];
+        wide.count = (uint32_t)cnt[3 * p + 2];
+        hipLaunchKernelGGL(louvain_qnum_wide_kernel, dim3(std::min(wide.count, 65536u)), dim3(256), 0, c->stream, wide);
+    }
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(sums, a.sums, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    return F2V_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int f2v_louvain(f2v_handle c, uint64_t seed, uint32_t max_levels, uint32_t max_sweeps, uint32_t *labels_out, uint32_t *level_labels_out,
+                f2v_louvain_level_t *levels_out, f2v_louvain_t *info_out) {
+    if (!c || !labels_out || !info_out) return fail(F2V_EINVAL, "f2v_louvain: null argument");
+    if (max_levels == 0 || max_sweeps == 0) return fail(F2V_EINVAL, "f2v_louvain: max_levels and max_sweeps must be at least 1");
+    HIPC(hipSetDevice(c->device));
+    if (!rows_ascending(c)) return fail(F2V_EINVAL, "f2v_louvain: the CSR's column ids are not ascending inside every row (needed to search a row)");
+    bool symmetric = false;
+    F2VC(rows_symmetric(c, &symmetric));
+    if (!symmetric) return fail(F2V_EINVAL, "f2v_louvain: the CSR is not structurally symmetric: a nonzero (u, v) without (v, u)");
+    *info_out = f2v_louvain_t{};
+    const uint32_t n = c->n;
+    if (n == 0) return F2V_OK;
+
+    f2v_ctx::Louvain &w = c->lv;
+    const char *what = kLouvainWhat;
+    F2VC(w.d_k[0].reserve(c, n, what));
+    F2VC(w.d_loop[0].reserve(c, n, what));
+    F2VC(w.d_c.reserve(c, n, what));
+    F2VC(w.d_next.reserve(c, n, what));
+    F2VC(w.d_tot.reserve(c, n, what));
+    F2VC(w.d_size.reserve(c, n, what));
+    F2VC(w.d_kept.reserve(c, n, what));
+    F2VC(w.d_newid.reserve(c, (size_t)n + 1, what));
+    F2VC(w.d_ccount.reserve(c, (size_t)n + 1, what));
+    F2VC(w.d_members.reserve(c, n, what));
+    F2VC(w.d_vlabel.reserve(c, n, what));
+    F2VC(w.d_sums.reserve(c, 8, what));
+    F2VC(w.d_bins.reserve(c, 64, what));
+    HIPC(hipMemsetAsync(w.d_sums, 0, 8 * sizeof(unsigned long long), c->stream));
+    F2VC(w.timer.start(c->stream));
+    const dim3 rows16(std::max(1u, std::min((n + 15) / 16, 16384u)));
+    hipLaunchKernelGGL(louvain_degree_kernel, rows16, dim3(256), 0, c->stream, c->d_rowptr, c->d_colids, n, (uint32_t *)w.d_k[0], (uint32_t *)w.d_loop[0],
+                       (unsigned long long *)w.d_sums);
+    hipLaunchKernelGGL(louvain_iota_kernel, louvain_grid(n), dim3(256), 0, c->stream, (uint32_t *)w.d_vlabel, n);
+    HIPC(hipGetLastError());
+    unsigned long long two_m = 0;
+    HIPC(hipMemcpyAsync(&two_m, w.d_sums + 3, sizeof two_m, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    if (two_m >= (1ull << 31)) {
+        F2VC(w.timer.stop(c->stream));
+        return fail(F2V_EINVAL, "f2v_louvain: the degrees sum to %llu, not below 2^31", two_m);
+    }
+
+    LouvainArgs a{};
+    a.rowbeg = c->d_rowptr;
+    a.rowend = c->d_rowptr + 1;
+    a.cols = c->d_colids;
+    a.wts = nullptr;
+    a.dedupe = 1;
+    a.N = a.n = n;
+    a.two_m = (uint32_t)two_m;
+    a.c = w.d_c;
+    a.next = w.d_next;
+    a.tot = w.d_tot;
+    a.size = w.d_size;
+    a.kept = w.d_kept;
+    a.vlabel = w.d_vlabel;
+    a.sums = w.d_sums;
+    a.short_max = w.short_max;
+    a.lds_slots = w.lds_slots;
+    uint32_t levels = 0, communities = n;
+    for (uint32_t level = 0; level < max_levels; level++) {
+        const uint32_t set = level & 1u, out = set ^ 1u, N = a.N;
+        a.k = w.d_k[set];
+        a.loop = w.d_loop[set];
+        a.key = a.c;
+        a.level_mix = mix64_host(seed + level);
+        hipLaunchKernelGGL(louvain_init_kernel, louvain_grid(N), dim3(256), 0, c->stream, a);
+        unsigned long long cnt[32], sums[3];
+        F2VC(louvain_place(c, a, N, false, cnt));
+        HIPC(hipMemsetAsync(w.d_sums, 0, 3 * sizeof(unsigned long long), c->stream));
+        F2VC(louvain_qnum(c, a, cnt, sums));
+        const int64_t start = (int64_t)(sums[1] * two_m) - (int64_t)sums[2];
+        int64_t best = start;
+        uint32_t sweeps = 0;
+        uint64_t moves = 0;
+        while (sweeps < max_sweeps) {
+            HIPC(hipMemsetAsync(w.d_sums, 0, 3 * sizeof(unsigned long long), c->stream));
+            for (uint32_t p = 0; p < F2V_LOUVAIN_PHASES; p++) {
+                if (cnt[3 * p] + cnt[3 * p + 1] + cnt[3 * p + 2] == 0) continue;
+                F2VC(louvain_gather<false>(c, a, cnt, p));
+                hipLaunchKernelGGL(louvain_apply_kernel, louvain_grid(N), dim3(256), 0, c->stream, a);
+            }
+            F2VC(louvain_qnum(c, a, cnt, sums));
+            sweeps++;
+            moves += sums[0];
+            const int64_t q = (int64_t)(sums[1] * two_m) - (int64_t)sums[2];
+            if (q <= best) break;
+            best = q;
+            HIPC(hipMemcpyAsync(w.d_kept, w.d_c, (size_t)N * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+        }
+
+        // aggregation: the kept communities renumbered in ascending id, the members grouped, the coarse rows gathered
+        uint32_t K = N;
+        if (best != start) {
+            HIPC(hipMemsetAsync(w.d_newid, 0, ((size_t)N + 1) * sizeof(uint32_t), c->stream));
+            a.newid = w.d_newid;
+            hipLaunchKernelGGL(louvain_flag_kernel, louvain_grid(N), dim3(256), 0, c->stream, a);
+            F2VC(louvain_scan(c, w.d_newid, N));
+            HIPC(hipMemcpyAsync(&K, w.d_newid + N, sizeof K, hipMemcpyDeviceToHost, c->stream));
+            HIPC(hipStreamSynchronize(c->stream));
+            F2VC(w.d_rowbeg[out].reserve(c, (size_t)K + 1, what));
+            F2VC(w.d_rowend[out].reserve(c, K, what));
+            F2VC(w.d_k[out].reserve(c, K, what));
+            F2VC(w.d_loop[out].reserve(c, K, what));
+            HIPC(hipMemsetAsync(w.d_rowbeg[out], 0, ((size_t)K + 1) * sizeof(uint32_t), c->stream));
+            HIPC(hipMemsetAsync(w.d_k[out], 0, (size_t)K * sizeof(uint32_t), c->stream));
+            HIPC(hipMemsetAsync(w.d_loop[out], 0, (size_t)K * sizeof(uint32_t), c->stream));
+            HIPC(hipMemsetAsync(w.d_ccount, 0, ((size_t)K + 1) * sizeof(uint32_t), c->stream));
+            HIPC(hipMemsetAsync(w.d_size, 0, (size_t)K * sizeof(uint32_t), c->stream));  // (the cursors of louvain_member_fill_kernel)
+            a.orowbeg = w.d_rowbeg[out];
+            a.orowend = w.d_rowend[out];
+            a.ok = w.d_k[out];
+            a.oloop = w.d_loop[out];
+            a.ccount = w.d_ccount;
+            a.mstart = w.d_ccount;
+            a.members = w.d_members;
+            hipLaunchKernelGGL(louvain_member_count_kernel, louvain_grid(N), dim3(256), 0, c->stream, a);
+            F2VC(louvain_scan(c, w.d_ccount, K));
+            F2VC(louvain_scan(c, w.d_rowbeg[out], K));
+            uint32_t nnz_out = 0;
+            HIPC(hipMemcpyAsync(&nnz_out, w.d_rowbeg[out] + K, sizeof nnz_out, hipMemcpyDeviceToHost, c->stream));
+            HIPC(hipStreamSynchronize(c->stream));
+            F2VC(w.d_cols[out].reserve(c, nnz_out, what));
+            F2VC(w.d_wts[out].reserve(c, nnz_out, what));
+            a.ocols = w.d_cols[out];
+            a.owts = w.d_wts[out];
+            hipLaunchKernelGGL(louvain_member_fill_kernel, louvain_grid(N), dim3(256), 0, c->stream, a);
+            hipLaunchKernelGGL(louvain_relabel_kernel, louvain_grid(n), dim3(256), 0, c->stream, a);
+            a.K = K;
+            F2VC(louvain_place(c, a, K, true, cnt));
+            a.key = a.next;
+            F2VC(louvain_gather<true>(c, a, cnt, 0));
+            a.rowbeg = w.d_rowbeg[out];
+            a.rowend = w.d_rowend[out];
+            a.cols = w.d_cols[out];
+            a.wts = w.d_wts[out];
+            a.dedupe = 0;
+            a.N = K;
+        }
+        HIPC(hipGetLastError());
+        if (level_labels_out)
+            HIPC(hipMemcpyAsync(level_labels_out + (size_t)level * n, w.d_vlabel, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (levels_out) levels_out[level] = f2v_louvain_level_t{N, K, sweeps, 0u, moves, best};
+        levels = level + 1;
+        communities = K;
+        if (best == start) break;  // an identity level: nothing left to merge
+    }
+    F2VC(w.timer.stop(c->stream));
+    HIPC(hipMemcpyAsync(labels_out, w.d_vlabel, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    F2VC(w.timer.seconds(&info_out->seconds));
+    info_out->communities = communities;
+    info_out->levels = levels;
+    info_out->edges = two_m / 2;
+    uint64_t edges = 0;
+    F2VC(f2v_modularity(c, labels_out, communities, &info_out->modularity, &edges, nullptr, nullptr));
+    return F2V_OK;
+}
+
+int f2v_partition_agreement(f2v_handle c, const uint32_t *la, uint32_t ka, const uint32_t *lb, uint32_t kb, f2v_agreement_t *out) {
+    if (!c || !la || !lb || !out) return fail(F2V_EINVAL, "f2v_partition_agreement: null argument");
+    if (ka == 0 || kb == 0) return fail(F2V_EINVAL, "f2v_partition_agreement: ka and kb must be at least 1");
+    const uint64_t cells = (uint64_t)ka * kb;
+    if (cells > F2V_AGREEMENT_MAX_CELLS) return fail(F2V_EINVAL, "f2v_partition_agreement: ka * kb = %llu cells are more than %u", (unsigned long long)cells, F2V_AGREEMENT_MAX_CELLS);
+    const uint32_t n = c->n;
+    uint64_t both = 0;
+    for (uint32_t v = 0; v < n; v++) {
+        if (la[v] != F2V_LABEL_NONE && la[v] >= ka) return fail(F2V_EINVAL, "f2v_partition_agreement: a[%u] = %u is not below ka = %u", v, la[v], ka);
+        if (lb[v] != F2V_LABEL_NONE && lb[v] >= kb) return fail(F2V_EINVAL, "f2v_partition_agreement: b[%u] = %u is not below kb = %u", v, lb[v], kb);
+        both += la[v] != F2V_LABEL_NONE && lb[v] != F2V_LABEL_NONE;
+    }
+    if (both < 2) return fail(F2V_EINVAL, "f2v_partition_agreement: %llu vertices are labelled in both, fewer than 2", (unsigned long long)both);
+    HIPC(hipSetDevice(c->device));
+    f2v_ctx::Louvain &w = c->lv;
+    const char *what = kLouvainWhat;
+    const uint64_t words = cells + ka + kb;
+    const uint64_t pc = (cells + kAgreePiece - 1) / kAgreePiece, pa = ((uint64_t)ka + kAgreePiece - 1) / kAgreePiece, pb = ((uint64_t)kb + kAgreePiece - 1) / kAgreePiece;
+    const uint64_t pieces = pc + pa + pb;
+    F2VC(w.d_a.reserve(c, n, what));
+    F2VC(w.d_b.reserve(c, n, what));
+    F2VC(w.d_cells.reserve(c, words, what));
+    F2VC(w.d_sums.reserve(c, 8, what));
+    F2VC(w.d_pieces.reserve(c, pieces + 1, what));
+    HIPC(hipMemcpyAsync(w.d_a, la, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(w.d_b, lb, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemsetAsync(w.d_cells, 0, words * sizeof(uint32_t), c->stream));
+    HIPC(hipMemsetAsync(w.d_sums, 0, 8 * sizeof(unsigned long long), c->stream));
+    AgreeArgs g{};
+    g.a = w.d_a;
+    g.b = w.d_b;
+    g.cells = w.d_cells;
+    g.sums = w.d_sums;
+    g.pieces = w.d_pieces;
+    g.cells_count = cells;
+    g.n = n;
+    g.ka = ka;
+    g.kb = kb;
+    F2VC(w.timer.start(c->stream));
+    hipLaunchKernelGGL(agree_count_kernel, louvain_grid(n), dim3(256), 0, c->stream, g);
+    hipLaunchKernelGGL(agree_piece_kernel, louvain_grid(pc), dim3(256), 0, c->stream, g, 0u, (uint64_t)0, cells, (uint64_t)0);
+    hipLaunchKernelGGL(agree_piece_kernel, louvain_grid(pa), dim3(256), 0, c->stream, g, 1u, cells, (uint64_t)ka, pc);
+    hipLaunchKernelGGL(agree_piece_kernel, louvain_grid(pb), dim3(256), 0, c->stream, g, 2u, cells + ka, (uint64_t)kb, pc + pa);
+    hipLaunchKernelGGL(agree_log_kernel, dim3(1), dim3(1), 0, c->stream, g, pieces);
+    HIPC(hipGetLastError());
+    F2VC(w.timer.stop(c->stream));
+    unsigned long long sums[8];
+    std::vector<double> piece(pieces + 1);
+    HIPC(hipMemcpyAsync(sums, w.d_sums, sizeof sums, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipMemcpyAsync(piece.data(), w.d_pieces, (pieces + 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    *out = f2v_agreement_t{};
+    F2VC(w.timer.seconds(&out->seconds));
+    auto chain = [&](uint64_t lo, uint64_t cnt) {  // the piece sums, added in order from +0
+        double s = 0.0;
+        for (uint64_t p = 0; p < cnt; p++) s = s + piece[lo + p];
+        return s;
+    };
+    const double S_ab = chain(0, pc), S_a = chain(pc, pa), S_b = chain(pc + pa, pb), logN = piece[pieces];
+    const uint64_t N = sums[0];
+    const double Nf = (double)N;
+    out->n = N;
+    out->sum_comb = sums[1];
+    out->sum_a = sums[2];
+    out->sum_b = sums[3];
+    out->total = N * (N - 1) / 2;
+    out->rows = (uint32_t)sums[5];
+    out->cols = (uint32_t)sums[6];
+    // a side with one non-empty class has no entropy and shares no information: decided on the integers, not on a rounded difference
+    out->entropy_a = out->rows == 1 ? 0.0 : logN - S_a / Nf;
+    out->entropy_b = out->cols == 1 ? 0.0 : logN - S_b / Nf;
+    const double mi = (out->rows == 1 || out->cols == 1) ? 0.0 : (S_ab - S_a - S_b) / Nf + logN;
+    out->mi = mi > 0.0 ? mi : 0.0;
+    out->nmi = (out->entropy_a == 0.0 && out->entropy_b == 0.0) ? 1.0 : out->mi / (0.5 * (out->entropy_a + out->entropy_b));
+    const double sc = (double)out->sum_comb, sa = (double)out->sum_a, sb = (double)out->sum_b, tt = (double)out->total;
+    const double den = 0.5 * (sa + sb) - sa * sb / tt;
+    out->ari = den == 0.0 ? 1.0 : (sc - sa * sb / tt) / den;
     return F2V_OK;
 }
 

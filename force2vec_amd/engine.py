@@ -38,6 +38,10 @@ FOLD_INITS = {"mean": _lib.FOLD_INIT_MEAN, "random": _lib.FOLD_INIT_RANDOM}
 
 # Engine.link_pairs (include/f2v.h: link prediction pairs)
 LinkInfo = namedtuple("LinkInfo", "seconds positives negatives candidates capped")
+# Engine.communities, Engine.agreement (include/f2v.h: communities)
+Communities = namedtuple("Communities", "modularity communities levels edges seconds level_records level_labels")
+LouvainLevel = namedtuple("LouvainLevel", "nodes communities sweeps moves qnum")
+Agreement = namedtuple("Agreement", "nmi ari mi entropy_a entropy_b n sum_comb sum_a sum_b total rows cols seconds")
 
 
 # Engine.logreg_fit / Engine.classify / Engine.link_predict (include/f2v.h: logistic regression)
@@ -89,6 +93,7 @@ class Engine:
         self.last_layout_seconds = 0.0  # ... / pca or trustworthiness call
         self.last_fold_seconds = 0.0  # ... / fold_in call
         self.last_link_seconds = 0.0  # ... / link_pairs call (its count and its fill together)
+        self.last_louvain_seconds = 0.0  # ... / communities call
 
     def _ck(self, rc):
         check(rc, self._L)  # the error text lives in the library that returned the code
@@ -607,6 +612,35 @@ class Engine:
             seconds += info.seconds
         self.last_link_seconds = seconds
         return (u, v, y, LinkInfo(seconds, info.positives, info.negatives, info.candidates, info.capped)) if details else (u, v, y)
+
+    # -- communities (include/f2v.h: definition; a function of the CSR, seed, max_levels and max_sweeps alone) --
+    def communities(self, seed=1, max_levels=32, max_sweeps=64, details=False):
+        """The communities of the graph itself (Louvain, in integers: bit-reproducible), on the GPU -> labels uint32[n], or with
+        details=True (labels, Communities(modularity, communities, levels, edges, seconds, level_records, level_labels uint32[levels,
+        n])); level_records: LouvainLevel(nodes, communities, sweeps, moves, qnum) per level.  `modularity` equals
+        `modularity(labels).q`.  Needs no embeddings.  `last_louvain_seconds` keeps the device time."""
+        max_levels, max_sweeps = int(max_levels), int(max_sweeps)
+        if not 0 <= max_levels < 2 ** 16:
+            raise ValueError("communities: max_levels must be below 65536")
+        labels = np.empty(self.n, dtype=np.uint32)
+        per_level = np.empty((max_levels, self.n), dtype=np.uint32) if details else None
+        records, info = (_lib.LouvainLevel * max(max_levels, 1))(), _lib.LouvainInfo()
+        self._ck(self._L.f2v_louvain(self._h, seed, max_levels, max_sweeps, _u32(labels), _u32(per_level) if details else None, records, C.byref(info)))
+        self.last_louvain_seconds = info.seconds
+        if not details:
+            return labels
+        recs = [LouvainLevel(r.nodes, r.communities, r.sweeps, r.moves, r.qnum) for r in records[:info.levels]]
+        return labels, Communities(info.modularity, info.communities, info.levels, info.edges, info.seconds, recs, per_level[:info.levels].copy())
+
+    def agreement(self, a, b):
+        """How far two labellings agree (any integer arrays, one label per vertex; negative = the vertex takes no part), the
+        contingency table counted on the GPU -> Agreement(nmi, ari, mi, entropy_a, entropy_b, n, sum_comb, sum_a, sum_b, total, rows,
+        cols, seconds): normalised mutual information (arithmetic mean of the entropies), adjusted Rand index, and their integers."""
+        (la, ka), (lb, kb) = self._labelling(a), self._labelling(b)
+        info = _lib.AgreementInfo()
+        self._ck(self._L.f2v_partition_agreement(self._h, _u32(la), ka, _u32(lb), kb, C.byref(info)))
+        return Agreement(info.nmi, info.ari, info.mi, info.entropy_a, info.entropy_b, info.n, info.sum_comb, info.sum_a, info.sum_b, info.total,
+                         info.rows, info.cols, info.seconds)
 
     def link_predict(self, u=None, v=None, y=None, train_frac=0.5, feature="hadamard", lam=1.0, tol=1e-4, max_iter=100, ratio=2, seed=1):
         """Link prediction as the reference scores it (performancescores/runlinkpredict.py:127-140): fits on the first

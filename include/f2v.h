@@ -9,8 +9,9 @@
  * Beside training, what the reference judges an embedding by is evaluated on the matrix where it lies, in HBM: the training
  * objective (f2v_objective), nearest rows (f2v_nearest_*), k-means and modularity (f2v_kmeans, f2v_modularity), the
  * logistic-regression scorers of node labels and links (f2v_logreg_*), the separation of a labelling in the embedding space
- * (f2v_silhouette, f2v_davies_bouldin) and a two-dimensional picture of the matrix with the score of how faithful it is (f2v_pca,
- * f2v_trustworthiness).  Each has a definition below that fixes every order of summation, so that its results are
+ * (f2v_silhouette, f2v_davies_bouldin), a two-dimensional picture of the matrix with the score of how faithful it is (f2v_pca,
+ * f2v_trustworthiness), and -- the yardstick for the clusters' modularity -- the communities of the graph itself with the agreement of
+ * two labellings (f2v_louvain, f2v_partition_agreement).  Each has a definition below that fixes every order of summation, so that its results are
  * functions of its inputs alone.
  *
  * Conventions: every function returns 0 on success and a negative F2V_E* code on failure
@@ -846,6 +847,88 @@ typedef struct {
 } f2v_link_t;
 F2V_API int f2v_link_pairs(f2v_handle h, uint32_t ratio, uint64_t seed, uint32_t *u_out, uint32_t *v_out, uint8_t *y_out /* all three NULL: count only */,
                    uint64_t cap, uint64_t *count_out, f2v_link_t *info /* may be NULL */);
+
+/* ---- communities ----------------------------------------------------------------------------------------------------------------
+ * What the graph itself achieves, to hold the modularity of an embedding's clusters against: the reference colours its pictures by
+ * the graph's communities and prints their modularity (performancescores/runvisualization.py:127-152) and sweeps k-means for the best
+ * modularity (runnodeclassclust.py:311-331).  f2v_louvain is the Louvain method in a form that is parallel and exact at once: every
+ * quantity is an integer until the final Q, so the result is a function of (CSR, seed, max_levels, max_sweeps) alone -- never of
+ * launch shapes, tunables, handles, the order in which workgroups or lanes run, or the order in which a coarse row stores its columns.
+ *   graph       the simple undirected graph f2v_modularity uses: a pair u != v that occurs as a nonzero is one edge of weight 1
+ *               (duplicates collapse), a diagonal nonzero is a self-loop: one edge, adding 2 to its vertex's degree.  Rows must be
+ *               ascending (checked once per handle) and the CSR structurally symmetric: every nonzero (u, v), u != v, has (v, u)
+ *               (checked once per handle on the device, by binary search in row v); 2m, the sum of the degrees, must be below 2^31:
+ *               every product below then fits a signed 64-bit integer;
+ *   level       a weighted graph with nodes 0 .. N_l - 1, integer weights w(i, j) = w(j, i) > 0 for i != j, loop(i) the weight of the
+ *               edges inside node i, k(i) = sum_j w(i, j) + 2 loop(i); 2m is the same at every level.  Level 0 is the graph above
+ *               with loop = 1 for a vertex that has a self-loop;
+ *   moving      start with c(i) = i, tot(c) = k(c), size(c) = 1.  class(i) = mix64(mix64(seed + l) ^ i) % F2V_LOUVAIN_PHASES (mix64: the
+ *               splitmix64 finaliser of the objective's section, seed + l wraps in 64 bits, l the level index).  A sweep is 8
+ *               sub-rounds p = 0 .. 7; in sub-round p every node of class p with at least one neighbour j != i decides, all of them
+ *               from the state (c, tot, size) as it was when the sub-round began: a = c(i); for every community d that holds a
+ *               neighbour j != i, e(d) = the sum of w(i, j) over those j (e(a) = 0 if a holds none); tot'(d) = tot(d) - k(i) if d == a,
+ *               else tot(d); score(d) = e(d) * 2m - k(i) * tot'(d) in signed 64-bit; best = the adjacent community of largest score,
+ *               ties to the lowest id (a is adjacent only if it holds a neighbour); i moves to best iff best != a and score(best) >
+ *               score(a) strictly -- except that it stays when size(a) == 1, size(best) == 1 and best > a: two singletons never
+ *               swap.  After the decisions the moves are applied and tot and size updated (integer sums: order-free);
+ *   level end   after every sweep Qnum = sum_c (in2(c) * 2m - tot(c)^2), in2(c) the sum of w(i, j) over the ordered pairs i != j
+ *               inside c plus 2 loop(i) over its members (two sums of at most 2^62, formed separately and subtracted).  start =
+ *               Qnum of the singleton state, best = the largest so far (at first start).  A sweep whose Qnum exceeds best becomes
+ *               best and its labelling is kept, and the next sweep runs unless max_sweeps have run; otherwise the level ends with the
+ *               kept labelling.  A level never lowers Qnum;
+ *   aggregation the kept communities are renumbered 0 .. K - 1 in ascending id; node C of the next level has loop(C) = its members'
+ *               loops + the weights of the edges between its members (each unordered pair once), w(C, D) = the sum of w(i, j) across
+ *               the two; a vertex's label becomes the renumbered community of its node;
+ *   stop        after a level whose best == start (an identity, still applied and recorded), or after max_levels levels.
+ * Results: labels_out[v] in 0 .. communities - 1; level_labels_out[l * n + v] the label of v after level l; one record per level --
+ * nodes, communities, sweeps (those run, the rejected last one included), moves (summed over them), qnum (the level's best); info:
+ * communities, levels, edges (= m), seconds, and modularity = exactly what f2v_modularity returns for labels_out (the same tallies,
+ * the same host formula).  The call needs no embeddings; it runs on the handle's stream and touches neither the matrices nor the
+ * rand() stream nor any later training result.  Defaults everywhere: seed 1, max_levels 32, max_sweeps 64.  F2V_EINVAL: a null handle,
+ * labels_out or info_out, a zero maximum, rows not ascending, an asymmetric CSR, 2m >= 2^31.
+ * Launches: a unit's (a node's when moving, a community's when aggregating) weights to the communities around it are summed in an
+ * open-addressing table of (community, weight) -- integer compare-and-swap on keys, integer adds on weights, a power of two of slots,
+ * at least twice the nonzeros of the unit's rows, every probe loop bounded by the slots.  Units whose rows hold at most
+ * "louvain_short_max" (0..256, default 32) nonzeros take 16 lanes each, sixteen to a workgroup, tables in LDS; longer ones a workgroup
+ * each, the table in LDS up to "louvain_lds_slots" (0..8192, default 4096) slots and in the workspace above.  Decisions go to a
+ * per-node array; a second launch applies them.  Neither tunable changes a bit.  The host reads back 24 bytes per sweep.
+ * Workspace, allocated on first use (grown for a larger call) and freed by f2v_destroy: 4 bytes x 11 per vertex, per level node 8
+ * bytes of placement, two sets of coarse graphs (per node 16 bytes, per nonzero of the finer level 8), 8 bytes per table slot of the
+ * units above "louvain_lds_slots" of one sub-round, 4 bytes per 1024 nodes of the prefix sums, 1 KiB of counters.
+ *
+ * f2v_partition_agreement: how far two labellings agree.  a and b hold n labels each, below ka / kb, or F2V_LABEL_NONE (the vertex
+ * takes no part).  N counts the vertices labelled in both; n_ij is the contingency table with row sums a_i and column sums b_j, counted
+ * on the device with integer atomics; ka * kb <= F2V_AGREEMENT_MAX_CELLS.  Integers: n = N, sum_comb = sum_ij C(n_ij, 2), sum_a =
+ * sum_i C(a_i, 2), sum_b = sum_j C(b_j, 2), total = C(N, 2), rows / cols = the non-empty rows and columns.  Floats, all fp64: S_ab =
+ * the sum of n_ij * flog(n_ij) over the nonzero cells in row-major order, in pieces of 1024 consecutive cells -- each piece summed from
+ * +0 in order, the piece sums added in order from +0 (flog: the logarithm of the option-1 objective) --, S_a and S_b likewise over the
+ * row and column sums; H(A) = flog(N) - S_a / N, H(B) likewise, and exactly 0 for a side with one non-empty class (rows == 1, cols == 1:
+ * decided on the integers, the rounded difference is not 0 for every N); mi = max(0, (S_ab - S_a - S_b) / N + flog(N)), and exactly 0
+ * where either side has one non-empty class; nmi = mi / (0.5 * (H(A) + H(B))), 1 where both entropies are 0; ari = (sum_comb - sum_a * sum_b / total) / (0.5 * (sum_a + sum_b) - sum_a * sum_b /
+ * total) on the fp64 conversions of the integers, 1 where the denominator is 0.  Bit-reproducible from the inputs.  F2V_EINVAL: null
+ * arguments, ka or kb zero, too many cells, a label that is neither below its bound nor F2V_LABEL_NONE, N < 2.
+ * Workspace: 8 bytes per vertex, 4 per cell, row and column, 8 per 1024 of them. */
+#define F2V_LOUVAIN_PHASES 8
+#define F2V_AGREEMENT_MAX_CELLS (1u << 26)
+typedef struct {
+    uint32_t nodes, communities, sweeps, reserved;
+    uint64_t moves;
+    int64_t qnum;
+} f2v_louvain_level_t;
+typedef struct {
+    double modularity, seconds;
+    uint64_t edges;
+    uint32_t communities, levels;
+} f2v_louvain_t;
+typedef struct {
+    double nmi, ari, mi, entropy_a, entropy_b, seconds;
+    uint64_t n, sum_comb, sum_a, sum_b, total;
+    uint32_t rows, cols;
+} f2v_agreement_t;
+F2V_API int f2v_louvain(f2v_handle h, uint64_t seed, uint32_t max_levels, uint32_t max_sweeps, uint32_t *labels_out /* n */,
+                uint32_t *level_labels_out /* max_levels x n, may be NULL */, f2v_louvain_level_t *levels_out /* max_levels, may be NULL */,
+                f2v_louvain_t *info_out);
+F2V_API int f2v_partition_agreement(f2v_handle h, const uint32_t *a, uint32_t ka, const uint32_t *b, uint32_t kb, f2v_agreement_t *out);
 
 /* ---- host-side I/O of the drop-in boundary (no device needed) ----------------------------
  * f2v_read_mtx replaces SetInputMatricesAsCSR (sample/commonutility.h:44-54 -> ReadASCII
