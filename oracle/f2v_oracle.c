@@ -243,11 +243,15 @@ static const float *current_table(void) {
 
 /* fast_SM, sample/algorithms.cpp:766-770; SM_RESOLUTION is a float constant
  * (algorithms.h:49).  v == 6.0 indexes one past the table in the reference; the
- * restatement clamps that one case to the last entry. */
+ * restatement clamps that one case to the last entry.  A NaN passes both comparisons and its
+ * conversion to int is undefined in C (x86's cvttsd2si gives INT_MIN, which the clamp below
+ * turned into 0; the reference reads far outside its table): stated here as entry 0, which is
+ * also what the device's conversion (NaN -> 0) selects. */
 static inline float fast_sm(const float *table, float v) {
     const float res = (float)(ORC_SM_TABLE_SIZE / (2.0 * ORC_SM_BOUND));
     if (v > (float)ORC_SM_BOUND) return 1.0f;
     if (v < -(float)ORC_SM_BOUND) return 0.0f;
+    if (v != v) return table[0];
     int idx = (int)(((double)v + ORC_SM_BOUND) * (double)res);
     if (idx > ORC_SM_TABLE_SIZE - 1) idx = ORC_SM_TABLE_SIZE - 1;
     if (idx < 0) idx = 0;

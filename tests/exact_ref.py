@@ -121,9 +121,17 @@ def _threads(threads):
     return threads if threads else max(1, min(8, os.cpu_count() or 1))
 
 
-def train(X0, rowptr, colids, batch, epochs, first_epoch=0, order="engine", threads=0, chunk=16):
-    """`epochs` epochs from epoch index `first_epoch` on; returns the new matrix (X0 is left alone)."""
+def train(X0, rowptr, colids, batch, epochs, first_epoch=0, order="engine", threads=0, chunk=16, special_values=False):
+    """`epochs` epochs from epoch index `first_epoch` on; returns the new matrix (X0 is left alone).  special_values: the matrix holds
+    rows of 1e19, inf or NaN on purpose -- inf - inf and overflowing squares are part of the definition then, and numpy's warnings
+    about them are switched off (here, not by the caller: the worker threads have a floating-point error state of their own)."""
     assert order in ("engine", "reference")
+    quiet = dict(over="ignore", invalid="ignore") if special_values else {}
+
+    def update(rows):
+        with np.errstate(**quiet):
+            return _rows_update(X, rowptr, colids, rows, step, order)
+
     X = np.array(X0, dtype=F32, copy=True)
     rowptr = np.asarray(rowptr, dtype=np.int64)
     colids = np.asarray(colids, dtype=np.int64)
@@ -134,8 +142,9 @@ def train(X0, rowptr, colids, batch, epochs, first_epoch=0, order="engine", thre
             for lo in range(0, n, batch):
                 hi = min(lo + batch, n)
                 groups = [np.arange(g, min(g + chunk, hi)) for g in range(lo, hi, chunk)]
-                Y = list(pool.map(lambda rows: _rows_update(X, rowptr, colids, rows, step, order), groups))
-                X[lo:hi] = X[lo:hi] + np.concatenate(Y)  # every read above saw the matrix as it was before the minibatch
+                Y = list(pool.map(update, groups))
+                with np.errstate(**quiet):
+                    X[lo:hi] = X[lo:hi] + np.concatenate(Y)  # every read above saw the matrix as it was before the minibatch
             step = F32(np.float64(step) * 0.999)
     return X
 
