@@ -39,6 +39,7 @@ the same labels on every run; `details=True` adds their modularity, the yardstic
 from . import _lib  # noqa: F401
 from ._lib import F2VError  # noqa: F401
 from ._lib import KMEANS_MAX_K, KMEANS_PIECE  # noqa: F401
+from ._lib import INDEX_MAX_LISTS, INDEX_MAX_PROBES  # noqa: F401
 from ._lib import LABEL_NONE, SEPARATION_MAX_CLUSTERS, SEPARATION_PIECE, SEPARATION_SPAN  # noqa: F401
 from ._lib import PCA_PIECE, TRUST_MAX_DIM, TSNE_PIECE, TSNE_SPAN  # noqa: F401
 from ._lib import FOLD_INIT_GIVEN, FOLD_INIT_MEAN, FOLD_INIT_RANDOM  # noqa: F401

@@ -15,6 +15,7 @@ NEAREST_MAX_K = 128
 NEAREST_EXCLUDE_SELF, NEAREST_EXCLUDE_NEIGHBOURS = 1, 2
 NEAREST_PAD_ID = 0xFFFFFFFF  # id of a slot past the last candidate (its score is -inf)
 KMEANS_MAX_K, KMEANS_PIECE = 1024, 64
+INDEX_MAX_LISTS, INDEX_MAX_PROBES = 1024, 128
 LOGREG_MAX_CLASSES, LOGREG_BLOCK = 64, 1024
 PAIR_HADAMARD, PAIR_L1, PAIR_L2, PAIR_AVERAGE = 0, 1, 2, 3
 LABEL_NONE = 0xFFFFFFFF  # F2V_LABEL_NONE: the vertex takes no part in a separation score
@@ -45,6 +46,15 @@ class Objective(C.Structure):  # f2v_objective_t
 class KMeansInfo(C.Structure):  # f2v_kmeans_t
     _fields_ = [("inertia", C.c_double), ("seconds", C.c_double), ("iterations", C.c_uint32), ("converged", C.c_uint32),
                 ("restart", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class IndexInfo(C.Structure):  # f2v_index_t
+    _fields_ = [("inertia", C.c_double), ("seconds", C.c_double), ("bytes", C.c_uint64), ("lists", C.c_uint32), ("iterations", C.c_uint32),
+                ("converged", C.c_uint32), ("largest", C.c_uint32), ("empty", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class IndexSearchInfo(C.Structure):  # f2v_index_search_t
+    _fields_ = [("seconds", C.c_double), ("candidates", C.c_uint64), ("nprobe", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class LogregInfo(C.Structure):  # f2v_logreg_t
@@ -133,6 +143,12 @@ SIGNATURES = {
     "f2v_neighbour_recall": (C.c_int, [C.c_void_p, u32p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "f2v_kmeans": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, f32p, u32p, f32p, C.POINTER(C.c_uint64), C.POINTER(KMeansInfo)]),
     "f2v_modularity": (C.c_int, [C.c_void_p, u32p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "f2v_index_build": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, f32p, C.POINTER(IndexInfo)]),
+    "f2v_index_build_given": (C.c_int, [C.c_void_p, u32p, f32p, C.c_uint32, C.POINTER(IndexInfo)]),
+    "f2v_index_get": (C.c_int, [C.c_void_p, u32p, f32p, C.POINTER(C.c_uint64), C.POINTER(IndexInfo)]),
+    "f2v_index_drop": (C.c_int, [C.c_void_p]),
+    "f2v_index_search_rows": (C.c_int, [C.c_void_p, u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, u32p, f32p, u32p, C.POINTER(IndexSearchInfo)]),
+    "f2v_index_search_vectors": (C.c_int, [C.c_void_p, f32p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, u32p, f32p, u32p, C.POINTER(IndexSearchInfo)]),
     "f2v_logreg_eval": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32, C.c_int, u8p, C.c_uint32, f64p, C.c_double, f64p, f64p, f64p]),
     "f2v_logreg_fit": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32, C.c_int, u8p, C.c_uint32, C.c_double, C.c_double, C.c_uint32, f64p, C.POINTER(LogregInfo)]),
     "f2v_logreg_decision": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint32, C.c_int, f64p, C.c_uint32, f64p, f64p]),

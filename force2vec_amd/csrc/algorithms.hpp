@@ -136,8 +136,14 @@ class algorithms {
     // -nearest <k>: every vertex's k nearest rows under `metric` (self excluded) as "<embd output name>.nn", one line per vertex
     // "v j1 s1 ... jk sk" (0-based ids, scores %.9g, slots past the last candidate omitted), in query blocks through the same ABI
     // as any other caller's; then the graph-reconstruction precision@k.  Call after a run (last_output names the .embd file).
+    // With `lists` > 0 (-nearest-lists) the sweep goes through an index (f2v_index_*: k-means into `lists` lists, `iters` iterations
+    // from `seed`; `probes` lists per query): an extra line "Index: lists <L> probes <P> candidates/query <c>", and with `check` > 0
+    // (-nearest-check) the recall against the exact search over the vertices floor(i n / check), i < check.
+    static constexpr uint32_t kIndexMaxLists = F2V_INDEX_MAX_LISTS, kIndexMaxProbes = F2V_INDEX_MAX_PROBES;
     std::string last_output;
-    void writeNearest(uint32_t k, int metric, const char *metric_name) {
+    void writeNearest(uint32_t k, int metric, const char *metric_name, uint32_t lists = 0, uint32_t probes = 8, uint32_t iters = 20, uint64_t seed = 1,
+                      uint32_t check_count = 0) {
+        if (lists > 0) check(f2v_index_build(h, lists, iters, seed, nullptr, nullptr));
         const std::string name = last_output + ".nn";
         FILE *f = fopen(name.c_str(), "w");
         if (!f) throw std::runtime_error("cannot write " + name);
@@ -145,13 +151,20 @@ class algorithms {
         std::vector<uint32_t> q(block), ids((size_t)block * k);
         std::vector<float> scores((size_t)block * k);
         double seconds = 0.0, sec = 0.0;
-        uint64_t hits = 0, possible = 0;
+        uint64_t hits = 0, possible = 0, candidates = 0;
+        f2v_index_search_t found{};
         for (uint32_t lo = 0; lo < rows; lo += block) {
             const uint32_t cnt = rows - lo < block ? rows - lo : block;
             for (uint32_t i = 0; i < cnt; i++) q[i] = lo + i;
-            if (f2v_nearest_rows(h, q.data(), cnt, k, metric, F2V_NEAREST_EXCLUDE_SELF, ids.data(), scores.data(), &sec) != F2V_OK) {
+            const int rc = lists > 0 ? f2v_index_search_rows(h, q.data(), cnt, k, metric, F2V_NEAREST_EXCLUDE_SELF, probes, ids.data(), scores.data(), nullptr, &found)
+                                     : f2v_nearest_rows(h, q.data(), cnt, k, metric, F2V_NEAREST_EXCLUDE_SELF, ids.data(), scores.data(), &sec);
+            if (rc != F2V_OK) {
                 fclose(f);
                 throw std::runtime_error(f2v_last_error());
+            }
+            if (lists > 0) {
+                sec = found.seconds;
+                candidates += found.candidates;
             }
             seconds += sec;
             for (uint32_t i = 0; i < cnt; i++) {
@@ -170,6 +183,23 @@ class algorithms {
         }
         if (fclose(f) != 0) throw std::runtime_error("cannot write " + name);
         printf("Nearest: k=%u metric=%s %.6f s, precision@k %llu/%llu\n", k, metric_name, seconds, (unsigned long long)hits, (unsigned long long)possible);
+        if (lists == 0) return;
+        printf("Index: lists %u probes %u candidates/query %.1f\n", lists, found.nprobe, rows ? (double)candidates / rows : 0.0);
+        if (check_count == 0) return;
+        const uint32_t m = check_count < rows ? check_count : rows;
+        std::vector<uint32_t> want((size_t)m * k);
+        q.resize(m);
+        ids.resize((size_t)m * k);
+        for (uint32_t i = 0; i < m; i++) q[i] = (uint32_t)((uint64_t)i * rows / m);
+        check(f2v_nearest_rows(h, q.data(), m, k, metric, F2V_NEAREST_EXCLUDE_SELF, want.data(), nullptr, nullptr));
+        check(f2v_index_search_rows(h, q.data(), m, k, metric, F2V_NEAREST_EXCLUDE_SELF, probes, ids.data(), nullptr, nullptr, nullptr));
+        uint64_t hit = 0, all = 0;
+        for (uint32_t i = 0; i < m; i++)
+            for (uint32_t j = 0; j < k && want[(size_t)i * k + j] != 0xFFFFFFFFu; j++) {
+                all++;
+                hit += std::find(ids.begin() + (size_t)i * k, ids.begin() + (size_t)(i + 1) * k, want[(size_t)i * k + j]) != ids.begin() + (size_t)(i + 1) * k ? 1 : 0;
+            }
+        printf("Recall@%u against the exact search (%u vertices): %.6f\n", k, m, all ? (double)hit / (double)all : 1.0);
     }
 
     // -cluster <k>: k-means on the trained matrix (f2v_kmeans: `restarts` seeded runs from `seed`, the one of lowest inertia) as

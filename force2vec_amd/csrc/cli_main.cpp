@@ -9,7 +9,8 @@
 // f2v_train_sharded; the ranks meet through files in a private temporary directory; same output, written by rank 0),
 // -loss <k> (print the training objective after every k-th epoch and the last, in the line the reference has commented out),
 // -nearest <k> [-metric dot|l2|cos] (after training: every vertex's k nearest rows as "<embd output name>.nn" and the
-// graph-reconstruction precision@k; default metric: the option's own similarity), -cluster <k> [-cluster-iters <n>]
+// graph-reconstruction precision@k; default metric: the option's own similarity; with -nearest-lists <L> [-nearest-probes <p>]
+// [-nearest-iters <i>] [-nearest-check <s>] through an inverted-file index: L k-means lists, p of them scored per query), -cluster <k> [-cluster-iters <n>]
 // [-cluster-restarts <r>] (after training: k-means on the embedding as "<embd output name>.clu" and its modularity on the graph),
 // -classify <labels file> [-classify-frac <f>] [-classify-splits <s>] (after training: node-classification F1 of the embedding),
 // -separation <labels file | kmeans> [-separation-sample <n>] (after training: the labelling's silhouette and Davies-Bouldin score),
@@ -42,6 +43,7 @@ struct Settings {
     long batch = 384, iter = 1200, threads = (long)std::thread::hardware_concurrency(), dim = 128, nsamples = 5, option = 5, bs = 0;
     long device = 0, seed = 1, cache = 0, binout = 0, fastrng = 0, notext = 0, gpus = 1, samegpu = 0, loss = 0, nearest = 0, cluster = 0, cluster_iters = 300, cluster_restarts = 10;
     std::string metric, classify, separation, foldin, foldin_init = "mean", layout_method = "pca";
+    long nearest_lists = 0, nearest_probes = 0, nearest_iters = 20, nearest_check = 0;  // nearest_probes 0: not given (8)
     long layout_iters = 1000;
     double layout_perplexity = 30.0;
     long foldin_iters = 300;
@@ -115,6 +117,10 @@ int main(int argc, char *argv[]) {
         {"-fastrng", Kind::Integer, &s.fastrng, "<int>, 1 = NON-PARITY fast mode: initial embeddings and option-7 walks from a device-side RNG."},
         {"-loss", Kind::Integer, &s.loss, "<int>, k > 0: print \"Iteration:<epoch> :LOGLIKELIHOOD: <loss>\" after every k-th epoch and the last (the training objective, include/f2v.h; one GPU). (default:0)"},
         {"-nearest", Kind::Integer, &s.nearest, "<int>, k in 1..128: after training write <output file>.nn, one line per vertex \"v j1 s1 ... jk sk\" (its k nearest rows, self excluded), and print the precision@k against the graph (one GPU). (default:0)"},
+        {"-nearest-lists", Kind::Integer, &s.nearest_lists, "<int>, L in 1..1024, at most the number of vertices: run the -nearest sweep through an inverted-file index (k-means of the trained matrix into L lists on the GPU, seeded by -seed; a query scores only the rows of the lists whose centroids are nearest) and print \"Index: lists <L> probes <P> candidates/query <c>\"; 0 = the exact search. (default:0)"},
+        {"-nearest-probes", Kind::Integer, &s.nearest_probes, "<int>, p in 1..128: lists a query of a -nearest-lists sweep scores; with p >= L the result is the exact search's. (default:8)"},
+        {"-nearest-iters", Kind::Integer, &s.nearest_iters, "<int>, most Lloyd iterations of the -nearest-lists k-means. (default:20)"},
+        {"-nearest-check", Kind::Integer, &s.nearest_check, "<int>, s > 0: also print \"Recall@<k> against the exact search (<s> vertices): <r>\" of a -nearest-lists sweep over the vertices floor(i n / s), i < s. (default:0)"},
         {"-cluster", Kind::Integer, &s.cluster, "<int>, k in 1..1024: after training cluster the embedding with k-means on the GPU, write <output file>.clu, one line per vertex \"v label\" (0-based), and print the clustering's modularity on the graph (one GPU; seeded by -seed). (default:0)"},
         {"-cluster-iters", Kind::Integer, &s.cluster_iters, "<int>, most Lloyd iterations of a -cluster run. (default:300)"},
         {"-cluster-restarts", Kind::Integer, &s.cluster_restarts, "<int>, seeded runs of -cluster, the one of lowest inertia is kept (the scorer's n_init). (default:10)"},
@@ -198,6 +204,26 @@ int main(int argc, char *argv[]) {
     const int metric = s.metric == "dot" ? F2V_SIM_DOT : s.metric == "l2" ? F2V_SIM_L2 : s.metric == "cos" ? F2V_SIM_COSINE : -1;
     if (metric < 0) {
         printf("-metric must be dot, l2 or cos.\n");
+        return 1;
+    }
+    if (s.nearest_lists < 0 || s.nearest_lists > F2V_INDEX_MAX_LISTS) {
+        printf("-nearest-lists must be 0..%d.\n", F2V_INDEX_MAX_LISTS);
+        return 1;
+    }
+    if (s.nearest_probes < 0 || s.nearest_probes > F2V_INDEX_MAX_PROBES) {
+        printf("-nearest-probes must be 1..%d.\n", F2V_INDEX_MAX_PROBES);
+        return 1;
+    }
+    if (s.nearest_iters < 0 || s.nearest_iters > 0x7FFFFFFF || s.nearest_check < 0 || s.nearest_check > 0x7FFFFFFF) {
+        printf("-nearest-iters and -nearest-check must be non-negative.\n");
+        return 1;
+    }
+    if (s.nearest == 0 && (s.nearest_lists > 0 || s.nearest_probes > 0 || s.nearest_check > 0)) {
+        printf("-nearest-lists, -nearest-probes and -nearest-check need -nearest.\n");
+        return 1;
+    }
+    if (s.nearest_lists == 0 && (s.nearest_probes > 0 || s.nearest_check > 0)) {
+        printf("-nearest-probes and -nearest-check need -nearest-lists.\n");
         return 1;
     }
     if (s.nearest > 0 && s.gpus > 1) {
@@ -367,7 +393,7 @@ int main(int argc, char *argv[]) {
                 if (f2v_train_losses(algo.h, epochs.data(), values.data(), count, &count) != F2V_OK) throw std::runtime_error(f2v_last_error());
                 for (uint32_t m = 0; m < count; m++) std::cout << "Iteration:" << epochs[m] << " :LOGLIKELIHOOD: " << values[3 * m] << std::endl;
             }
-            if (s.nearest > 0 && rank == 0) algo.writeNearest((uint32_t)s.nearest, metric, s.metric.c_str());
+            if (s.nearest > 0 && rank == 0) algo.writeNearest((uint32_t)s.nearest, metric, s.metric.c_str(), (uint32_t)s.nearest_lists, (uint32_t)(s.nearest_probes ? s.nearest_probes : 8), (uint32_t)s.nearest_iters, (uint64_t)s.seed, (uint32_t)s.nearest_check);
             if (s.cluster > 0 && rank == 0) algo.writeClusters((uint32_t)s.cluster, (uint32_t)s.cluster_iters, (uint32_t)s.cluster_restarts, (uint64_t)s.seed);
             if (!s.classify.empty() && rank == 0) algo.classify(s.classify, s.classify_frac, (uint32_t)s.classify_splits, (uint64_t)s.seed);
             if (!s.separation.empty() && rank == 0) algo.separation(s.separation, (uint32_t)s.separation_sample, (uint64_t)s.seed);

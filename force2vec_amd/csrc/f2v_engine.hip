@@ -34,6 +34,7 @@
 #include "f2v_kernels.hip.h"
 #include "f2v_nearest.hip.h"
 #include "f2v_kmeans.hip.h"
+#include "f2v_index.hip.h"
 #include "f2v_logreg.hip.h"
 #include "f2v_separation.hip.h"
 #include "f2v_layout.hip.h"
@@ -228,6 +229,24 @@ struct f2v_ctx {
         DevTimer timer;
         uint32_t splits = 0, block = 0, chunk = 8192;
     } nn;
+    // nearest neighbours through an index (f2v_index_*): the index in buffers of its own -- labels, members in list order, lists + 1
+    // offsets, centroids; no scorer's workspace overlaps them -- and the buffers of one query chunk of a search, allocated on first
+    // use and grown on demand; "index_chunk": queries per launch, "index_split_tiles": tiles of 128 candidates per work item of the
+    // scan (a longer list is cut into several ranges), "index_block" (0 = 128 where D <= 128 and a bucket has more than 32 queries
+    // left, else 32 | 32): queries per work item -- placement only
+    struct Index {
+        DevBuf<uint32_t> d_labels, d_members, d_offsets;
+        DevBuf<float> d_C;
+        std::vector<uint32_t> offsets;  // host copy of d_offsets
+        f2v_index_t info{};
+        bool built = false;
+        DevBuf<float> d_Q, d_rq, d_rc, d_scores;
+        DevBuf<uint32_t> d_qids, d_probes, d_counts, d_start, d_bucket, d_ids;
+        DevBuf<IxItem> d_items;
+        DevBuf<unsigned long long> d_ws;
+        DevTimer timer;
+        uint32_t chunk = 8192, split_tiles = 8, block = 0;
+    } ix;
     int rows_sorted = -1;  // the CSR's ids ascend inside every row (rows are searched by the nearest queries and f2v_modularity): -1 not checked yet (rows_ascending)
     // clustering (f2v_kmeans, f2v_modularity): the workspace f2v.h states, allocated on first use for the call's k and grown for a
     // larger one; "kmeans_block" (0 = from k | 64 | 128 | 256): rows per workgroup of kmeans_assign_kernel
@@ -2285,6 +2304,12 @@ const Param kParams[] = {
     {"nearest_block", F2V_FIELD(nn.block), kValue, kKeep, one_of<0, 32, 128>, "nearest_block must be 0, 32 or 128", set_nearest_block},
     // queries per launch: bounds the workspace (chunk x splits x k keys)
     {"nearest_chunk", F2V_FIELD(nn.chunk), kValue, kKeep, in<1, 65536>, "nearest_chunk must be 1..65536"},
+    // queries per launch of an index search: bounds its workspace (chunk x probes x ranges x k keys); results do not depend on it
+    {"index_chunk", F2V_FIELD(ix.chunk), kValue, kKeep, in<1, 65536>, "index_chunk must be 1..65536"},
+    // tiles of 128 candidates per work item of the index scan (longer lists are cut into ranges); results do not depend on it
+    {"index_split_tiles", F2V_FIELD(ix.split_tiles), kValue, kKeep, in<1, 65536>, "index_split_tiles must be 1..65536"},
+    // queries per work item of the index scan (0: 128 where D <= 128 and a bucket has more than 32 queries left, else 32); results do not depend on it
+    {"index_block", F2V_FIELD(ix.block), kValue, kKeep, one_of<0, 32>, "index_block must be 0 or 32"},
     // rows per workgroup of the k-means assignment kernel (0: 256 for k <= 2, 128 for k <= 4, else 64); results do not depend on it
     {"kmeans_block", F2V_FIELD(km.block), kValue, kKeep, one_of<0, 64, 128, 256>, "kmeans_block must be 0, 64, 128 or 256"},
     // samples per launch of the silhouette: bounds its workspace (chunk x spans doubles); results do not depend on it
@@ -3561,10 +3586,11 @@ int launch_nearest_t(f2v_ctx *c, const NnArgs &a, uint32_t qblocks, uint32_t spl
 // merge (/ count) on the handle's stream between two events.  ids_out / scores_out may be nullptr (the recall count needs neither).
 // `X`: the n x D matrix that is searched -- the handle's, or f2v_trustworthiness's second matrix (row queries, no cosine, no CSR flag);
 // `d_ids_dst` (may be nullptr): device array that also receives the ids, nq x k; `d_scores_dst`: the same for the scores; `n_rows`
-// (0: n): the rows of `X` where it is not a matrix over the vertices (f2v_tsne_affinities' gathered sample).
+// (0: n): the rows of `X` where it is not a matrix over the vertices (f2v_tsne_affinities' gathered sample, the index's centroids);
+// `vecs_on_device`: `vecs` is a device array (the index's staged queries).
 int nearest_run_on(f2v_ctx *c, const float *X, uint32_t D, const uint32_t *qids, bool all, const float *vecs, uint32_t nq, uint32_t k, int metric,
                    uint32_t flags, uint32_t *ids_out, float *scores_out, uint64_t *recall_out, double *seconds_out, uint32_t *d_ids_dst,
-                   float *d_scores_dst = nullptr, uint32_t n_rows = 0) {
+                   float *d_scores_dst = nullptr, uint32_t n_rows = 0, bool vecs_on_device = false) {
     f2v_ctx::Nearest &w = c->nn;
     const uint32_t n = n_rows ? n_rows : c->n;
     const bool rows = qids || all, cosine = metric == F2V_SIM_COSINE;
@@ -3597,7 +3623,7 @@ int nearest_run_on(f2v_ctx *c, const float *X, uint32_t D, const uint32_t *qids,
             for (uint32_t i = 0; i < cq; i++) iota[i] = done + i;
         }
         if (rows) HIPC(hipMemcpyAsync(w.d_qids, all ? iota.data() : qids + done, (size_t)cq * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        else HIPC(hipMemcpyAsync(w.d_Q, vecs + (size_t)done * D, (size_t)cq * D * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        else HIPC(hipMemcpyAsync(w.d_Q, vecs + (size_t)done * D, (size_t)cq * D * sizeof(float), vecs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
         F2VC(w.timer.start(c->stream));
         if (rows) hipLaunchKernelGGL(nearest_gather_kernel, dim3(std::min<size_t>(((size_t)cq * D + 255) / 256, 4096)), dim3(256), 0, c->stream, X, (const uint32_t *)w.d_qids, cq, D, w.d_Q);
         if (cosine) {
@@ -3807,6 +3833,220 @@ int kmeans_run(f2v_ctx *c, uint32_t k, uint32_t max_iters, uint32_t *iterations,
                            (const uint32_t *)w.d_pstart, D, w.d_C);
         HIPC(hipGetLastError());
     }
+}
+
+// ---- nearest neighbours through an index (f2v_index.hip.h; definition in include/f2v.h) ------------------------------------------
+constexpr size_t kIxMaxKeys = (size_t)1 << 24;  // keys of one launch's result lists (128 MiB): a search runs fewer queries per launch to stay below
+constexpr uint32_t kIxMaxSplits = 16;           // candidate ranges of the longest list: bounds the lists the merge reads per query
+constexpr uint32_t kIxFewSplits = 2;            // ... in a call of kIxManyPairs (query, list) pairs or more
+constexpr uint64_t kIxManyPairs = 16384;
+
+void index_drop(f2v_ctx *c) {
+    f2v_ctx::Index &w = c->ix;
+    (void)hipStreamSynchronize(c->stream);  // a search may still read it
+    w.d_labels.release();
+    w.d_members.release();
+    w.d_offsets.release();
+    w.d_C.release();
+    w.offsets.clear();
+    w.info = f2v_index_t{};
+    w.built = false;
+}
+
+// Both builds end here: the host's labels and centroids become the handle's index.  The counting sort into list order (ascending id
+// inside a list) is the clustering's own, run in its workspace; what it leaves is copied into the index's buffers.
+int index_install(f2v_ctx *c, const char *who, const uint32_t *labels, const float *centroids, uint32_t lists, const f2v_kmeans_t *km, f2v_index_t *info_out) {
+    f2v_ctx::Index &w = c->ix;
+    const uint32_t n = c->n, D = c->D;
+    for (uint32_t v = 0; v < n; v++)
+        if (labels[v] >= lists) return fail(F2V_EINVAL, "%s: labels[%u] = %u is not a list (lists = %u)", who, v, labels[v], lists);
+    HIPC(hipSetDevice(c->device));
+    const char *what = "index";
+    w.built = false;
+    F2VC(w.d_labels.reserve(c, n, what));
+    F2VC(w.d_members.reserve(c, n, what));
+    F2VC(w.d_offsets.reserve(c, (size_t)lists + 1, what));
+    F2VC(w.d_C.reserve(c, (size_t)lists * D, what));
+    F2VC(kmeans_workspace(c, lists));
+    HIPC(hipMemcpyAsync(w.d_labels, labels, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(w.d_C, centroids, (size_t)lists * D * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    F2VC(w.timer.start(c->stream));
+    kmeans_sort(c, w.d_labels, n, lists);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(w.d_members, c->km.d_order, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+    HIPC(hipMemcpyAsync(w.d_offsets, c->km.d_start, ((size_t)lists + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+    F2VC(w.timer.stop(c->stream));
+    w.offsets.assign((size_t)lists + 1, 0);
+    HIPC(hipMemcpyAsync(w.offsets.data(), w.d_offsets, ((size_t)lists + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    F2VC(check_kernel_err(c, who));
+    f2v_index_t info{};
+    if (km) {
+        info.inertia = km->inertia;
+        info.seconds = km->seconds;
+        info.iterations = km->iterations;
+        info.converged = km->converged;
+    }
+    F2VC(w.timer.seconds(&info.seconds));
+    info.bytes = (2 * (uint64_t)n + lists + 1) * sizeof(uint32_t) + (uint64_t)lists * D * sizeof(float);
+    info.lists = lists;
+    for (uint32_t l = 0; l < lists; l++) {
+        const uint32_t len = w.offsets[l + 1] - w.offsets[l];
+        info.largest = std::max(info.largest, len);
+        info.empty += len == 0 ? 1u : 0u;
+    }
+    w.info = info;
+    w.built = true;
+    if (info_out) *info_out = info;
+    return F2V_OK;
+}
+
+template <bool L2, int WQ, int MI, int NI>
+int launch_index_scan_t(f2v_ctx *c, const IxArgs &a, uint32_t items) {
+    const size_t lds = ix_lds_bytes(32u * WQ * MI, a.D);
+    F2VC(allow_lds(c, reinterpret_cast<const void *>(&index_scan_kernel<L2, WQ, MI, NI>), lds));
+    hipLaunchKernelGGL((index_scan_kernel<L2, WQ, MI, NI>), dim3(items), dim3(kNnThreads), lds, c->stream, a);
+    HIPC(hipGetLastError());
+    return F2V_OK;
+}
+
+// What the two searches share behind their checks.  Queries are rows `qids` of the matrix or the host vectors `vecs`; they run in
+// chunks, each chunk as: stage the vectors / rank the centroids (nearest_run_on over the centroid matrix: the defined probe order) /
+// count the pairs per list -- the counts come back, the host cuts the buckets into work items -- / fill the buckets / scan / merge.
+int index_search(f2v_ctx *c, const char *who, const uint32_t *qids, const float *vecs, uint32_t nq, uint32_t k, int metric, uint32_t flags,
+                 uint32_t nprobe, uint32_t *ids_out, float *scores_out, uint32_t *probes_out, f2v_index_search_t *info_out) {
+    f2v_ctx::Index &w = c->ix;
+    const uint32_t n = c->n, D = c->D, lists = w.info.lists, P = std::min(nprobe, lists);
+    const bool rows = qids != nullptr, cosine = metric == F2V_SIM_COSINE;
+    const float *X = c->d_X[c->cur];
+    const char *what = "index search";
+    // candidate ranges per list: placement only (a query's lists are merged whatever their number)
+    const uint32_t tiles_max = (w.info.largest + kNnTile - 1) / kNnTile;
+    const uint32_t max_splits = (uint64_t)nq * P >= kIxManyPairs ? kIxFewSplits : kIxMaxSplits;  // many pairs fill the card by themselves
+    uint32_t tps = w.split_tiles, splits = std::max(1u, (tiles_max + tps - 1) / tps);
+    if (splits > max_splits) {
+        tps = (tiles_max + max_splits - 1) / max_splits;
+        splits = (tiles_max + tps - 1) / tps;
+    }
+    const uint32_t big = w.block == kIxBlock || D > 128 ? 0u : kIxBlockBig;  // "index_block": the large form's block, 0 where only the small form runs
+    const size_t per_query = (size_t)P * splits * k;
+    const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(w.chunk, kIxMaxKeys / per_query));
+    if (cosine) F2VC(w.d_rc.reserve(c, n, what));
+    F2VC(w.d_counts.reserve(c, 2 * (size_t)lists, what));  // the counts, then the fill's cursors
+    F2VC(w.d_start.reserve(c, lists, what));
+    std::vector<uint32_t> counts(lists), start(lists);
+    std::vector<IxItem> items, items_big;
+    double seconds = 0.0;
+    uint64_t candidates = 0;
+    for (uint32_t done = 0; done < nq; done += chunk) {
+        const uint32_t cq = std::min(chunk, nq - done), pairs = cq * P;
+        const size_t slots = (size_t)cq * k;
+        F2VC(w.d_Q.reserve(c, (size_t)cq * D, what));
+        F2VC(w.d_rq.reserve(c, cq, what));
+        F2VC(w.d_qids.reserve(c, cq, what));
+        F2VC(w.d_probes.reserve(c, pairs, what));
+        F2VC(w.d_bucket.reserve(c, pairs, what));
+        F2VC(w.d_ws.reserve(c, cq * per_query, what));
+        F2VC(w.d_ids.reserve(c, slots, what));
+        F2VC(w.d_scores.reserve(c, slots, what));
+        if (rows) HIPC(hipMemcpyAsync(w.d_qids, qids + done, (size_t)cq * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        else HIPC(hipMemcpyAsync(w.d_Q, vecs + (size_t)done * D, (size_t)cq * D * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        F2VC(w.timer.start(c->stream));
+        if (rows) hipLaunchKernelGGL(nearest_gather_kernel, dim3(std::min<size_t>(((size_t)cq * D + 255) / 256, 4096)), dim3(256), 0, c->stream, X, (const uint32_t *)w.d_qids, cq, D, w.d_Q);
+        if (cosine) {
+            if (done == 0) hipLaunchKernelGGL(nearest_rnorm_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, X, n, D, w.d_rc);
+            hipLaunchKernelGGL(nearest_rnorm_kernel, dim3((cq + 255) / 256), dim3(256), 0, c->stream, (const float *)w.d_Q, cq, D, w.d_rq);
+        }
+        HIPC(hipGetLastError());
+        double probe_seconds = 0.0;  // (inside this call's own events)
+        F2VC(nearest_run_on(c, w.d_C, D, nullptr, false, w.d_Q, cq, P, metric, 0, nullptr, nullptr, nullptr, &probe_seconds, w.d_probes, nullptr, lists, true));
+        HIPC(hipMemsetAsync(w.d_counts, 0, 2 * (size_t)lists * sizeof(uint32_t), c->stream));
+        hipLaunchKernelGGL(index_count_kernel, dim3((pairs + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)w.d_probes, pairs, lists, w.d_counts);
+        HIPC(hipGetLastError());
+        F2VC(w.timer.stop(c->stream));
+        HIPC(hipMemcpyAsync(counts.data(), w.d_counts, (size_t)lists * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (probes_out) HIPC(hipMemcpyAsync(probes_out + (size_t)done * P, w.d_probes, (size_t)pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+        F2VC(w.timer.seconds(&seconds));
+        // the work items: per list its bucket in blocks of queries -- 128 where more than 32 are left and the large form runs, else 32 --
+        // times its candidate ranges
+        items.clear();
+        items_big.clear();
+        const uint64_t step = (uint64_t)tps * kNnTile;
+        uint32_t run = 0;
+        for (uint32_t l = 0; l < lists; l++) {
+            const uint32_t lo = w.offsets[l], len = w.offsets[l + 1] - lo;
+            start[l] = run;
+            candidates += (uint64_t)counts[l] * len;
+            for (uint32_t b = 0; len && b < counts[l];) {
+                const bool large = big && counts[l] - b > kIxBlock;
+                const uint32_t qb = large ? big : kIxBlock, cnt = std::min(qb, counts[l] - b);
+                for (uint32_t s = 0; s * step < len; s++)
+                    (large ? items_big : items).push_back(IxItem{(uint32_t)(lo + s * step), (uint32_t)(lo + std::min<uint64_t>(len, (s + 1) * step)), run + b, cnt, s});
+                b += cnt;
+            }
+            run += counts[l];
+        }
+        const size_t n_small = items.size(), n_big = items_big.size();
+        items.insert(items.end(), items_big.begin(), items_big.end());
+        F2VC(w.d_items.reserve(c, items.size(), what));
+        HIPC(hipMemcpyAsync(w.d_start, start.data(), (size_t)lists * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        if (!items.empty()) HIPC(hipMemcpyAsync(w.d_items, items.data(), items.size() * sizeof(IxItem), hipMemcpyHostToDevice, c->stream));
+        F2VC(w.timer.start(c->stream));
+        HIPC(hipMemsetAsync(w.d_ws, 0, cq * per_query * sizeof(nn_key_t), c->stream));
+        hipLaunchKernelGGL(index_fill_kernel, dim3((pairs + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)w.d_probes, pairs, lists, (const uint32_t *)w.d_start,
+                           w.d_counts + lists, w.d_bucket);
+        HIPC(hipGetLastError());
+        if (!items.empty()) {
+            IxArgs a{};
+            a.X = X;
+            a.Q = w.d_Q;
+            a.rq = cosine ? w.d_rq : nullptr;
+            a.rc = cosine ? w.d_rc : nullptr;
+            a.qids = rows ? w.d_qids : nullptr;
+            a.rowptr = c->d_rowptr;
+            a.colids = c->d_colids;
+            a.members = w.d_members;
+            a.bucket = w.d_bucket;
+            a.items = w.d_items;
+            a.ws = w.d_ws;
+            a.n = n;
+            a.D = D;
+            a.nq = cq;
+            a.k = k;
+            a.flags = flags;
+            a.P = P;
+            a.splits = splits;
+            a.cosine = cosine ? 1u : 0u;
+            if (n_big) {  // first: these are the long work items
+                a.items = w.d_items + n_small;
+                F2VC((metric == F2V_SIM_L2 ? launch_index_scan_t<true, 2, 2, 2>(c, a, (uint32_t)n_big) : launch_index_scan_t<false, 2, 2, 2>(c, a, (uint32_t)n_big)));
+            }
+            if (n_small) {
+                a.items = w.d_items;
+                F2VC((metric == F2V_SIM_L2 ? launch_index_scan_t<true, 1, 1, 1>(c, a, (uint32_t)n_small) : launch_index_scan_t<false, 1, 1, 1>(c, a, (uint32_t)n_small)));
+            }
+        }
+        hipLaunchKernelGGL(nearest_merge_kernel, dim3(cq), dim3(256), 0, c->stream, (const nn_key_t *)w.d_ws, P * splits, k, w.d_ids, w.d_scores);
+        HIPC(hipGetLastError());
+        F2VC(w.timer.stop(c->stream));
+        HIPC(hipMemcpyAsync(ids_out + (size_t)done * k, w.d_ids, slots * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (scores_out) HIPC(hipMemcpyAsync(scores_out + (size_t)done * k, w.d_scores, slots * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+        F2VC(w.timer.seconds(&seconds));
+    }
+    F2VC(check_kernel_err(c, who));
+    if (info_out) *info_out = f2v_index_search_t{seconds, candidates, P, 0};
+    return F2V_OK;
+}
+
+// The searches' common checks, in the order f2v.h lists them.  -> 1: nq == 0, nothing to do and nothing touched.
+int index_enter(f2v_ctx *c, const char *who, uint32_t nq, uint32_t k, int metric, uint32_t flags, uint32_t nprobe, f2v_index_search_t *info_out) {
+    if (nprobe == 0 || nprobe > F2V_INDEX_MAX_PROBES) return fail(F2V_EINVAL, "%s: nprobe = %u is outside 1..%d", who, nprobe, F2V_INDEX_MAX_PROBES);
+    if (!c->ix.built) return fail(F2V_ESTATE, "%s: the handle has no index: build one first", who);
+    const int rc = nearest_enter(c, who, nq, k, metric, flags, (flags & F2V_NEAREST_EXCLUDE_NEIGHBOURS) != 0);
+    if (rc == 1 && info_out) *info_out = f2v_index_search_t{0.0, 0, std::min(nprobe, c->ix.info.lists), 0};
+    return rc;
 }
 
 // ---- logistic regression (f2v_logreg.hip.h; definition in include/f2v.h) ----------------------------------------------------------
@@ -5617,6 +5857,63 @@ int f2v_neighbour_recall(f2v_handle c, const uint32_t *query_ids, uint32_t nq, u
     *hits_out = counts[0];
     *possible_out = counts[1];
     return F2V_OK;
+}
+
+int f2v_index_build(f2v_handle c, uint32_t lists, uint32_t max_iters, uint64_t seed, const float *init_centroids, f2v_index_t *info_out) {
+    if (!c) return fail(F2V_EINVAL, "f2v_index_build: null argument");
+    if (lists == 0 || lists > F2V_INDEX_MAX_LISTS || lists > c->n)
+        return fail(F2V_EINVAL, "f2v_index_build: lists = %u is outside 1..min(%d, n = %u)", lists, F2V_INDEX_MAX_LISTS, c->n);
+    std::vector<uint32_t> labels(c->n);
+    std::vector<float> centroids((size_t)lists * c->D);
+    f2v_kmeans_t km{};
+    F2VC(f2v_kmeans(c, lists, max_iters, 1, seed, init_centroids, labels.data(), centroids.data(), nullptr, &km));
+    return index_install(c, "f2v_index_build", labels.data(), centroids.data(), lists, &km, info_out);
+}
+
+int f2v_index_build_given(f2v_handle c, const uint32_t *labels, const float *centroids, uint32_t lists, f2v_index_t *info_out) {
+    if (!c || !labels || !centroids) return fail(F2V_EINVAL, "f2v_index_build_given: null argument");
+    if (lists == 0 || lists > F2V_INDEX_MAX_LISTS || lists > c->n)
+        return fail(F2V_EINVAL, "f2v_index_build_given: lists = %u is outside 1..min(%d, n = %u)", lists, F2V_INDEX_MAX_LISTS, c->n);
+    if (c->n >= 0xFFFFFFFFu - 256u) return fail(F2V_EINVAL, "f2v_index_build_given: too many vertices for 32-bit row blocks");
+    return index_install(c, "f2v_index_build_given", labels, centroids, lists, nullptr, info_out);
+}
+
+int f2v_index_get(f2v_handle c, uint32_t *labels_out, float *centroids_out, uint64_t *counts_out, f2v_index_t *info_out) {
+    if (!c) return fail(F2V_EINVAL, "f2v_index_get: null argument");
+    f2v_ctx::Index &w = c->ix;
+    if (!w.built) return fail(F2V_ESTATE, "f2v_index_get: the handle has no index: build one first");
+    HIPC(hipSetDevice(c->device));
+    if (labels_out) HIPC(hipMemcpyAsync(labels_out, w.d_labels, (size_t)c->n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (centroids_out) HIPC(hipMemcpyAsync(centroids_out, w.d_C, (size_t)w.info.lists * c->D * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    for (uint32_t l = 0; counts_out && l < w.info.lists; l++) counts_out[l] = w.offsets[l + 1] - w.offsets[l];
+    if (info_out) *info_out = w.info;
+    return F2V_OK;
+}
+
+int f2v_index_drop(f2v_handle c) {
+    if (!c) return fail(F2V_EINVAL, "f2v_index_drop: null argument");
+    (void)hipSetDevice(c->device);
+    index_drop(c);
+    return F2V_OK;
+}
+
+int f2v_index_search_rows(f2v_handle c, const uint32_t *query_ids, uint32_t nq, uint32_t k, int metric, uint32_t flags, uint32_t nprobe,
+                          uint32_t *ids_out, float *scores_out, uint32_t *probes_out, f2v_index_search_t *info_out) {
+    if (!c || (nq && (!query_ids || !ids_out))) return fail(F2V_EINVAL, "f2v_index_search_rows: null argument");
+    for (uint32_t i = 0; i < nq; i++)
+        if (query_ids[i] >= c->n) return fail(F2V_EINVAL, "f2v_index_search_rows: query_ids[%u] = %u is not a vertex", i, query_ids[i]);
+    const int rc = index_enter(c, "f2v_index_search_rows", nq, k, metric, flags, nprobe, info_out);
+    if (rc != F2V_OK) return rc == 1 ? F2V_OK : rc;
+    return index_search(c, "f2v_index_search_rows", query_ids, nullptr, nq, k, metric, flags, nprobe, ids_out, scores_out, probes_out, info_out);
+}
+
+int f2v_index_search_vectors(f2v_handle c, const float *queries, uint32_t nq, uint32_t k, int metric, uint32_t nprobe, uint32_t *ids_out,
+                             float *scores_out, uint32_t *probes_out, f2v_index_search_t *info_out) {
+    if (!c || (nq && (!queries || !ids_out))) return fail(F2V_EINVAL, "f2v_index_search_vectors: null argument");
+    const int rc = index_enter(c, "f2v_index_search_vectors", nq, k, metric, 0, nprobe, info_out);
+    if (rc != F2V_OK) return rc == 1 ? F2V_OK : rc;
+    return index_search(c, "f2v_index_search_vectors", nullptr, queries, nq, k, metric, 0, nprobe, ids_out, scores_out, probes_out, info_out);
 }
 
 int f2v_push_export(f2v_handle c, void *handles_out) {

@@ -23,6 +23,7 @@ Objective = namedtuple("Objective", "loss attraction repulsion positive_pairs ne
 # Engine.kmeans / Engine.modularity (include/f2v.h: clustering)
 KMeans = namedtuple("KMeans", "labels centroids inertia iterations converged restart counts")
 Modularity = namedtuple("Modularity", "q edges inside degree")
+IndexInfo = namedtuple("IndexInfo", "lists inertia iterations converged largest empty bytes seconds")
 
 
 # Engine.pca / Engine.trustworthiness (include/f2v.h: layout)
@@ -310,6 +311,82 @@ class Engine:
             self._ck(self._L.f2v_neighbour_recall(self._h, _u32(q), len(q), k, m, C.byref(hits), C.byref(possible), C.byref(sec)))
         self.last_nearest_seconds = sec.value
         return hits.value, possible.value
+
+    # -- nearest neighbours through an index (include/f2v.h: definition; exact top-k over the members of the probed lists) ---------
+    def build_index(self, lists=None, max_iters=20, seed=1, init=None, labels=None, centroids=None):
+        """Partition the rows into `lists` lists for index_search -> IndexInfo.  By k-means on the matrix as it stands (the very
+        labels and centroids kmeans(lists, max_iters, seed) returns; `init`: its initial centroids), or from the given `labels`
+        (uint32 [n]) and `centroids` (float32 [lists, dim]).  lists=None: min(1024, max(1, round(sqrt(n)))), or the centroids'
+        count in the given form.  The index keeps no copy of the matrix and is never rebuilt by itself."""
+        info = _lib.IndexInfo()
+        if (labels is None) != (centroids is None):
+            raise ValueError("build_index: give labels and centroids together")
+        if labels is not None:
+            cen = np.ascontiguousarray(centroids, dtype=np.float32)
+            lab = np.ascontiguousarray(labels, dtype=np.uint32).reshape(-1)
+            if cen.ndim != 2 or cen.shape[1] != self.dim or len(lab) != self.n or (lists is not None and lists != cen.shape[0]):
+                raise ValueError("build_index: labels must be [%d] and centroids [lists, %d]" % (self.n, self.dim))
+            self._ck(self._L.f2v_index_build_given(self._h, _u32(lab), _f32(cen), cen.shape[0], C.byref(info)))
+        else:
+            if lists is None:
+                lists = min(_lib.INDEX_MAX_LISTS, max(1, int(round(self.n ** 0.5))))
+            c0 = None
+            if init is not None:
+                c0 = np.ascontiguousarray(init, dtype=np.float32)
+                if c0.shape != (lists, self.dim):
+                    raise ValueError("build_index: init must be [%d, %d]" % (lists, self.dim))
+            self._ck(self._L.f2v_index_build(self._h, lists, max_iters, seed, _f32(c0) if c0 is not None else None, C.byref(info)))
+        return IndexInfo(info.lists, info.inertia, info.iterations, bool(info.converged), info.largest, info.empty, info.bytes, info.seconds)
+
+    def index(self):
+        """The index as it stands -> (labels uint32 [n], centroids float32 [lists, dim], counts uint64 [lists])."""
+        info = _lib.IndexInfo()
+        self._ck(self._L.f2v_index_get(self._h, None, None, None, C.byref(info)))
+        labels = np.empty(self.n, dtype=np.uint32)
+        centroids = np.empty((info.lists, self.dim), dtype=np.float32)
+        counts = np.empty(info.lists, dtype=np.uint64)
+        self._ck(self._L.f2v_index_get(self._h, _u32(labels), _f32(centroids), counts.ctypes.data_as(C.POINTER(C.c_uint64)), None))
+        return labels, centroids, counts
+
+    def drop_index(self):
+        self._ck(self._L.f2v_index_drop(self._h))
+
+    def index_search(self, ids=None, vectors=None, k=10, metric="dot", nprobe=8, exclude_self=True, exclude_neighbours=False, details=False):
+        """nearest() over the members of the `nprobe` lists whose centroids are nearest to each query -> (ids, scores), with
+        `details` also (probes uint32 [nq, P], {"seconds", "candidates", "nprobe"}).  Same queries, metrics, exclusions, order and
+        padding as nearest(); with nprobe >= lists the two are equal bit for bit.  `last_nearest_seconds` keeps the device time."""
+        m = METRICS[metric] if isinstance(metric, str) else int(metric)
+        ginfo, info = _lib.IndexInfo(), _lib.IndexSearchInfo()
+        self._ck(self._L.f2v_index_get(self._h, None, None, None, C.byref(ginfo)))
+        P = max(1, min(int(nprobe), ginfo.lists))
+        if vectors is not None:
+            if ids is not None:
+                raise ValueError("index_search: give ids or vectors, not both")
+            q = np.ascontiguousarray(vectors, dtype=np.float32)
+            if q.ndim != 2 or q.shape[1] != self.dim:
+                raise ValueError("index_search: vectors must be [nq, %d]" % self.dim)
+            nq = q.shape[0]
+            out_ids, out_scores, probes = np.empty((nq, k), dtype=np.uint32), np.empty((nq, k), dtype=np.float32), np.empty((nq, P), dtype=np.uint32)
+            self._ck(self._L.f2v_index_search_vectors(self._h, _f32(q), nq, k, m, nprobe, _u32(out_ids), _f32(out_scores), _u32(probes), C.byref(info)))
+        else:
+            q = np.arange(self.n, dtype=np.uint32) if ids is None else np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+            flags = (_lib.NEAREST_EXCLUDE_SELF if exclude_self else 0) | (_lib.NEAREST_EXCLUDE_NEIGHBOURS if exclude_neighbours else 0)
+            out_ids, out_scores, probes = np.empty((len(q), k), dtype=np.uint32), np.empty((len(q), k), dtype=np.float32), np.empty((len(q), P), dtype=np.uint32)
+            self._ck(self._L.f2v_index_search_rows(self._h, _u32(q), len(q), k, m, flags, nprobe, _u32(out_ids), _f32(out_scores), _u32(probes), C.byref(info)))
+        self.last_nearest_seconds = info.seconds
+        if details:
+            return out_ids, out_scores, probes, {"seconds": info.seconds, "candidates": info.candidates, "nprobe": info.nprobe}
+        return out_ids, out_scores
+
+    def index_recall(self, k=10, metric="dot", nprobe=8, ids=None):
+        """How many of nearest()'s top-k ids index_search finds for the vertices `ids` (default: all) -> (found, possible)."""
+        want, _ = self.nearest(ids=ids, k=k, metric=metric)
+        got, _ = self.index_search(ids=ids, k=k, metric=metric, nprobe=nprobe)
+        found = 0
+        for lo in range(0, len(want), 65536):  # set intersection per query (a row's ids are distinct), in blocks that bound the comparison table
+            g, w = got[lo:lo + 65536], want[lo:lo + 65536]
+            found += int(((g[:, None, :] == w[:, :, None]).any(axis=2) & (w != _lib.NEAREST_PAD_ID)).sum())
+        return found, int((want != _lib.NEAREST_PAD_ID).sum())
 
     # -- clustering (include/f2v.h: definition; a function of the matrix, k, max_iters, restarts and the seed alone) -------------
     def kmeans(self, k, max_iters=300, seed=1, restarts=1, init=None):

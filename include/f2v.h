@@ -460,6 +460,79 @@ F2V_API int f2v_kmeans(f2v_handle h, uint32_t k, uint32_t max_iters, uint32_t re
 F2V_API int f2v_modularity(f2v_handle h, const uint32_t *labels /* n */, uint32_t n_clusters, double *q_out, uint64_t *edges_out,
                    uint64_t *inside_out, uint64_t *degree_out);
 
+/* ---- nearest neighbours through an index ---------------------------------------------------------------------------------------
+ * f2v_nearest_* score every query against all n rows.  An inverted-file index looks only where the answer can be: the rows are
+ * partitioned once, and a query scores the rows of the few lists whose centroids are nearest.  It is EXACT top-k over a well-defined
+ * candidate set, so the rule that a result is a function of its inputs alone, bit for bit, holds here too.
+ *   index       a partition of the n vertices into `lists` lists, labels[v] < lists, plus one centroid of D floats per list;
+ *               1 <= lists <= min(n, F2V_INDEX_MAX_LISTS).  The members of list c are the vertices with labels[v] == c in ascending
+ *               id; an empty list is legal.
+ *   build       k-means form: labels and centroids are exactly what f2v_kmeans(h, lists, max_iters, 1, seed, init_centroids, ...)
+ *               returns on the matrix as it stands, bit for bit -- it IS that call, not a second k-means; info reports its inertia,
+ *               iterations and converged.  Given form: the caller supplies labels (n words) and centroids (lists x D floats, any
+ *               values); nothing requires a vertex to lie in the list of its nearest centroid, the definition below does not care.
+ *   ownership   the index lives in buffers of its own inside the handle (labels, members in list order, lists + 1 offsets,
+ *               centroids: info.bytes), not in the growable workspaces that f2v_kmeans, f2v_silhouette and the other scorers
+ *               overwrite: later f2v_kmeans calls, training and f2v_set_embeddings leave it alone.  A second build replaces it;
+ *               f2v_index_drop and f2v_destroy free it.
+ *   no copy     THE INDEX HOLDS NO COPY OF THE MATRIX.  Scores, and the vectors of queries given by id, always come from the matrix as
+ *               f2v_get_embeddings would return it at the time of the search (pending minibatches are committed first).  Training or
+ *               f2v_set_embeddings after a build makes the PARTITION stale: that costs recall and never makes a result ill-defined.
+ *               Nothing rebuilds the index by itself and nothing tracks its age.
+ *   search      scores, metrics, flags, ranking order and padding (id 0xFFFFFFFF, score -inf) are those of "nearest neighbours"
+ *               above, unchanged.  For a query q and nprobe, P = min(nprobe, lists).  The probed lists are the first P entries of the
+ *               result order f2v_nearest_vectors gives for q over the lists x D centroid matrix with the call's metric and k = P
+ *               (score descending, ties to the lower list index, a NaN score last, cosine with r = 0 for a zero centroid; an empty
+ *               list is ranked like any other).  The candidates are the members of the probed lists; the result is the first k
+ *               candidates, after the exclusions, in the nearest-neighbour order.  1 <= nprobe <= F2V_INDEX_MAX_PROBES,
+ *               1 <= k <= F2V_NEAREST_MAX_K.  probes_out (nq x P, may be NULL) receives the probed lists in probe order.
+ * Consequences:
+ *   (a) the result is a function of (X, labels, centroids, metric, k, nprobe, flags, query) alone: never of how many queries share a
+ *       call, of how (query, list) pairs are grouped into workgroups, of "index_chunk" (queries per launch, default 8192),
+ *       "index_split_tiles" (tiles of 128 candidates per work item of the scan, default 8), "index_block" (queries per work item of
+ *       the scan: 0 = 128 where D <= 128 and a list has more than 32 queries left, else 32 | 32) or any other tunable, of the handle, or
+ *       of the order in which workgroups or atomics land (the only atomics are integer counters that place work);
+ *   (b) with nprobe >= lists (possible for lists <= 128) ids and scores equal f2v_nearest_rows / f2v_nearest_vectors bit for bit;
+ *   (c) per query the probed lists at nprobe = p are a prefix of those at p + 1, so the number of true top-k ids found never falls
+ *       as nprobe rises.
+ * f2v_index_search_t: seconds -- device time between events around the call's own launches; nprobe -- the P used; candidates -- the
+ * sum over the queries of the member counts of their probed lists (an integer function of the inputs).  f2v_index_t: the k-means
+ * form's inertia / iterations / converged (0 in the given form), seconds (the k-means and the counting sort into list order), bytes
+ * (device bytes the index holds), lists, largest (members of the longest list), empty (lists without members).
+ * No call touches the matrices, the rand() stream or any later training result; all run on the handle's stream; on a handle attached
+ * to a push exchange they read this rank's replica.  The searches' workspace (one query chunk: vectors, probes, buckets, work items,
+ * chunk x P x ranges x k keys, capped at 2^24 keys by running fewer queries per launch) is allocated on first use and freed by
+ * f2v_destroy.
+ * F2V_ESTATE: a search or f2v_index_get without an index, a k-means build without valid embeddings.  F2V_EINVAL: the
+ * nearest calls' conditions, lists = 0, lists > n or lists > F2V_INDEX_MAX_LISTS, a label >= lists, nprobe = 0 or nprobe >
+ * F2V_INDEX_MAX_PROBES, null labels or centroids in the given form.  nq = 0 is F2V_OK and touches nothing. */
+#define F2V_INDEX_MAX_LISTS 1024 /* == F2V_KMEANS_MAX_K */
+#define F2V_INDEX_MAX_PROBES 128 /* == F2V_NEAREST_MAX_K */
+typedef struct {
+    double inertia, seconds;
+    uint64_t bytes;
+    uint32_t lists, iterations, converged, largest, empty, reserved;
+} f2v_index_t;
+typedef struct {
+    double seconds;
+    uint64_t candidates;
+    uint32_t nprobe, reserved;
+} f2v_index_search_t;
+F2V_API int f2v_index_build(f2v_handle h, uint32_t lists, uint32_t max_iters, uint64_t seed, const float *init_centroids /* lists x D or NULL */,
+                    f2v_index_t *info_out /* may be NULL */);
+F2V_API int f2v_index_build_given(f2v_handle h, const uint32_t *labels /* n */, const float *centroids /* lists x D */, uint32_t lists,
+                          f2v_index_t *info_out /* may be NULL */);
+/* The index as it stands: labels (n), centroids (lists x D), member counts (lists) and the build's info; each output may be NULL. */
+F2V_API int f2v_index_get(f2v_handle h, uint32_t *labels_out, float *centroids_out, uint64_t *counts_out, f2v_index_t *info_out);
+/* Frees the index; F2V_OK where there is none. */
+F2V_API int f2v_index_drop(f2v_handle h);
+/* Queries are rows of the matrix.  ids_out: nq x k; scores_out: nq x k, may be NULL; probes_out: nq x P, may be NULL; info_out may be NULL. */
+F2V_API int f2v_index_search_rows(f2v_handle h, const uint32_t *query_ids, uint32_t nq, uint32_t k, int metric, uint32_t flags, uint32_t nprobe,
+                          uint32_t *ids_out, float *scores_out, uint32_t *probes_out, f2v_index_search_t *info_out);
+/* Queries are caller-supplied vectors, nq x D fp32 on the host (no query vertex, hence no flags). */
+F2V_API int f2v_index_search_vectors(f2v_handle h, const float *queries, uint32_t nq, uint32_t k, int metric, uint32_t nprobe, uint32_t *ids_out,
+                             float *scores_out, uint32_t *probes_out, f2v_index_search_t *info_out);
+
 /* ---- logistic regression -----------------------------------------------------------------------------------------------------
  * The other two scores the reference judges an embedding by: node-classification F1 (performancescores/runnodeclassclust.py:289-309)
  * and link-prediction accuracy / F1 (performancescores/runlinkpredict.py:127-140) are both an L2-regularised one-vs-rest logistic
