@@ -33,6 +33,10 @@ for each new vertex against the frozen matrix, all epochs in one launch (determi
 Link prediction: `Engine.link_pairs(ratio=2, seed=1)` builds the reference's pair set on the GPU (every edge once, twice as many
 non-neighbours per vertex, shuffled; deterministic, include/f2v.h) and `Engine.link_predict()` scores the embedding on it.
 
+Held-out link prediction: `Engine.edge_split(frac=0.2)` hides a share of the edges (and draws as many non-edges), an engine built on
+the returned training CSR is trained as usual, and its `heldout_scores(split)` ranks the hidden edges against the non-edges by the
+embedding's own similarity (`Engine.pair_scores`) -> ROC-AUC and average precision (`Engine.ranking`, sorted and tallied on the GPU).
+
 What the graph itself achieves: `Engine.communities()` finds the graph's communities with the Louvain method on the GPU (integers only:
 the same labels on every run; `details=True` adds their modularity, the yardstick for `modularity(kmeans(k).labels)`), and
 `Engine.agreement(a, b)` gives NMI and ARI of two labellings -- clusters against communities, either against ground truth."""
@@ -46,6 +50,7 @@ from ._lib import FOLD_INIT_GIVEN, FOLD_INIT_MEAN, FOLD_INIT_RANDOM  # noqa: F40
 from ._lib import LOGREG_BLOCK, LOGREG_MAX_CLASSES, PAIR_AVERAGE, PAIR_HADAMARD, PAIR_L1, PAIR_L2  # noqa: F401
 from ._lib import NEAREST_EXCLUDE_NEIGHBOURS, NEAREST_EXCLUDE_SELF, NEAREST_MAX_K, NEAREST_PAD_ID, SIM_COSINE, SIM_DOT, SIM_L2  # noqa: F401
 from .engine import FoldInfo, LinkInfo, Pca, Trust  # noqa: F401
+from .engine import EdgeSplit, HeldoutScores, Ranking, SplitInfo  # noqa: F401
 from .engine import Agreement, Communities, LouvainLevel  # noqa: F401
 from .engine import Engine, KMeans, LogregModel, Modularity, algorithms, output_name, push_masks, read_embd, read_embd_bin, sm_table, write_embd, write_embd_bin  # noqa: F401
 from .graph import read_csr_bin, read_mtx, rmat_csr, write_csr_bin  # noqa: F401

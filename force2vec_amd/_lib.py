@@ -89,6 +89,16 @@ class LinkInfo(C.Structure):  # f2v_link_t
     _fields_ = [("seconds", C.c_double), ("positives", C.c_uint64), ("negatives", C.c_uint64), ("candidates", C.c_uint64), ("capped", C.c_uint64)]
 
 
+class SplitInfo(C.Structure):  # f2v_split_t
+    _fields_ = [("seconds", C.c_double), ("edges", C.c_uint64), ("candidates_held", C.c_uint64), ("protected_edges", C.c_uint64), ("held", C.c_uint64),
+                ("train_nnz", C.c_uint64), ("negatives", C.c_uint64), ("drawn", C.c_uint64), ("capped", C.c_uint64)]
+
+
+class RankingInfo(C.Structure):  # f2v_ranking_t
+    _fields_ = [("auc", C.c_double), ("ap", C.c_double), ("concordant", C.c_uint64), ("tied", C.c_uint64), ("positives", C.c_uint64),
+                ("negatives", C.c_uint64), ("groups", C.c_uint64), ("seconds", C.c_double)]
+
+
 class LouvainLevel(C.Structure):  # f2v_louvain_level_t
     _fields_ = [("nodes", C.c_uint32), ("communities", C.c_uint32), ("sweeps", C.c_uint32), ("reserved", C.c_uint32), ("moves", C.c_uint64),
                 ("qnum", C.c_int64)]
@@ -161,6 +171,10 @@ SIGNATURES = {
     "f2v_tsne_kl_log": (C.c_int, [C.c_void_p, u32p, f64p, C.c_uint32, u32p]),
     "f2v_fold_in": (C.c_int, [C.c_void_p, C.c_int, u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_int, f32p, C.c_uint64, C.c_uint64, f32p, C.POINTER(FoldInfo)]),
     "f2v_link_pairs": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, u32p, u32p, u8p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(LinkInfo)]),
+    "f2v_edge_split": (C.c_int, [C.c_void_p, C.c_double, C.c_uint64, C.c_uint32, u32p, u32p, C.c_uint64, u32p, u32p, C.c_uint64, u32p, u32p, C.c_uint64,
+                                 C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(SplitInfo)]),
+    "f2v_pair_scores": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint64, C.c_int, f32p, C.POINTER(C.c_double)]),
+    "f2v_ranking": (C.c_int, [C.c_void_p, f64p, u8p, C.c_uint64, C.POINTER(RankingInfo)]),
     "f2v_louvain": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, u32p, u32p, C.POINTER(LouvainLevel), C.POINTER(LouvainInfo)]),
     "f2v_partition_agreement": (C.c_int, [C.c_void_p, u32p, C.c_uint32, u32p, C.c_uint32, C.POINTER(AgreementInfo)]),
     "f2v_push_export": (C.c_int, [C.c_void_p, C.c_void_p]),

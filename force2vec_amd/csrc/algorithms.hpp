@@ -9,6 +9,7 @@
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <fstream>
 #include <iostream>
 #include <sstream>
@@ -56,6 +57,40 @@ inline void SetInputMatricesAsCSR(CSRGraph &A, const std::string &inputfile, boo
     std::cout << "Input Matrix: Rows = " << A.rows << ", nnz = " << A.nnz << std::endl;
     if (use_cache && f2v_write_csr_bin(cache.c_str(), A.rowptr, A.colids, A.rows, A.nnz) != F2V_OK)
         std::cerr << "warning: " << f2v_last_error() << std::endl;
+}
+
+// -holdout <f>: the input graph split by f2v_edge_split(frac, seed, ratio) on `device` -- the training graph (the run's handle is
+// created on it), the hidden edges and as many non-edges of the full graph per vertex.  The split needs no embeddings: it runs on a
+// handle of its own, gone before the training handle is made.
+struct Holdout {
+    CSRGraph train;
+    std::vector<uint32_t> held_u, held_v, neg_u, neg_v;
+};
+inline void SplitForHoldout(const CSRGraph &A, double frac, uint32_t ratio, uint64_t seed, int device, Holdout &out) {
+    f2v_handle h = nullptr;
+    if (f2v_create(A.rowptr, A.colids, A.rows, A.nnz, 1, device, &h) != F2V_OK) throw std::runtime_error(f2v_last_error());
+    uint64_t nnz = 0, held = 0, neg = 0;
+    int rc = f2v_edge_split(h, frac, seed, ratio, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, &nnz, &held, &neg, nullptr);
+    if (rc == F2V_OK) {
+        out.train.rows = A.rows;
+        out.train.nnz = nnz;
+        out.train.rowptr = static_cast<INDEXTYPE *>(malloc(((size_t)A.rows + 1) * sizeof(INDEXTYPE)));
+        out.train.colids = static_cast<INDEXTYPE *>(malloc((nnz ? nnz : 1) * sizeof(INDEXTYPE)));
+        out.held_u.resize(held + 1);  // (+ 1: an empty vector has no array to name)
+        out.held_v.resize(held + 1);
+        out.neg_u.resize(neg + 1);
+        out.neg_v.resize(neg + 1);
+        rc = out.train.rowptr && out.train.colids
+                 ? f2v_edge_split(h, frac, seed, ratio, out.train.rowptr, out.train.colids, nnz ? nnz : 1, out.held_u.data(), out.held_v.data(), held + 1,
+                                  out.neg_u.data(), out.neg_v.data(), neg + 1, &nnz, &held, &neg, nullptr)
+                 : F2V_ENOMEM;
+        for (auto *a : {&out.held_u, &out.held_v}) a->resize(held);
+        for (auto *a : {&out.neg_u, &out.neg_v}) a->resize(neg);
+    }
+    const std::string why = rc == F2V_OK ? "" : rc == F2V_ENOMEM ? "out of memory" : f2v_last_error();
+    f2v_destroy(h);
+    if (rc != F2V_OK) throw std::runtime_error(why);
+    std::cout << "Holdout: " << held << " of the edges hidden, " << neg << " non-edges drawn, training graph nnz = " << nnz << std::endl;
 }
 
 class algorithms {
@@ -529,6 +564,51 @@ class algorithms {
         const LinkScores s{100.0 * (hits / (double)tests), 100.0 * (per / classes), 100.0 * (den > 0 ? 2 * tps / den : 0.0)};
         printf("Link predictions(%s): %g :Accuracy: %.17g F1-macro: %.17g F1-micro: %.17g\n", names[feature], frac, s.accuracy / 100.0, s.f1_macro / 100.0, s.f1_micro / 100.0);
         return s;
+    }
+
+    // -holdout <f>: held-out link prediction of the embedding this object trained on `split.train`.  Writes "<embd output name>.held",
+    // one line "u v y" per pair (1-based ids; the hidden edges, y = 1, then the non-edges, y = 0), ranks the pairs by the embedding's
+    // own similarity (f2v_pair_scores, f2v_ranking) and prints "Held-out link prediction(<metric>): <H> edges :AUC: <a> AP: <p>"; with
+    // `feature` >= 0 also by the decision values of a logistic regression fitted on every pair of f2v_link_pairs(ratio, seed) of the
+    // training graph, under the feature's name.  Computed as Engine.heldout_scores computes them.
+    struct HeldScores {
+        double auc, ap, classifier_auc, classifier_ap;
+    };
+    HeldScores heldOut(const Holdout &split, int metric, const char *metric_name, int feature, uint32_t ratio, uint64_t seed) {
+        static const char *const names[] = {"Hadamard", "L1", "L2", "Average"};
+        const size_t H = split.held_u.size(), m = H + split.neg_u.size();
+        std::vector<uint32_t> u(split.held_u), v(split.held_v);
+        u.insert(u.end(), split.neg_u.begin(), split.neg_u.end());
+        v.insert(v.end(), split.neg_v.begin(), split.neg_v.end());
+        std::vector<uint8_t> y(m, 0);
+        std::fill(y.begin(), y.begin() + H, (uint8_t)1);
+        const std::string name = last_output + ".held";
+        FILE *f = fopen(name.c_str(), "w");
+        if (!f) throw std::runtime_error("cannot write " + name);
+        for (size_t i = 0; i < m; i++) fprintf(f, "%u %u %u\n", u[i] + 1, v[i] + 1, (unsigned)y[i]);
+        if (fclose(f) != 0) throw std::runtime_error("cannot write " + name);
+        std::vector<float> s(m);
+        std::vector<double> z(m);
+        check(f2v_pair_scores(h, u.data(), v.data(), m, metric, s.data(), nullptr));
+        for (size_t i = 0; i < m; i++) z[i] = (double)s[i];
+        f2v_ranking_t own{}, clf{};
+        check(f2v_ranking(h, z.data(), y.data(), m, &own));
+        printf("Held-out link prediction(%s): %zu edges :AUC: %.17g AP: %.17g\n", metric_name, H, own.auc, own.ap);
+        if (feature >= 0) {
+            uint64_t M = 0;
+            check(f2v_link_pairs(h, ratio, seed, nullptr, nullptr, nullptr, 0, &M, nullptr));
+            if (M == 0 || M > 0xFFFFFFFFull || m > 0xFFFFFFFFull) throw std::runtime_error("-holdout with -linkpredict: no pair of the training graph to fit on, or more than 2^32 - 1");
+            std::vector<uint32_t> tu(M), tv(M);
+            std::vector<uint8_t> ty(M);
+            check(f2v_link_pairs(h, ratio, seed, tu.data(), tv.data(), ty.data(), M, &M, nullptr));
+            std::vector<double> W((size_t)DIM + 1);
+            f2v_logreg_t info{};
+            check(f2v_logreg_fit(h, tu.data(), tv.data(), (uint32_t)M, feature, ty.data(), 1, 1.0, 1e-4, 100, W.data(), &info));
+            check(f2v_logreg_decision(h, u.data(), v.data(), (uint32_t)m, feature, W.data(), 1, z.data(), nullptr));
+            check(f2v_ranking(h, z.data(), y.data(), m, &clf));
+            printf("Held-out link prediction(%s): %zu edges :AUC: %.17g AP: %.17g\n", names[feature], H, clf.auc, clf.ap);
+        }
+        return HeldScores{own.auc, own.ap, clf.auc, clf.ap};
     }
 
     // writeToFile, sample/algorithms.h:118-136 (file name rule in f2v_output_name)

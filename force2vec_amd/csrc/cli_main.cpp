@@ -20,7 +20,10 @@
 // -linkpredict <hadamard|l1|l2|average> [-linkpredict-frac <f>] [-linkpredict-ratio <r>] (after training, or on -init <file> with -iter 0:
 // the reference's link-prediction scores of the embedding on the pair set f2v_link_pairs builds from the graph),
 // -communities 1 [-communities-levels <L>] [-communities-seed <s>] (after training, or on -init <file> with -iter 0: the communities of the
-// graph itself as "<embd output name>.com", their modularity, and their agreement with the -cluster clusters and the ground truth).
+// graph itself as "<embd output name>.com", their modularity, and their agreement with the -cluster clusters and the ground truth),
+// -holdout <f> [-holdout-ratio <r>] [-holdout-metric dot|l2|cos] (held-out link prediction: a share of the edges is hidden BEFORE training,
+// the run trains on the rest -- the .embd is then the training graph's embedding -- and the hidden edges are ranked against non-edges:
+// "<embd output name>.held" and ROC-AUC / average precision; with -linkpredict also by the classifier's decision values).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -51,6 +54,9 @@ struct Settings {
     long communities = 0, communities_levels = 32, communities_seed = 1;
     long linkpredict_ratio = 2;
     double linkpredict_frac = 0.5;
+    double holdout = -1.0;  // not given
+    long holdout_ratio = 1;
+    std::string holdout_metric;
     long classify_splits = 10, separation_sample = 0, layout = 0, layout_neighbours = 5, layout_sample = 0;
     double gamma = 1.0, lr = 0.02, classify_frac = 0.1;
 };
@@ -144,6 +150,9 @@ int main(int argc, char *argv[]) {
         {"-communities-seed", Kind::Integer, &s.communities_seed, "<int>, non-negative: the seed of the -communities sub-round classes. (default:1)"},
         {"-linkpredict-frac", Kind::Real, &s.linkpredict_frac, "<float>, above 0 and below 1: the share of the pair set that trains the -linkpredict model. (default:0.5)"},
         {"-linkpredict-ratio", Kind::Integer, &s.linkpredict_ratio, "<int>, 1..16: negatives per positive of a vertex in the -linkpredict pair set. (default:2)"},
+        {"-holdout", Kind::Real, &s.holdout, "<float>, f in [0, 1): held-out link prediction. About that share of the edges is hidden before training (a hash of the pair seeded by -seed decides; every vertex keeps the edge of its lowest hash, so the share falls somewhat below f and no vertex loses all its neighbours; connectivity is not promised) and the run trains on the remaining graph: THE .embd IS THEN THE TRAINING GRAPH'S EMBEDDING, not the input graph's, and every other scorer flag of the run sees the training graph. Afterwards the hidden edges and -holdout-ratio times as many non-edges of the input graph per vertex are written to <output file>.held, one line \"u v y\" per pair (1-based ids, y = 1 for a hidden edge), ranked by the embedding's own similarity on the GPU, and \"Held-out link prediction(<metric>): <H> edges :AUC: <a> AP: <p>\" is printed (ROC-AUC with ties counted half, average precision); with -linkpredict <feature> the same line also for the decision values of the classifier, fitted on pairs of the training graph alone (one GPU; not with -foldin)."},
+        {"-holdout-ratio", Kind::Integer, &s.holdout_ratio, "<int>, 0..16: non-edges per hidden edge of a vertex in the -holdout test set. (default:1)"},
+        {"-holdout-metric", Kind::Text, &s.holdout_metric, "<string>, similarity that ranks the -holdout pairs: dot | l2 | cos. (default: l2 for options 1, 5, 8, 11, dot for the sigmoid options)"},
         {"-metric", Kind::Text, &s.metric, "<string>, similarity of -nearest: dot | l2 | cos. (default: l2 for options 5, 8, 11, dot for the sigmoid options)"},
     };
     const size_t nflags = sizeof flags / sizeof flags[0];
@@ -349,6 +358,29 @@ int main(int argc, char *argv[]) {
         printf("-communities is not available with -gpus > 1 (it runs on one GPU's copy of the graph).\n");
         return 1;
     }
+    const bool holdout = s.holdout != -1.0;
+    if (holdout && !(s.holdout >= 0.0 && s.holdout < 1.0)) {
+        printf("-holdout must be at least 0 and below 1.\n");
+        return 1;
+    }
+    if (holdout && (s.holdout_ratio < 0 || s.holdout_ratio > 16)) {
+        printf("-holdout-ratio must be 0..16.\n");
+        return 1;
+    }
+    if (s.holdout_metric.empty()) s.holdout_metric = (s.option == 1 || s.option == 5 || s.option == 8 || s.option == 11) ? "l2" : "dot";
+    const int holdout_metric = s.holdout_metric == "dot" ? F2V_SIM_DOT : s.holdout_metric == "l2" ? F2V_SIM_L2 : s.holdout_metric == "cos" ? F2V_SIM_COSINE : -1;
+    if (holdout && holdout_metric < 0) {
+        printf("-holdout-metric must be dot, l2 or cos.\n");
+        return 1;
+    }
+    if (holdout && s.gpus > 1) {
+        printf("-holdout is not available with -gpus > 1 (it splits and scores on one GPU).\n");
+        return 1;
+    }
+    if (holdout && !s.foldin.empty()) {
+        printf("-holdout is not available with -foldin (a new vertex's neighbours are edges of the input graph, which the run did not train on).\n");
+        return 1;
+    }
     std::vector<VALUETYPE> seconds;
     int rank = 0;
     std::string meet;  // directory the ranks of a -gpus run meet in
@@ -373,7 +405,9 @@ int main(int argc, char *argv[]) {
         }
         int rc_mine = 0;
         try {
-            algorithms algo(graph, s.input, s.output, (INDEXTYPE)s.dim, (VALUETYPE)s.gamma, (INDEXTYPE)s.batch, (int)s.device + (s.samegpu ? 0 : rank));
+            Holdout split;
+            if (holdout) SplitForHoldout(graph, s.holdout, (uint32_t)s.holdout_ratio, (uint64_t)s.seed, (int)s.device, split);
+            algorithms algo(holdout ? split.train : graph, s.input, s.output, (INDEXTYPE)s.dim, (VALUETYPE)s.gamma, (INDEXTYPE)s.batch, (int)s.device + (s.samegpu ? 0 : rank));
             algo.binary_output = s.binout != 0;
             algo.text_output = s.notext == 0;
             algo.init_path = s.init;
@@ -401,6 +435,8 @@ int main(int argc, char *argv[]) {
                 algo.layout((uint32_t)s.layout, (uint32_t)s.layout_neighbours, (uint32_t)s.layout_sample, (uint64_t)s.seed, tsne, s.layout_perplexity, (uint32_t)s.layout_iters);
             if (!s.foldin.empty() && rank == 0) algo.foldIn(s.foldin, (int)s.option, (uint32_t)s.foldin_iters, (INDEXTYPE)s.nsamples, (VALUETYPE)s.lr, foldin_init, (uint64_t)s.seed);
             if (!s.linkpredict.empty() && rank == 0) algo.linkPredict(linkpredict_feature, s.linkpredict_frac, (uint32_t)s.linkpredict_ratio, (uint64_t)s.seed);
+            if (holdout && rank == 0)
+                algo.heldOut(split, holdout_metric, s.holdout_metric.c_str(), s.linkpredict.empty() ? -1 : linkpredict_feature, (uint32_t)s.linkpredict_ratio, (uint64_t)s.seed);
             if (s.communities && rank == 0)
                 algo.writeCommunities((uint32_t)s.communities_levels, (uint64_t)s.communities_seed,
                                       !s.separation.empty() && s.separation != "kmeans" ? s.separation : s.classify);

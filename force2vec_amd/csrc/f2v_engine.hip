@@ -8,6 +8,7 @@
 //   sample ids u32, walks u32 [5N], sigmoid table fp32 [2048]
 // The host side only sequences launches; every arithmetic step runs in f2v_kernels.hip.h.
 #include <hip/hip_runtime.h>
+#include <rocprim/device/device_radix_sort.hpp>  // f2v_ranking sorts its keys with it
 
 #include <algorithm>
 #include <chrono>
@@ -41,6 +42,7 @@
 #include "f2v_exact.hip.h"
 #include "f2v_foldin.hip.h"
 #include "f2v_linkpairs.hip.h"
+#include "f2v_heldout.hip.h"
 #include "f2v_louvain.hip.h"
 #include "f2v_tsne.hip.h"
 
@@ -314,6 +316,21 @@ struct f2v_ctx {
         DevTimer timer;
         uint32_t short_max = 256;
     } link;
+    // held-out link prediction (f2v_edge_split, f2v_pair_scores, f2v_ranking): the workspace f2v.h states, allocated on first use and
+    // grown for a larger call; "pairs_chunk": pairs per upload and launch of f2v_pair_scores -- placement only
+    struct Heldout {
+        DevBuf<uint32_t> d_anchor, d_kept, d_q, d_total, d_zero, d_order, d_table, d_rowptr, d_colids, d_hu, d_hv, d_nu, d_nv;
+        DevBuf<uint8_t> d_ny;
+        DevBuf<unsigned long long> d_kept_at, d_held_at, d_neg_at, d_tile, d_sums, d_table_at;
+        DevBuf<uint32_t> d_pu, d_pv;   // f2v_pair_scores: one chunk's ids
+        DevBuf<float> d_ps;            // ... and scores
+        DevBuf<double> d_scores, d_terms, d_blocks;  // f2v_ranking
+        DevBuf<unsigned long long> d_keys[2], d_tallies;
+        DevBuf<uint8_t> d_labels[2], d_sort;
+        DevBuf<uint32_t> d_cum;
+        DevTimer timer;
+        uint32_t pairs_chunk = 1u << 20;
+    } held;
     // communities (f2v_louvain, f2v_partition_agreement): the workspace f2v.h states, allocated on first use and grown for a larger call;
     // "louvain_short_max": the longest row of a unit that 16 lanes gather, "louvain_lds_slots": the largest table kept in LDS --
     // placement only.  rows_symmetric: -1 not checked yet (checked once per handle, on the device)
@@ -2339,6 +2356,8 @@ const Param kParams[] = {
     {"fold_resident", F2V_FIELD(fold.resident), kValue, kKeep, in<-1, 0>, "fold_resident must be -1 (automatic) or 0: the resident form measured slower and is not part of this build"},
     // f2v_link_pairs: a vertex with at most this many negatives is one wavefront's (its accepted set a list in LDS), a longer one a workgroup's (a table); placement only
     {"link_short_max", F2V_FIELD(link.short_max), kValue, kKeep, in<0, kLinkShortLimit>, "link_short_max must be 0..1024"},
+    // f2v_pair_scores: pairs per upload and launch: bounds its workspace (12 bytes a pair); results do not depend on it
+    {"pairs_chunk", F2V_FIELD(held.pairs_chunk), kValue, kKeep, in<1, 1 << 26>, "pairs_chunk must be 1..67108864"},
     // f2v_louvain: a unit whose rows hold at most this many nonzeros is gathered by 16 lanes (table in LDS), a longer one by a workgroup; placement only
     {"louvain_short_max", F2V_FIELD(lv.short_max), kValue, kKeep, in<0, kLouvainShortLimit>, "louvain_short_max must be 0..256"},
     // f2v_louvain: the largest table (slots) a workgroup keeps in LDS; a longer one lies in the workspace; placement only
@@ -4667,6 +4686,83 @@ int f2v_fold_in(f2v_handle c, int option, const uint32_t *q_rowptr, const uint32
 }  // extern "C"
 
 // ---- link prediction pairs (f2v_linkpairs.hip.h; definition in include/f2v.h) ---------------------------------------------------
+namespace {
+
+// Which vertices draw negatives, and how: by descending total(u), ties in id order -- the first `nw` with tables in the workspace, up
+// to `nl` a workgroup each, the others a wavefront each.  Shared by f2v_link_pairs and f2v_edge_split, each with buffers of its own.
+struct LinkPlan {
+    std::vector<uint32_t> order;
+    uint32_t nw = 0, nl = 0;
+};
+
+// placement (a counting sort: total(u) < n / 2); the order and the workspace tables go to the device, a.keys / table_words / table_at are set
+int link_place(f2v_ctx *c, const char *who, const char *what, const std::vector<uint32_t> &total, uint32_t short_max, DevBuf<uint32_t> &d_order,
+               DevBuf<unsigned long long> &d_table_at, DevBuf<uint32_t> &d_table, LinkArgs &a, LinkPlan &pl) {
+    const uint32_t n = c->n;
+    uint32_t most = 0;
+    for (uint32_t v = 0; v < n; v++) most = std::max(most, total[v]);
+    if (most > (1u << 29)) return fail(F2V_EINVAL, "%s: a vertex with more than 2^29 negatives", who);
+    std::vector<uint32_t> first((size_t)most + 2, 0), &order = pl.order;
+    for (uint32_t v = 0; v < n; v++)
+        if (total[v]) first[most - total[v] + 1]++;
+    for (uint32_t k = 0; k <= most; k++) first[k + 1] += first[k];
+    order.resize(first[(size_t)most + 1]);
+    for (uint32_t v = 0; v < n; v++)
+        if (total[v]) order[first[most - total[v]]++] = v;
+    const uint32_t cnt = (uint32_t)order.size();
+    uint32_t nw = 0, nl = 0;
+    std::vector<unsigned long long> table_at;
+    uint64_t words = 0;
+    while (nl < cnt && total[order[nl]] > short_max) nl++;
+    while (nw < nl && link_slots(total[order[nw]]) > kLinkLdsSlots) {
+        table_at.push_back(words);
+        words += link_slots(total[order[nw++]]);
+    }
+    pl.nw = nw;
+    pl.nl = nl;
+    F2VC(d_order.reserve(c, cnt, what));
+    F2VC(d_table_at.reserve(c, nw, what));
+    F2VC(d_table.reserve(c, 2 * words, what));
+    if (cnt) HIPC(hipMemcpyAsync(d_order, order.data(), (size_t)cnt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (nw) {
+        HIPC(hipMemcpyAsync(d_table_at, table_at.data(), (size_t)nw * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
+        HIPC(hipMemsetAsync(d_table, 0xFF, 2 * words * sizeof(uint32_t), c->stream));  // kLinkEmpty
+    }
+    a.keys = d_table;
+    a.table_words = words;
+    a.table_at = d_table_at;
+    return F2V_OK;
+}
+
+// the launches that draw: every negative goes straight to its place in a.u_out / v_out / y_out
+int link_draw(f2v_ctx *c, const std::vector<uint32_t> &total, const LinkPlan &pl, const uint32_t *d_order, LinkArgs &a) {
+    const std::vector<uint32_t> &order = pl.order;
+    const uint32_t cnt = (uint32_t)order.size(), nw = pl.nw, nl = pl.nl;
+    // link_long_kernel: the wavefronts' counts of two rounds, in front of an LDS table
+    const size_t counts_bytes = 2 * (kLinkLongThreads / 64) * sizeof(uint32_t), wide_counts_bytes = 2 * (kLinkWideThreads / 64) * sizeof(uint32_t);
+    if (nw) {  // the longest lists first: their workgroups run longest
+        a.order = d_order;
+        hipLaunchKernelGGL(link_long_kernel<true>, dim3(nw), dim3(kLinkWideThreads), wide_counts_bytes, c->stream, a);
+    }
+    for (uint32_t i = nw, j; i < nl; i = j) {  // one launch per table size
+        a.slots = (uint32_t)link_slots(total[order[i]]);
+        for (j = i + 1; j < nl && j - i < (1u << 30) && link_slots(total[order[j]]) == a.slots; j++) {}
+        const size_t lds = counts_bytes + 2 * (size_t)a.slots * sizeof(uint32_t);
+        F2VC(allow_lds(c, reinterpret_cast<const void *>(&link_long_kernel<false>), lds));
+        a.order = d_order + i;
+        hipLaunchKernelGGL(link_long_kernel<false>, dim3(j - i), dim3(kLinkLongThreads), lds, c->stream, a);
+    }
+    if (nl < cnt) {
+        a.order = d_order + nl;
+        a.count = cnt - nl;
+        a.short_max = total[order[nl]];  // the longest list of the launch
+        hipLaunchKernelGGL(link_short_kernel, dim3(std::min((a.count + 3) / 4, 16384u)), dim3(256), 4 * (size_t)a.short_max * sizeof(uint32_t), c->stream, a);
+    }
+    return F2V_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int f2v_link_pairs(f2v_handle c, uint32_t ratio, uint64_t seed, uint32_t *u_out, uint32_t *v_out, uint8_t *y_out, uint64_t cap, uint64_t *count_out,
@@ -4728,70 +4824,21 @@ int f2v_link_pairs(f2v_handle c, uint32_t ratio, uint64_t seed, uint32_t *u_out,
     if (fill && cap < M) return fail(F2V_EINVAL, "f2v_link_pairs: the set has %llu pairs, the arrays hold %llu", (unsigned long long)M, (unsigned long long)cap);
     if (!fill || M == 0) return F2V_OK;
 
-    // placement: the vertices that draw negatives by descending total(u), ties in id order (a counting sort: total(u) < n / 2) -- the
-    // first `nw` of them with tables in the workspace, up to `nl` a workgroup each, the others a wavefront each
-    uint32_t most = 0;
-    for (uint32_t v = 0; v < n; v++) most = std::max(most, total[v]);
-    if (most > (1u << 29)) return fail(F2V_EINVAL, "f2v_link_pairs: a vertex with more than 2^29 negatives");
-    std::vector<uint32_t> first((size_t)most + 2, 0), order;
-    for (uint32_t v = 0; v < n; v++)
-        if (total[v]) first[most - total[v] + 1]++;
-    for (uint32_t k = 0; k <= most; k++) first[k + 1] += first[k];
-    order.resize(first[(size_t)most + 1]);
-    for (uint32_t v = 0; v < n; v++)
-        if (total[v]) order[first[most - total[v]]++] = v;
-    const uint32_t cnt = (uint32_t)order.size();
-    uint32_t nw = 0, nl = 0;
-    std::vector<unsigned long long> table_at;
-    uint64_t words = 0;
-    while (nl < cnt && total[order[nl]] > w.short_max) nl++;
-    while (nw < nl && link_slots(total[order[nw]]) > kLinkLdsSlots) {
-        table_at.push_back(words);
-        words += link_slots(total[order[nw++]]);
-    }
-    F2VC(w.d_order.reserve(c, cnt, what));
-    F2VC(w.d_table_at.reserve(c, nw, what));
-    F2VC(w.d_table.reserve(c, 2 * words, what));
+    LinkPlan plan;
+    F2VC(link_place(c, "f2v_link_pairs", what, total, w.short_max, w.d_order, w.d_table_at, w.d_table, a, plan));
     F2VC(w.d_u.reserve(c, M, what));
     F2VC(w.d_v.reserve(c, M, what));
     F2VC(w.d_y.reserve(c, M, what));
-    if (cnt) HIPC(hipMemcpyAsync(w.d_order, order.data(), (size_t)cnt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    if (nw) {
-        HIPC(hipMemcpyAsync(w.d_table_at, table_at.data(), (size_t)nw * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
-        HIPC(hipMemsetAsync(w.d_table, 0xFF, 2 * words * sizeof(uint32_t), c->stream));  // kLinkEmpty
-    }
     a.u_out = w.d_u;
     a.v_out = w.d_v;
     a.y_out = w.d_y;
-    a.keys = w.d_table;
-    a.table_words = words;
-    a.table_at = w.d_table_at;
     a.M = M;
     uint32_t bits = 2;
     while (bits < 64 && ((uint64_t)1 << bits) < M) bits += 2;
     a.half = bits / 2;
     a.mask = ((uint64_t)1 << a.half) - 1;
-    // link_long_kernel: the wavefronts' counts of two rounds, in front of an LDS table
-    const size_t counts_bytes = 2 * (kLinkLongThreads / 64) * sizeof(uint32_t), wide_counts_bytes = 2 * (kLinkWideThreads / 64) * sizeof(uint32_t);
     F2VC(w.timer.start(c->stream));
-    if (nw) {  // the longest lists first: their workgroups run longest
-        a.order = w.d_order;
-        hipLaunchKernelGGL(link_long_kernel<true>, dim3(nw), dim3(kLinkWideThreads), wide_counts_bytes, c->stream, a);
-    }
-    for (uint32_t i = nw, j; i < nl; i = j) {  // one launch per table size
-        a.slots = (uint32_t)link_slots(total[order[i]]);
-        for (j = i + 1; j < nl && j - i < (1u << 30) && link_slots(total[order[j]]) == a.slots; j++) {}
-        const size_t lds = counts_bytes + 2 * (size_t)a.slots * sizeof(uint32_t);
-        F2VC(allow_lds(c, reinterpret_cast<const void *>(&link_long_kernel<false>), lds));
-        a.order = w.d_order + i;
-        hipLaunchKernelGGL(link_long_kernel<false>, dim3(j - i), dim3(kLinkLongThreads), lds, c->stream, a);
-    }
-    if (nl < cnt) {
-        a.order = w.d_order + nl;
-        a.count = cnt - nl;
-        a.short_max = total[order[nl]];  // the longest list of the launch
-        hipLaunchKernelGGL(link_short_kernel, dim3(std::min((a.count + 3) / 4, 16384u)), dim3(256), 4 * (size_t)a.short_max * sizeof(uint32_t), c->stream, a);
-    }
+    F2VC(link_draw(c, total, plan, w.d_order, a));
     hipLaunchKernelGGL(link_positive_kernel, dim3(rows), dim3(256), 0, c->stream, a);
     HIPC(hipGetLastError());
     F2VC(w.timer.stop(c->stream));
@@ -4805,6 +4852,279 @@ int f2v_link_pairs(f2v_handle c, uint32_t ratio, uint64_t seed, uint32_t *u_out,
         info->seconds = seconds;
         info->candidates = sums[3];
     }
+    return F2V_OK;
+}
+
+}  // extern "C"
+
+// ---- held-out link prediction (f2v_heldout.hip.h; definition in include/f2v.h) ---------------------------------------------------
+extern "C" {
+
+int f2v_edge_split(f2v_handle c, double frac, uint64_t seed, uint32_t ratio, uint32_t *rowptr_train, uint32_t *colids_train, uint64_t cap_train,
+                   uint32_t *held_u, uint32_t *held_v, uint64_t cap_held, uint32_t *neg_u, uint32_t *neg_v, uint64_t cap_neg, uint64_t *train_nnz_out,
+                   uint64_t *held_out, uint64_t *negatives_out, f2v_split_t *info) {
+    if (!c || !train_nnz_out || !held_out || !negatives_out) return fail(F2V_EINVAL, "f2v_edge_split: null argument");
+    const int given = (rowptr_train != nullptr) + (colids_train != nullptr) + (held_u != nullptr) + (held_v != nullptr) + (neg_u != nullptr) + (neg_v != nullptr);
+    if (given != 0 && given != 6) return fail(F2V_EINVAL, "f2v_edge_split: the six output arrays are given together or not at all");
+    const bool fill = given == 6;
+    if (!(frac >= 0.0 && frac < 1.0)) return fail(F2V_EINVAL, "f2v_edge_split: frac = %g is outside [0, 1)", frac);
+    if (ratio > 16) return fail(F2V_EINVAL, "f2v_edge_split: ratio = %u is outside 0..16", ratio);
+    if (!rows_ascending(c)) return fail(F2V_EINVAL, "f2v_edge_split: the CSR's column ids are not ascending inside every row (needed to search a row)");
+    HIPC(hipSetDevice(c->device));
+    *train_nnz_out = *held_out = *negatives_out = 0;
+    if (info) *info = f2v_split_t{};
+    const uint32_t n = c->n;
+    if (n == 0) return F2V_OK;
+
+    f2v_ctx::Heldout &w = c->held;
+    const char *what = "edge split";
+    const uint32_t tiles = (uint32_t)(((uint64_t)n + kLinkScanTile - 1) / kLinkScanTile), rows = std::min((n + 3) / 4, 8192u);
+    F2VC(w.d_anchor.reserve(c, n, what));
+    F2VC(w.d_kept.reserve(c, n, what));
+    F2VC(w.d_q.reserve(c, n, what));
+    F2VC(w.d_total.reserve(c, n, what));
+    F2VC(w.d_zero.reserve(c, n, what));
+    F2VC(w.d_kept_at.reserve(c, n, what));
+    F2VC(w.d_held_at.reserve(c, n, what));
+    F2VC(w.d_neg_at.reserve(c, n, what));
+    F2VC(w.d_tile.reserve(c, tiles, what));
+    F2VC(w.d_sums.reserve(c, 12, what));  // [0..5] held_count_kernel's, [8..11] the link kernels' ([11]: candidates drawn)
+    const uint64_t s1 = mix64_host(seed);
+    HeldArgs a{};
+    a.rowptr = c->d_rowptr;
+    a.colids = c->d_colids;
+    a.anchor = w.d_anchor;
+    a.kept = w.d_kept;
+    a.q = w.d_q;
+    a.total = w.d_total;
+    a.kept_at = w.d_kept_at;
+    a.held_at = w.d_held_at;
+    a.sums = w.d_sums;
+    a.se = mix64_host(s1 ^ 0x65646765ull);
+    a.T = (uint64_t)(frac * 18446744073709551616.0);  // exact product, truncating conversion
+    a.n = n;
+    a.ratio = ratio;
+    LinkArgs l{};  // the scans and the negative draws of f2v_linkpairs.hip.h
+    l.rowptr = c->d_rowptr;
+    l.colids = c->d_colids;
+    l.tile = w.d_tile;
+    l.sums = w.d_sums + 8;
+    l.n = n;
+    l.ratio = ratio;
+    l.s1 = mix64_host(s1 ^ 0x6e656773ull);  // SN
+    l.M = ~0ull;  // half = 0, mask = 0: link_perm is the identity
+    HIPC(hipMemsetAsync(w.d_sums, 0, 12 * sizeof(unsigned long long), c->stream));
+    HIPC(hipMemsetAsync(w.d_zero, 0, (size_t)n * sizeof(uint32_t), c->stream));
+    auto scan = [&](uint32_t *p, uint32_t *total, unsigned long long *offset) {
+        l.p = p;
+        l.total = total;
+        l.offset = offset;
+        hipLaunchKernelGGL(link_scan_tile_kernel, dim3(tiles), dim3(256), 0, c->stream, l);
+        hipLaunchKernelGGL(link_scan_top_kernel, dim3(1), dim3(256), 0, c->stream, l, tiles);
+        hipLaunchKernelGGL(link_scan_apply_kernel, dim3(tiles), dim3(256), 0, c->stream, l);
+    };
+    double seconds = 0.0;
+    F2VC(w.timer.start(c->stream));
+    hipLaunchKernelGGL(held_anchor_kernel, dim3(rows), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(held_count_kernel, dim3(rows), dim3(256), 0, c->stream, a);
+    scan(w.d_kept, w.d_zero, w.d_kept_at);
+    scan(w.d_q, w.d_zero, w.d_held_at);
+    scan(w.d_zero, w.d_total, w.d_neg_at);
+    HIPC(hipGetLastError());
+    F2VC(w.timer.stop(c->stream));
+    unsigned long long sums[12];
+    HIPC(hipMemcpyAsync(sums, w.d_sums, sizeof sums, hipMemcpyDeviceToHost, c->stream));
+    std::vector<uint32_t> total(fill ? n : 0);
+    if (fill) HIPC(hipMemcpyAsync(total.data(), w.d_total, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    F2VC(w.timer.seconds(&seconds));
+    const uint64_t H = sums[2], nnz_train = sums[3], negs = sums[4];
+    *train_nnz_out = nnz_train;
+    *held_out = H;
+    *negatives_out = negs;
+    if (info) {
+        info->seconds = seconds;
+        info->edges = sums[0];
+        info->candidates_held = sums[1];
+        info->protected_edges = sums[1] - sums[2];
+        info->held = H;
+        info->train_nnz = nnz_train;
+        info->negatives = negs;
+        info->capped = sums[5];
+    }
+    if (fill && (cap_train < nnz_train || cap_held < H || cap_neg < negs))
+        return fail(F2V_EINVAL, "f2v_edge_split: %llu training nonzeros, %llu held pairs and %llu negatives; the arrays hold %llu, %llu and %llu",
+                    (unsigned long long)nnz_train, (unsigned long long)H, (unsigned long long)negs, (unsigned long long)cap_train, (unsigned long long)cap_held,
+                    (unsigned long long)cap_neg);
+    if (!fill) return F2V_OK;
+
+    F2VC(w.d_rowptr.reserve(c, (size_t)n + 1, what));
+    F2VC(w.d_colids.reserve(c, nnz_train, what));
+    F2VC(w.d_hu.reserve(c, H, what));
+    F2VC(w.d_hv.reserve(c, H, what));
+    F2VC(w.d_nu.reserve(c, negs, what));
+    F2VC(w.d_nv.reserve(c, negs, what));
+    F2VC(w.d_ny.reserve(c, negs, what));
+    a.rowptr_out = w.d_rowptr;
+    a.colids_out = w.d_colids;
+    a.held_u = w.d_hu;
+    a.held_v = w.d_hv;
+    LinkPlan plan;
+    if (negs) {
+        F2VC(link_place(c, "f2v_edge_split", what, total, c->link.short_max, w.d_order, w.d_table_at, w.d_table, l, plan));
+        l.p = w.d_zero;
+        l.total = w.d_total;
+        l.offset = w.d_neg_at;
+        l.u_out = w.d_nu;
+        l.v_out = w.d_nv;
+        l.y_out = w.d_ny;
+    }
+    F2VC(w.timer.start(c->stream));
+    hipLaunchKernelGGL(held_fill_kernel, dim3(rows), dim3(256), 0, c->stream, a);
+    if (negs) F2VC(link_draw(c, total, plan, w.d_order, l));
+    HIPC(hipGetLastError());
+    F2VC(w.timer.stop(c->stream));
+    HIPC(hipMemcpyAsync(rowptr_train, w.d_rowptr, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (nnz_train) HIPC(hipMemcpyAsync(colids_train, w.d_colids, nnz_train * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (H) {
+        HIPC(hipMemcpyAsync(held_u, w.d_hu, H * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipMemcpyAsync(held_v, w.d_hv, H * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (negs) {
+        HIPC(hipMemcpyAsync(neg_u, w.d_nu, negs * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipMemcpyAsync(neg_v, w.d_nv, negs * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPC(hipMemcpyAsync(sums, w.d_sums, sizeof sums, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    F2VC(w.timer.seconds(&seconds));
+    rowptr_train[n] = (uint32_t)nnz_train;
+    if (info) {
+        info->seconds = seconds;
+        info->drawn = sums[11];
+    }
+    return F2V_OK;
+}
+
+int f2v_pair_scores(f2v_handle c, const uint32_t *u_ids, const uint32_t *v_ids, uint64_t m, int metric, float *scores_out, double *seconds_out) {
+    if (!c) return fail(F2V_EINVAL, "f2v_pair_scores: null argument");
+    if (metric != F2V_SIM_DOT && metric != F2V_SIM_L2 && metric != F2V_SIM_COSINE) return fail(F2V_EINVAL, "f2v_pair_scores: unknown metric %d", metric);
+    if (seconds_out) *seconds_out = 0.0;
+    if (m == 0 && c->have_x) return F2V_OK;
+    if (m && (!u_ids || !v_ids || !scores_out)) return fail(F2V_EINVAL, "f2v_pair_scores: null argument");
+    for (uint64_t i = 0; i < m; i++)
+        if (u_ids[i] >= c->n || v_ids[i] >= c->n)
+            return fail(F2V_EINVAL, "f2v_pair_scores: pair %llu = (%u, %u) names a vertex that is not one of the %u", (unsigned long long)i, u_ids[i], v_ids[i], c->n);
+    F2VC(settled_enter(c, "f2v_pair_scores"));
+    if (m == 0) return F2V_OK;
+
+    f2v_ctx::Heldout &w = c->held;
+    const char *what = "pair scores";
+    const uint64_t chunk = std::min<uint64_t>(w.pairs_chunk, m);
+    F2VC(w.d_pu.reserve(c, chunk, what));
+    F2VC(w.d_pv.reserve(c, chunk, what));
+    F2VC(w.d_ps.reserve(c, chunk, what));
+    PairArgs a{};
+    a.X = c->d_X[c->cur];
+    a.u = w.d_pu;
+    a.v = w.d_pv;
+    a.out = w.d_ps;
+    a.D = c->D;
+    double seconds = 0.0;
+    for (uint64_t i0 = 0; i0 < m; i0 += chunk) {
+        const uint32_t cm = (uint32_t)std::min<uint64_t>(chunk, m - i0);
+        a.m = cm;
+        HIPC(hipMemcpyAsync(w.d_pu, u_ids + i0, (size_t)cm * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIPC(hipMemcpyAsync(w.d_pv, v_ids + i0, (size_t)cm * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        const dim3 grid(std::min((cm + 63u) / 64u, 65536u));
+        F2VC(w.timer.start(c->stream));
+        if (metric == F2V_SIM_DOT) hipLaunchKernelGGL(pair_score_kernel<F2V_SIM_DOT>, grid, dim3(64), 0, c->stream, a);
+        else if (metric == F2V_SIM_L2) hipLaunchKernelGGL(pair_score_kernel<F2V_SIM_L2>, grid, dim3(64), 0, c->stream, a);
+        else hipLaunchKernelGGL(pair_score_kernel<F2V_SIM_COSINE>, grid, dim3(64), 0, c->stream, a);
+        HIPC(hipGetLastError());
+        F2VC(w.timer.stop(c->stream));
+        HIPC(hipMemcpyAsync(scores_out + i0, w.d_ps, (size_t)cm * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+        F2VC(w.timer.seconds(&seconds));
+    }
+    if (seconds_out) *seconds_out = seconds;
+    return F2V_OK;
+}
+
+int f2v_ranking(f2v_handle c, const double *scores, const uint8_t *y, uint64_t m, f2v_ranking_t *out) {
+    if (!c || !out || (m && (!scores || !y))) return fail(F2V_EINVAL, "f2v_ranking: null argument");
+    if (m >= (1ull << 31)) return fail(F2V_EINVAL, "f2v_ranking: m = %llu reaches 2^31", (unsigned long long)m);
+    *out = f2v_ranking_t{};
+    uint64_t P = 0;
+    for (uint64_t i = 0; i < m; i++) {
+        if (y[i] > 1) return fail(F2V_EINVAL, "f2v_ranking: y[%llu] = %u is neither 0 nor 1", (unsigned long long)i, (unsigned)y[i]);
+        P += y[i];
+    }
+    const uint64_t N = m - P;
+    out->positives = P;
+    out->negatives = N;
+    if (P == 0 || N == 0) return fail(F2V_EINVAL, "f2v_ranking: %llu ones and %llu zeros: both classes are needed", (unsigned long long)P, (unsigned long long)N);
+    HIPC(hipSetDevice(c->device));
+
+    f2v_ctx::Heldout &w = c->held;
+    const char *what = "ranking";
+    const uint32_t mm = (uint32_t)m, tiles = (mm + kLinkScanTile - 1) / kLinkScanTile, blocks = (mm + kRankBlock - 1) / kRankBlock;
+    F2VC(w.d_scores.reserve(c, m, what));
+    F2VC(w.d_keys[0].reserve(c, m, what));
+    F2VC(w.d_keys[1].reserve(c, m, what));
+    F2VC(w.d_labels[0].reserve(c, m, what));
+    F2VC(w.d_labels[1].reserve(c, m, what));
+    F2VC(w.d_cum.reserve(c, m, what));
+    F2VC(w.d_terms.reserve(c, m, what));
+    F2VC(w.d_blocks.reserve(c, (size_t)blocks + 1, what));  // the last word: the sum of the block sums
+    F2VC(w.d_tile.reserve(c, tiles, what));
+    F2VC(w.d_tallies.reserve(c, 3, what));
+    size_t sort_bytes = 0;
+    HIPC(rocprim::radix_sort_pairs(nullptr, sort_bytes, (unsigned long long *)w.d_keys[0], (unsigned long long *)w.d_keys[1], (uint8_t *)w.d_labels[0],
+                                   (uint8_t *)w.d_labels[1], (size_t)mm, 0u, 64u, c->stream));
+    F2VC(w.d_sort.reserve(c, sort_bytes, what));
+    HIPC(hipMemcpyAsync(w.d_scores, scores, m * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemcpyAsync(w.d_labels[0], y, m * sizeof(uint8_t), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemsetAsync(w.d_tallies, 0, 3 * sizeof(unsigned long long), c->stream));
+    RankArgs a{};
+    a.scores = w.d_scores;
+    a.keys = w.d_keys[0];
+    a.cum = w.d_cum;
+    a.tile = w.d_tile;
+    a.terms = w.d_terms;
+    a.blocks = w.d_blocks;
+    a.ap_sum = w.d_blocks + blocks;
+    a.tallies = w.d_tallies;
+    a.negatives = N;
+    a.m = mm;
+    LinkArgs l{};  // link_scan_top_kernel reads its tile sums alone
+    l.tile = w.d_tile;
+    const dim3 grid(std::min((mm + 255u) / 256u, 65536u));
+    F2VC(w.timer.start(c->stream));
+    hipLaunchKernelGGL(rank_key_kernel, grid, dim3(256), 0, c->stream, a);
+    HIPC(rocprim::radix_sort_pairs((void *)(uint8_t *)w.d_sort, sort_bytes, (unsigned long long *)w.d_keys[0], (unsigned long long *)w.d_keys[1],
+                                   (uint8_t *)w.d_labels[0], (uint8_t *)w.d_labels[1], (size_t)mm, 0u, 64u, c->stream));
+    a.keys = w.d_keys[1];
+    a.labels = w.d_labels[1];
+    hipLaunchKernelGGL(rank_scan_tile_kernel, dim3(tiles), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(link_scan_top_kernel, dim3(1), dim3(256), 0, c->stream, l, tiles);
+    hipLaunchKernelGGL(rank_scan_apply_kernel, dim3(tiles), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(rank_group_kernel, grid, dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(rank_block_kernel, dim3((blocks + 63u) / 64u), dim3(64), 0, c->stream, a, blocks);
+    hipLaunchKernelGGL(rank_total_kernel, dim3(1), dim3(64), 0, c->stream, a, blocks);
+    HIPC(hipGetLastError());
+    F2VC(w.timer.stop(c->stream));
+    unsigned long long tallies[3];
+    double sum = 0.0, seconds = 0.0;
+    HIPC(hipMemcpyAsync(tallies, w.d_tallies, sizeof tallies, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipMemcpyAsync(&sum, w.d_blocks + blocks, sizeof sum, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    F2VC(w.timer.seconds(&seconds));
+    out->concordant = tallies[0];
+    out->tied = tallies[1];
+    out->groups = tallies[2];
+    out->auc = (double)(2 * out->concordant + out->tied) / (2.0 * (double)P * (double)N);
+    out->ap = sum / (double)P;
+    out->seconds = seconds;
     return F2V_OK;
 }
 

@@ -39,6 +39,11 @@ FOLD_INITS = {"mean": _lib.FOLD_INIT_MEAN, "random": _lib.FOLD_INIT_RANDOM}
 
 # Engine.link_pairs (include/f2v.h: link prediction pairs)
 LinkInfo = namedtuple("LinkInfo", "seconds positives negatives candidates capped")
+EdgeSplit = namedtuple("EdgeSplit", "rowptr colids held_u held_v neg_u neg_v")
+EdgeSplitDetails = namedtuple("EdgeSplitDetails", "rowptr colids held_u held_v neg_u neg_v info")
+SplitInfo = namedtuple("SplitInfo", "seconds edges candidates_held protected held train_nnz negatives drawn capped")
+Ranking = namedtuple("Ranking", "auc ap concordant tied positives negatives groups seconds")
+HeldoutScores = namedtuple("HeldoutScores", "auc ap classifier_auc classifier_ap")
 # Engine.communities, Engine.agreement (include/f2v.h: communities)
 Communities = namedtuple("Communities", "modularity communities levels edges seconds level_records level_labels")
 LouvainLevel = namedtuple("LouvainLevel", "nodes communities sweeps moves qnum")
@@ -689,6 +694,69 @@ class Engine:
             seconds += info.seconds
         self.last_link_seconds = seconds
         return (u, v, y, LinkInfo(seconds, info.positives, info.negatives, info.candidates, info.capped)) if details else (u, v, y)
+
+    # -- held-out link prediction (include/f2v.h: definition) --
+    def edge_split(self, frac=0.2, seed=1, ratio=1, details=False):
+        """Hide a share of the edges (include/f2v.h: a keyed hash of the pair below frac, except every vertex's anchor edge) ->
+        EdgeSplit(rowptr, colids: the training CSR; held_u, held_v: the hidden edges, u < v; neg_u, neg_v: `ratio` times as many
+        non-edges of the full graph per vertex), with details=True also info = SplitInfo(seconds, edges, candidates_held, protected,
+        held, train_nnz, negatives, drawn, capped).  A function of (CSR, frac, seed, ratio) alone; needs no embeddings.
+        `last_split_seconds` keeps the device time."""
+        counts, info = [C.c_uint64() for _ in range(3)], _lib.SplitInfo()
+        refs = [C.byref(x) for x in counts]
+        self._ck(self._L.f2v_edge_split(self._h, frac, seed, ratio, None, None, 0, None, None, 0, None, None, 0, *refs, C.byref(info)))
+        nnz, held, neg = (x.value for x in counts)
+        seconds = info.seconds
+        rowptr, colids = np.empty(self.n + 1, dtype=np.uint32), np.empty(nnz, dtype=np.uint32)
+        hu, hv = np.empty(held, dtype=np.uint32), np.empty(held, dtype=np.uint32)
+        nu, nv = np.empty(neg, dtype=np.uint32), np.empty(neg, dtype=np.uint32)
+        self._ck(self._L.f2v_edge_split(self._h, frac, seed, ratio, _u32(rowptr), _u32(colids), nnz, _u32(hu), _u32(hv), held, _u32(nu), _u32(nv), neg,
+                                        *refs, C.byref(info)))
+        self.last_split_seconds = seconds = seconds + info.seconds
+        if not details:
+            return EdgeSplit(rowptr, colids, hu, hv, nu, nv)
+        return EdgeSplitDetails(rowptr, colids, hu, hv, nu, nv, SplitInfo(seconds, info.edges, info.candidates_held, info.protected_edges, info.held,
+                                                                          info.train_nnz, info.negatives, info.drawn, info.capped))
+
+    def pair_scores(self, u, v, metric="dot"):
+        """The similarity of rows u[i] and v[i] of the matrix (metric: "dot" | "l2" | "cos", as `nearest` defines them) -> float32 [m],
+        each bit-equal to the score `nearest` reports for that (query, id).  `last_pairs_seconds` keeps the device time."""
+        u, v = np.ascontiguousarray(u, dtype=np.uint32).reshape(-1), np.ascontiguousarray(v, dtype=np.uint32).reshape(-1)
+        if len(u) != len(v):
+            raise ValueError("pair_scores: u and v must be two arrays of one length")
+        out, sec = np.empty(len(u), dtype=np.float32), C.c_double()
+        self._ck(self._L.f2v_pair_scores(self._h, _u32(u), _u32(v), len(u), METRICS[metric] if isinstance(metric, str) else int(metric), _f32(out), C.byref(sec)))
+        self.last_pairs_seconds = sec.value
+        return out
+
+    def ranking(self, scores, y):
+        """ROC-AUC (ties count half) and average precision of `scores` against the 0/1 labels `y`, sorted and tallied on the GPU ->
+        Ranking(auc, ap, concordant, tied, positives, negatives, groups, seconds); larger scores rank first, NaN last.  The result is
+        a function of the multiset of (score, label): the same bits under every permutation."""
+        s = np.ascontiguousarray(scores, dtype=np.float64).reshape(-1)
+        y = np.ascontiguousarray(y, dtype=np.uint8).reshape(-1)
+        if len(s) != len(y):
+            raise ValueError("ranking: one label per score")
+        r = _lib.RankingInfo()
+        self._ck(self._L.f2v_ranking(self._h, s.ctypes.data_as(_lib.f64p), y.ctypes.data_as(_lib.u8p), len(s), C.byref(r)))
+        return Ranking(r.auc, r.ap, r.concordant, r.tied, r.positives, r.negatives, r.groups, r.seconds)
+
+    def heldout_scores(self, split, metric="dot", feature=None, lam=1.0, tol=1e-4, max_iter=100, ratio=2, seed=1):
+        """Held-out link prediction.  Called on the engine that was built on split.rowptr / split.colids and trained there: ranks
+        the split's hidden edges against its negatives by `pair_scores(metric)` -> HeldoutScores(auc, ap, classifier_auc,
+        classifier_ap).  With `feature` ("hadamard" | "l1" | "l2" | "average") they are also ranked by the decision values of a
+        logistic regression fitted on this engine's own link_pairs(ratio, seed) -- pairs of the training graph only; without it the
+        two classifier values are None."""
+        u = np.concatenate([split.held_u, split.neg_u]).astype(np.uint32)
+        v = np.concatenate([split.held_v, split.neg_v]).astype(np.uint32)
+        y = np.concatenate([np.ones(len(split.held_u), dtype=np.uint8), np.zeros(len(split.neg_u), dtype=np.uint8)])
+        own = self.ranking(self.pair_scores(u, v, metric), y)
+        if feature is None:
+            return HeldoutScores(own.auc, own.ap, None, None)
+        tu, tv, ty = self.link_pairs(ratio=ratio, seed=seed)
+        model = self.logreg_fit(pairs=(tu, tv), y=ty.reshape(-1, 1), feature=feature, lam=lam, tol=tol, max_iter=max_iter)
+        clf = self.ranking(self.logreg_decision(model, pairs=(u, v))[:, 0], y)
+        return HeldoutScores(own.auc, own.ap, clf.auc, clf.ap)
 
     # -- communities (include/f2v.h: definition; a function of the CSR, seed, max_levels and max_sweeps alone) --
     def communities(self, seed=1, max_levels=32, max_sweeps=64, details=False):

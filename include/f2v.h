@@ -921,6 +921,94 @@ typedef struct {
 F2V_API int f2v_link_pairs(f2v_handle h, uint32_t ratio, uint64_t seed, uint32_t *u_out, uint32_t *v_out, uint8_t *y_out /* all three NULL: count only */,
                    uint64_t cap, uint64_t *count_out, f2v_link_t *info /* may be NULL */);
 
+/* ---- held-out link prediction ---------------------------------------------------------------------------------------------------
+ * The pair set above is the reference's protocol: the embedding is trained on every edge and a classifier is then asked to recognise
+ * those same edges.  The standard protocol hides a share of the edges, trains on the rest, ranks the hidden edges against non-edges
+ * and reports threshold-free ROC-AUC and average precision.  Three calls: f2v_edge_split (integers only), f2v_pair_scores (the
+ * embedding's own similarity of arbitrary pairs) and f2v_ranking (scores and 0/1 labels -> AUC, AP).  All run on the handle's stream
+ * as plain launches without in-grid waits or float atomics and touch neither the matrices nor the rand() stream nor any later
+ * training result.  N(u), A(u) and "rows must be ascending" are those of the link prediction pairs; mix64 as there.
+ * S1 = mix64(seed), SE = mix64(S1 ^ 0x65646765), SN = mix64(S1 ^ 0x6e656773).
+ *
+ * f2v_edge_split: a function of (the CSR, frac, seed, ratio) alone; it needs no embeddings.
+ *   candidate   for u != v: a = min(u, v), b = max(u, v), key(a, b) = mix64(SE ^ (a * 2^32 | b)); T = (uint64)(frac * 2^64) for 0 <= frac
+ *               < 1 (the product is exact, the conversion truncates); {a, b} is a hold-out candidate iff key < T.  A hash of the pair,
+ *               not a draw: both directions of an edge and every duplicate decide alike without talking to each other;
+ *   anchor      anchor(u) = the v in N(u) of smallest key(u, v), ties to the lower v; none where N(u) is empty.  The edge {u,
+ *               anchor(u)} is never held out, so every vertex that had a neighbour keeps at least one: no vertex is left without a
+ *               training signal.  CONNECTIVITY IS NOT PROMISED: a component may fall apart.  The anchors save candidates, so the held
+ *               share lies below frac (`protected_edges` counts them);
+ *   held        {a, b} is held iff it is a candidate, b != anchor(a) and a != anchor(b).  On a symmetric CSR both directions decide
+ *               alike; on a CSR that stores a nonzero in one direction only the rule is applied per nonzero as written;
+ *   training    row u keeps, in order, every nonzero v with v == u or {u, v} not held: duplicates and self-loops stay.  rowptr_train
+ *               u32[n + 1], colids_train;
+ *   positives   for u ascending, the v in N(u) with v > u and {u, v} held, ascending; q(u) is their number, H the total;
+ *   negatives   non-edges of the FULL graph: total'(u) = min(ratio * q(u), A(u) / 2), 0 <= ratio <= 16 (0 draws none); candidates
+ *               c'(u, t) = mix64(mix64(SN ^ u) + t) % n, accepted by the rule of f2v_link_pairs (not u, not in N(u), not an earlier
+ *               accepted candidate of u); order: u ascending, then acceptance order.  There is no shuffle: a ranking does not depend
+ *               on input order.  `capped` counts the vertices with A(u) / 2 < ratio * q(u), `drawn` the candidates drawn.
+ * Calling (as f2v_link_pairs): with the six output arrays all NULL only the three counts and info are filled (info->drawn stays 0);
+ * with all six given the capacities are checked: one too small is F2V_EINVAL with the counts written.  F2V_EINVAL also for a null
+ * handle or count pointer, frac outside [0, 1) or NaN, a ratio above 16, rows that are not ascending, some outputs but not all, and
+ * a vertex with more than 2^29 negatives.
+ * Launches: the anchors by one wavefront per row (a minimum over the row), the decisions and counts by one wavefront per row, the
+ * 64-bit exclusive prefix sum of the link-pair code three times (kept nonzeros, held pairs, negatives), one fill launch that writes
+ * each kept nonzero and each held pair to its place, and the negative-drawing launches of f2v_link_pairs with SN as their stream
+ * constant and the identity as their shuffle; "link_short_max" places them as there and changes no bit.
+ * Workspace of its own (no other call's buffers are used or resized), allocated on first use, grown for a larger call and freed by
+ * f2v_destroy: per vertex 5 x 4 and 3 x 8 bytes, 8 bytes per 1024 vertices, 4 (n + 1 + train_nnz) + 8 H + 9 negatives bytes of
+ * results, 4 bytes per vertex that draws negatives and the tables of f2v_link_pairs for the vertices with more than 3072.
+ *
+ * f2v_pair_scores: scores_out[i] = the similarity of the "nearest neighbours" section with q = row u_ids[i] and c = row v_ids[i]:
+ * the fp32 fma chain from +0 over ascending d; for F2V_SIM_COSINE r_v = 0 for a zero row.  A score is therefore bit-equal to the
+ * score f2v_nearest_rows reports for the same (query, id) and metric (as there, -0 is reported as +0 and every NaN as one NaN).  It
+ * works on the matrix as f2v_get_embeddings would return it (pending minibatches are committed first).  Any D.  Pairs are uploaded
+ * and run in chunks of "pairs_chunk" (f2v_set_param, 1 .. 2^26, default 2^20: 12 bytes of workspace a pair); the chunk size never
+ * changes a bit.  One wavefront per 64 pairs: 32 dimensions of the 128 rows a round are loaded by the whole wavefront, coalesced,
+ * into a padded LDS tile, then every lane runs its own pair's chain from LDS.  seconds_out (may be NULL): device time around the
+ * launches.  F2V_ESTATE without valid embeddings; F2V_EINVAL for null pointers, an id >= n, an unknown metric.  m = 0 is F2V_OK and
+ * touches nothing.
+ *
+ * f2v_ranking: scores double[m], y u8[m] (0 or 1), m < 2^31.  Larger scores rank first; -0 and +0 are one score; NaN ranks below
+ * every number and all NaNs tie.  P and N are the counts of 1 and 0.  The groups of equal score are taken in descending order, g = 1
+ * .. G, with pos_g ones and neg_g zeros:
+ *   concordant = sum_g pos_g * (zeros in later groups), tied = sum_g pos_g * neg_g, both exact uint64;
+ *   auc = (double)(2 * concordant + tied) / (2.0 * (double)P * (double)N), formed on the host: Mann-Whitney with half credit for
+ *         ties (scikit-learn's roc_auc_score);
+ *   ap  = sum / (double)P: TP_g, FP_g the inclusive cumulative ones and zeros through group g, term_g = ((double)pos_g * (double)TP_g)
+ *         / (double)(TP_g + FP_g) sits at the sorted position of the group's last item (every other position holds +0); the positions
+ *         are cut into blocks of 1024, a block is summed sequentially from +0, the block sums are added sequentially in ascending
+ *         order (scikit-learn's average_precision_score).
+ * The result is a function of the multiset of (score, label) alone -- permutation-invariant bit for bit -- and of no tunable.  Each
+ * score becomes an order-preserving 64-bit key (-0 canonicalised, NaN the lowest), the keys are sorted with the labels as payload
+ * (rocprim::radix_sort_pairs; the order inside a group is never looked at), then cumulative ones are scanned, every group's last item
+ * finds the group's first by binary search and forms the tallies (integer atomics) and its term.  Workspace: 38 bytes per item plus
+ * the sort's.  F2V_EINVAL for a label above 1, P = 0, N = 0 (out->positives / negatives are written), m >= 2^31, null pointers. */
+typedef struct {
+    double seconds;            /* device time between events around the call's own launches */
+    uint64_t edges;            /* distinct undirected edges, self-loops left out */
+    uint64_t candidates_held;  /* ... of them with key < T */
+    uint64_t protected_edges;  /* candidates that an anchor saved */
+    uint64_t held;             /* H = candidates_held - protected_edges */
+    uint64_t train_nnz;
+    uint64_t negatives;
+    uint64_t drawn;            /* candidates drawn for the negatives */
+    uint64_t capped;           /* vertices whose negatives were limited by the cap */
+} f2v_split_t;
+F2V_API int f2v_edge_split(f2v_handle h, double frac, uint64_t seed, uint32_t ratio, uint32_t *rowptr_train /* n + 1 */, uint32_t *colids_train,
+                   uint64_t cap_train, uint32_t *held_u, uint32_t *held_v, uint64_t cap_held, uint32_t *neg_u, uint32_t *neg_v, uint64_t cap_neg,
+                   uint64_t *train_nnz_out, uint64_t *held_out, uint64_t *negatives_out, f2v_split_t *info /* may be NULL */);
+F2V_API int f2v_pair_scores(f2v_handle h, const uint32_t *u_ids, const uint32_t *v_ids, uint64_t m, int metric, float *scores_out,
+                    double *seconds_out);
+typedef struct {
+    double auc, ap;
+    uint64_t concordant, tied;
+    uint64_t positives, negatives;  /* P, N */
+    uint64_t groups;                /* G */
+    double seconds;                 /* device time between events around the call's own launches */
+} f2v_ranking_t;
+F2V_API int f2v_ranking(f2v_handle h, const double *scores, const uint8_t *y, uint64_t m, f2v_ranking_t *out);
+
 /* ---- communities ----------------------------------------------------------------------------------------------------------------
  * What the graph itself achieves, to hold the modularity of an embedding's clusters against: the reference colours its pictures by
  * the graph's communities and prints their modularity (performancescores/runvisualization.py:127-152) and sweeps k-means for the best
