@@ -39,7 +39,11 @@ embedding's own similarity (`Engine.pair_scores`) -> ROC-AUC and average precisi
 
 What the graph itself achieves: `Engine.communities()` finds the graph's communities with the Louvain method on the GPU (integers only:
 the same labels on every run; `details=True` adds their modularity, the yardstick for `modularity(kmeans(k).labels)`), and
-`Engine.agreement(a, b)` gives NMI and ARI of two labellings -- clusters against communities, either against ground truth."""
+`Engine.agreement(a, b)` gives NMI and ARI of two labellings -- clusters against communities, either against ground truth.
+
+What the graph is made of: `Engine.components()` labels the connected components (the smallest id of each), `Engine.spanning_forest(seed)`
+is the unique spanning forest of a keyed order on the edges, `Engine.edge_split(..., keep="forest")` hides edges without ever cutting a
+component, and `Engine.subgraph(keep)` / `Engine.largest_component()` return an induced subgraph, relabelled, to build an engine on."""
 from . import _lib  # noqa: F401
 from ._lib import F2VError  # noqa: F401
 from ._lib import KMEANS_MAX_K, KMEANS_PIECE  # noqa: F401
@@ -52,6 +56,7 @@ from ._lib import NEAREST_EXCLUDE_NEIGHBOURS, NEAREST_EXCLUDE_SELF, NEAREST_MAX_
 from .engine import FoldInfo, LinkInfo, Pca, Trust  # noqa: F401
 from .engine import EdgeSplit, HeldoutScores, Ranking, SplitInfo  # noqa: F401
 from .engine import Agreement, Communities, LouvainLevel  # noqa: F401
+from .engine import Components, Forest, Subgraph  # noqa: F401
 from .engine import Engine, KMeans, LogregModel, Modularity, algorithms, output_name, push_masks, read_embd, read_embd_bin, sm_table, write_embd, write_embd_bin  # noqa: F401
 from .graph import read_csr_bin, read_mtx, rmat_csr, write_csr_bin  # noqa: F401
 

@@ -99,6 +99,15 @@ class RankingInfo(C.Structure):  # f2v_ranking_t
                 ("negatives", C.c_uint64), ("groups", C.c_uint64), ("seconds", C.c_double)]
 
 
+class ComponentsInfo(C.Structure):  # f2v_components_t
+    _fields_ = [("seconds", C.c_double), ("edges", C.c_uint64), ("components", C.c_uint32), ("isolated", C.c_uint32), ("largest", C.c_uint32),
+                ("largest_label", C.c_uint32), ("rounds", C.c_uint32)]
+
+
+class ForestInfo(C.Structure):  # f2v_forest_t
+    _fields_ = [("seconds", C.c_double), ("edges", C.c_uint64), ("forest_edges", C.c_uint64), ("components", C.c_uint32), ("rounds", C.c_uint32)]
+
+
 class LouvainLevel(C.Structure):  # f2v_louvain_level_t
     _fields_ = [("nodes", C.c_uint32), ("communities", C.c_uint32), ("sweeps", C.c_uint32), ("reserved", C.c_uint32), ("moves", C.c_uint64),
                 ("qnum", C.c_int64)]
@@ -173,6 +182,12 @@ SIGNATURES = {
     "f2v_link_pairs": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, u32p, u32p, u8p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(LinkInfo)]),
     "f2v_edge_split": (C.c_int, [C.c_void_p, C.c_double, C.c_uint64, C.c_uint32, u32p, u32p, C.c_uint64, u32p, u32p, C.c_uint64, u32p, u32p, C.c_uint64,
                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(SplitInfo)]),
+    "f2v_edge_split_connected": (C.c_int, [C.c_void_p, C.c_double, C.c_uint64, C.c_uint32, u32p, u32p, C.c_uint64, u32p, u32p, C.c_uint64, u32p, u32p, C.c_uint64,
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(SplitInfo)]),
+    "f2v_components": (C.c_int, [C.c_void_p, u32p, u32p, C.POINTER(ComponentsInfo)]),
+    "f2v_spanning_forest": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, u32p, u32p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(ForestInfo)]),
+    "f2v_forest_round_seconds": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_uint32, u32p]),
+    "f2v_subgraph": (C.c_int, [C.c_void_p, u8p, u32p, u32p, C.c_uint64, u32p, u32p, C.POINTER(C.c_uint64)]),
     "f2v_pair_scores": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint64, C.c_int, f32p, C.POINTER(C.c_double)]),
     "f2v_ranking": (C.c_int, [C.c_void_p, f64p, u8p, C.c_uint64, C.POINTER(RankingInfo)]),
     "f2v_louvain": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, u32p, u32p, C.POINTER(LouvainLevel), C.POINTER(LouvainInfo)]),

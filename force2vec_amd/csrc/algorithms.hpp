@@ -59,18 +59,20 @@ inline void SetInputMatricesAsCSR(CSRGraph &A, const std::string &inputfile, boo
         std::cerr << "warning: " << f2v_last_error() << std::endl;
 }
 
-// -holdout <f>: the input graph split by f2v_edge_split(frac, seed, ratio) on `device` -- the training graph (the run's handle is
+// -holdout <f>: the input graph split by f2v_edge_split(frac, seed, ratio) -- with -holdout-keep forest by f2v_edge_split_connected -- on `device` -- the training graph (the run's handle is
 // created on it), the hidden edges and as many non-edges of the full graph per vertex.  The split needs no embeddings: it runs on a
 // handle of its own, gone before the training handle is made.
 struct Holdout {
     CSRGraph train;
     std::vector<uint32_t> held_u, held_v, neg_u, neg_v;
 };
-inline void SplitForHoldout(const CSRGraph &A, double frac, uint32_t ratio, uint64_t seed, int device, Holdout &out) {
+inline void SplitForHoldout(const CSRGraph &A, double frac, uint32_t ratio, uint64_t seed, int device, Holdout &out, bool forest = false) {
+    // -holdout-keep forest: f2v_edge_split_connected, the same call but for what it protects
+    const auto split_call = forest ? f2v_edge_split_connected : f2v_edge_split;
     f2v_handle h = nullptr;
     if (f2v_create(A.rowptr, A.colids, A.rows, A.nnz, 1, device, &h) != F2V_OK) throw std::runtime_error(f2v_last_error());
     uint64_t nnz = 0, held = 0, neg = 0;
-    int rc = f2v_edge_split(h, frac, seed, ratio, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, &nnz, &held, &neg, nullptr);
+    int rc = split_call(h, frac, seed, ratio, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, &nnz, &held, &neg, nullptr);
     if (rc == F2V_OK) {
         out.train.rows = A.rows;
         out.train.nnz = nnz;
@@ -81,7 +83,7 @@ inline void SplitForHoldout(const CSRGraph &A, double frac, uint32_t ratio, uint
         out.neg_u.resize(neg + 1);
         out.neg_v.resize(neg + 1);
         rc = out.train.rowptr && out.train.colids
-                 ? f2v_edge_split(h, frac, seed, ratio, out.train.rowptr, out.train.colids, nnz ? nnz : 1, out.held_u.data(), out.held_v.data(), held + 1,
+                 ? split_call(h, frac, seed, ratio, out.train.rowptr, out.train.colids, nnz ? nnz : 1, out.held_u.data(), out.held_v.data(), held + 1,
                                   out.neg_u.data(), out.neg_v.data(), neg + 1, &nnz, &held, &neg, nullptr)
                  : F2V_ENOMEM;
         for (auto *a : {&out.held_u, &out.held_v}) a->resize(held);
@@ -268,6 +270,19 @@ class algorithms {
         f2v_agreement_t ag{};
         check(f2v_partition_agreement(h, a.data(), ka, b.data(), kb, &ag));
         printf("Agreement(%s, louvain): NMI %.17g ARI %.17g\n", what, ag.nmi, ag.ari);
+    }
+    // -components 1: the connected components of the run's graph (f2v_components) as "<embd output name>.cc", one line "v label" per
+    // vertex (0-based ids, the format of .com; the label is the smallest id of the component), and their counts
+    void writeComponents() {
+        std::vector<uint32_t> labels(rows, 0);
+        f2v_components_t info{};
+        check(f2v_components(h, labels.data(), nullptr, &info));
+        const std::string name = last_output + ".cc";
+        FILE *f = fopen(name.c_str(), "w");
+        if (!f) throw std::runtime_error("cannot write " + name);
+        for (uint32_t v = 0; v < rows; v++) fprintf(f, "%u %u\n", v, labels[v]);
+        if (fclose(f) != 0) throw std::runtime_error("cannot write " + name);
+        printf("Components: %u Largest: %u Isolated: %u\n", info.components, info.largest, info.isolated);
     }
     void writeCommunities(uint32_t levels, uint64_t seed, const std::string &truth) {
         std::vector<uint32_t> labels(rows, 0);

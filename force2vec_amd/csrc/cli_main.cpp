@@ -21,7 +21,8 @@
 // the reference's link-prediction scores of the embedding on the pair set f2v_link_pairs builds from the graph),
 // -communities 1 [-communities-levels <L>] [-communities-seed <s>] (after training, or on -init <file> with -iter 0: the communities of the
 // graph itself as "<embd output name>.com", their modularity, and their agreement with the -cluster clusters and the ground truth),
-// -holdout <f> [-holdout-ratio <r>] [-holdout-metric dot|l2|cos] (held-out link prediction: a share of the edges is hidden BEFORE training,
+// -components 1 (the connected components of the run's graph as "<embd output name>.cc" and their counts; needs no training),
+// -holdout <f> [-holdout-ratio <r>] [-holdout-metric dot|l2|cos] [-holdout-keep anchor|forest] (held-out link prediction: a share of the edges is hidden BEFORE training,
 // the run trains on the rest -- the .embd is then the training graph's embedding -- and the hidden edges are ranked against non-edges:
 // "<embd output name>.held" and ROC-AUC / average precision; with -linkpredict also by the classifier's decision values).
 #include <cstdio>
@@ -52,6 +53,8 @@ struct Settings {
     long foldin_iters = 300;
     std::string linkpredict;
     long communities = 0, communities_levels = 32, communities_seed = 1;
+    long components = 0;
+    std::string holdout_keep;
     long linkpredict_ratio = 2;
     double linkpredict_frac = 0.5;
     double holdout = -1.0;  // not given
@@ -152,6 +155,8 @@ int main(int argc, char *argv[]) {
         {"-linkpredict-ratio", Kind::Integer, &s.linkpredict_ratio, "<int>, 1..16: negatives per positive of a vertex in the -linkpredict pair set. (default:2)"},
         {"-holdout", Kind::Real, &s.holdout, "<float>, f in [0, 1): held-out link prediction. About that share of the edges is hidden before training (a hash of the pair seeded by -seed decides; every vertex keeps the edge of its lowest hash, so the share falls somewhat below f and no vertex loses all its neighbours; connectivity is not promised) and the run trains on the remaining graph: THE .embd IS THEN THE TRAINING GRAPH'S EMBEDDING, not the input graph's, and every other scorer flag of the run sees the training graph. Afterwards the hidden edges and -holdout-ratio times as many non-edges of the input graph per vertex are written to <output file>.held, one line \"u v y\" per pair (1-based ids, y = 1 for a hidden edge), ranked by the embedding's own similarity on the GPU, and \"Held-out link prediction(<metric>): <H> edges :AUC: <a> AP: <p>\" is printed (ROC-AUC with ties counted half, average precision); with -linkpredict <feature> the same line also for the decision values of the classifier, fitted on pairs of the training graph alone (one GPU; not with -foldin)."},
         {"-holdout-ratio", Kind::Integer, &s.holdout_ratio, "<int>, 0..16: non-edges per hidden edge of a vertex in the -holdout test set. (default:1)"},
+        {"-holdout-keep", Kind::Text, &s.holdout_keep, "<string>, anchor | forest: what a -holdout split never hides. anchor: every vertex's edge of lowest hash (connectivity is not promised). forest: the spanning forest of greatest hashes, found on the GPU -- the training graph keeps exactly the components of the input graph, and no rule that keeps them hides more edges. (default:anchor)"},
+        {"-components", Kind::Integer, &s.components, "<int>, 1: after the run (it needs no training: -iter 0 will do) find the connected components of the run's graph on the GPU, write <output file>.cc, one line per vertex \"v label\" (0-based; the label is the smallest id of the vertex's component), and print \"Components: <c> Largest: <s> Isolated: <z>\" (one GPU). (default:0)"},
         {"-holdout-metric", Kind::Text, &s.holdout_metric, "<string>, similarity that ranks the -holdout pairs: dot | l2 | cos. (default: l2 for options 1, 5, 8, 11, dot for the sigmoid options)"},
         {"-metric", Kind::Text, &s.metric, "<string>, similarity of -nearest: dot | l2 | cos. (default: l2 for options 5, 8, 11, dot for the sigmoid options)"},
     };
@@ -373,6 +378,22 @@ int main(int argc, char *argv[]) {
         printf("-holdout-metric must be dot, l2 or cos.\n");
         return 1;
     }
+    if (!s.holdout_keep.empty() && s.holdout_keep != "anchor" && s.holdout_keep != "forest") {
+        printf("-holdout-keep must be anchor or forest.\n");
+        return 1;
+    }
+    if (!s.holdout_keep.empty() && !holdout) {
+        printf("-holdout-keep needs -holdout (it chooses what the split protects).\n");
+        return 1;
+    }
+    if (s.components < 0 || s.components > 1) {
+        printf("-components must be 0 or 1.\n");
+        return 1;
+    }
+    if (s.components && s.gpus > 1) {
+        printf("-components is not available with -gpus > 1 (it runs on one GPU's copy of the graph).\n");
+        return 1;
+    }
     if (holdout && s.gpus > 1) {
         printf("-holdout is not available with -gpus > 1 (it splits and scores on one GPU).\n");
         return 1;
@@ -406,7 +427,7 @@ int main(int argc, char *argv[]) {
         int rc_mine = 0;
         try {
             Holdout split;
-            if (holdout) SplitForHoldout(graph, s.holdout, (uint32_t)s.holdout_ratio, (uint64_t)s.seed, (int)s.device, split);
+            if (holdout) SplitForHoldout(graph, s.holdout, (uint32_t)s.holdout_ratio, (uint64_t)s.seed, (int)s.device, split, s.holdout_keep == "forest");
             algorithms algo(holdout ? split.train : graph, s.input, s.output, (INDEXTYPE)s.dim, (VALUETYPE)s.gamma, (INDEXTYPE)s.batch, (int)s.device + (s.samegpu ? 0 : rank));
             algo.binary_output = s.binout != 0;
             algo.text_output = s.notext == 0;
@@ -437,6 +458,7 @@ int main(int argc, char *argv[]) {
             if (!s.linkpredict.empty() && rank == 0) algo.linkPredict(linkpredict_feature, s.linkpredict_frac, (uint32_t)s.linkpredict_ratio, (uint64_t)s.seed);
             if (holdout && rank == 0)
                 algo.heldOut(split, holdout_metric, s.holdout_metric.c_str(), s.linkpredict.empty() ? -1 : linkpredict_feature, (uint32_t)s.linkpredict_ratio, (uint64_t)s.seed);
+            if (s.components && rank == 0) algo.writeComponents();
             if (s.communities && rank == 0)
                 algo.writeCommunities((uint32_t)s.communities_levels, (uint64_t)s.communities_seed,
                                       !s.separation.empty() && s.separation != "kmeans" ? s.separation : s.classify);

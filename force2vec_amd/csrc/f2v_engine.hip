@@ -44,6 +44,7 @@
 #include "f2v_linkpairs.hip.h"
 #include "f2v_heldout.hip.h"
 #include "f2v_louvain.hip.h"
+#include "f2v_components.hip.h"
 #include "f2v_tsne.hip.h"
 
 using namespace f2v;
@@ -344,6 +345,23 @@ struct f2v_ctx {
         uint32_t short_max = 32, lds_slots = 4096;
         int rows_symmetric = -1;
     } lv;
+    // components, spanning forests and subgraphs (f2v_components, f2v_spanning_forest, f2v_edge_split_connected's forest flags,
+    // f2v_subgraph): the workspace f2v.h states, allocated on first use and grown for a larger call; "forest_key_bits": the leading bits
+    // of a key that the forest's order looks at (a diagnostic knob: small values force ties).  items_built: the pieces of the long rows
+    // are on the device; flags_*: which forest d_flag holds (a split with the same seed reuses it)
+    struct Components {
+        DevBuf<uint32_t> d_L, d_P, d_size, d_sizes, d_kept, d_cnt, d_zero, d_rowptr, d_colids, d_newid;
+        DevBuf<CcItem> d_items;
+        DevBuf<unsigned long long> d_sums, d_best1, d_best2, d_forest[2], d_id_at, d_row_at, d_tile;
+        DevBuf<uint8_t> d_flag, d_keep, d_sort;
+        DevTimer timer;
+        uint32_t nitems = 0, key_bits = 64;
+        bool items_built = false, flag_valid = false;
+        uint64_t flag_seed = 0;
+        uint32_t flag_bits = 0;
+        std::vector<double> round_seconds;  // f2v_forest_round_seconds
+    } cc;
+    double cc_subgraph_seconds = 0.0;  // "last_subgraph_us"
     // t-SNE layout (f2v_tsne_affinities, f2v_tsne): the workspace f2v.h states, allocated on first use and grown for a larger call;
     // "tsne_rows" (0 = automatic | 64 | 128 | 256): rows per workgroup of tsne_pair_kernel, "tsne_slices" (0 = automatic): spans per
     // workgroup of it -- placement only
@@ -2362,6 +2380,10 @@ const Param kParams[] = {
     {"louvain_short_max", F2V_FIELD(lv.short_max), kValue, kKeep, in<0, kLouvainShortLimit>, "louvain_short_max must be 0..256"},
     // f2v_louvain: the largest table (slots) a workgroup keeps in LDS; a longer one lies in the workspace; placement only
     {"louvain_lds_slots", F2V_FIELD(lv.lds_slots), kValue, kKeep, in<0, kLouvainLdsLimit>, "louvain_lds_slots must be 0..8192"},
+    // f2v_spanning_forest, f2v_edge_split_connected: the forest's order compares the leading `bits` bits of a key, then (a, b).  A
+    // diagnostic knob: small values force key ties so that the tie-break runs; it never affects which pairs are hold-out candidates
+    {"last_subgraph_us", [](const f2v_ctx *c) { return (int64_t)(c->cc_subgraph_seconds * 1e6 + 0.5); }, nullptr},
+    {"forest_key_bits", F2V_FIELD(cc.key_bits), kValue, kKeep, in<1, 64>, "forest_key_bits must be 1..64"},
     {"push_fused", F2V_FIELD(push.fused), kFlag},
     {"push_timeout_ms", F2V_FIELD(push.timeout_ms), kValue, kKeep, in<1, 600000>, "push_timeout_ms must be 1..600000"},
     // takes effect at the next f2v_push_export; read: what the exchange in place runs with
@@ -4858,18 +4880,23 @@ int f2v_link_pairs(f2v_handle c, uint32_t ratio, uint64_t seed, uint32_t *u_out,
 }  // extern "C"
 
 // ---- held-out link prediction (f2v_heldout.hip.h; definition in include/f2v.h) ---------------------------------------------------
-extern "C" {
+namespace {
 
-int f2v_edge_split(f2v_handle c, double frac, uint64_t seed, uint32_t ratio, uint32_t *rowptr_train, uint32_t *colids_train, uint64_t cap_train,
-                   uint32_t *held_u, uint32_t *held_v, uint64_t cap_held, uint32_t *neg_u, uint32_t *neg_v, uint64_t cap_neg, uint64_t *train_nnz_out,
-                   uint64_t *held_out, uint64_t *negatives_out, f2v_split_t *info) {
-    if (!c || !train_nnz_out || !held_out || !negatives_out) return fail(F2V_EINVAL, "f2v_edge_split: null argument");
+// the greatest spanning forest of `seed` as one flag per nonzero in c->cc.d_flag (the components section below)
+int forest_flags(f2v_ctx *c, const char *who, uint64_t seed, double *seconds);
+
+// f2v_edge_split (`forest` false: the anchors protect) and f2v_edge_split_connected (true: the greatest spanning forest does): one
+// definition but for the protection rule, so one body; the anchor path launches what it always launched
+int edge_split_impl(f2v_ctx *c, const char *who, bool forest, double frac, uint64_t seed, uint32_t ratio, uint32_t *rowptr_train, uint32_t *colids_train,
+                    uint64_t cap_train, uint32_t *held_u, uint32_t *held_v, uint64_t cap_held, uint32_t *neg_u, uint32_t *neg_v, uint64_t cap_neg,
+                    uint64_t *train_nnz_out, uint64_t *held_out, uint64_t *negatives_out, f2v_split_t *info) {
+    if (!c || !train_nnz_out || !held_out || !negatives_out) return fail(F2V_EINVAL, "%s: null argument", who);
     const int given = (rowptr_train != nullptr) + (colids_train != nullptr) + (held_u != nullptr) + (held_v != nullptr) + (neg_u != nullptr) + (neg_v != nullptr);
-    if (given != 0 && given != 6) return fail(F2V_EINVAL, "f2v_edge_split: the six output arrays are given together or not at all");
+    if (given != 0 && given != 6) return fail(F2V_EINVAL, "%s: the six output arrays are given together or not at all", who);
     const bool fill = given == 6;
-    if (!(frac >= 0.0 && frac < 1.0)) return fail(F2V_EINVAL, "f2v_edge_split: frac = %g is outside [0, 1)", frac);
-    if (ratio > 16) return fail(F2V_EINVAL, "f2v_edge_split: ratio = %u is outside 0..16", ratio);
-    if (!rows_ascending(c)) return fail(F2V_EINVAL, "f2v_edge_split: the CSR's column ids are not ascending inside every row (needed to search a row)");
+    if (!(frac >= 0.0 && frac < 1.0)) return fail(F2V_EINVAL, "%s: frac = %g is outside [0, 1)", who, frac);
+    if (ratio > 16) return fail(F2V_EINVAL, "%s: ratio = %u is outside 0..16", who, ratio);
+    if (!rows_ascending(c)) return fail(F2V_EINVAL, "%s: the CSR's column ids are not ascending inside every row (needed to search a row)", who);
     HIPC(hipSetDevice(c->device));
     *train_nnz_out = *held_out = *negatives_out = 0;
     if (info) *info = f2v_split_t{};
@@ -4924,9 +4951,17 @@ int f2v_edge_split(f2v_handle c, double frac, uint64_t seed, uint32_t ratio, uin
         hipLaunchKernelGGL(link_scan_apply_kernel, dim3(tiles), dim3(256), 0, c->stream, l);
     };
     double seconds = 0.0;
+    if (forest) {
+        F2VC(forest_flags(c, who, seed, &seconds));
+        a.forest = c->cc.d_flag;
+    }
     F2VC(w.timer.start(c->stream));
-    hipLaunchKernelGGL(held_anchor_kernel, dim3(rows), dim3(256), 0, c->stream, a);
-    hipLaunchKernelGGL(held_count_kernel, dim3(rows), dim3(256), 0, c->stream, a);
+    if (forest) {
+        hipLaunchKernelGGL(held_forest_count_kernel, dim3(rows), dim3(256), 0, c->stream, a);
+    } else {
+        hipLaunchKernelGGL(held_anchor_kernel, dim3(rows), dim3(256), 0, c->stream, a);
+        hipLaunchKernelGGL(held_count_kernel, dim3(rows), dim3(256), 0, c->stream, a);
+    }
     scan(w.d_kept, w.d_zero, w.d_kept_at);
     scan(w.d_q, w.d_zero, w.d_held_at);
     scan(w.d_zero, w.d_total, w.d_neg_at);
@@ -4953,7 +4988,7 @@ int f2v_edge_split(f2v_handle c, double frac, uint64_t seed, uint32_t ratio, uin
         info->capped = sums[5];
     }
     if (fill && (cap_train < nnz_train || cap_held < H || cap_neg < negs))
-        return fail(F2V_EINVAL, "f2v_edge_split: %llu training nonzeros, %llu held pairs and %llu negatives; the arrays hold %llu, %llu and %llu",
+        return fail(F2V_EINVAL, "%s: %llu training nonzeros, %llu held pairs and %llu negatives; the arrays hold %llu, %llu and %llu", who,
                     (unsigned long long)nnz_train, (unsigned long long)H, (unsigned long long)negs, (unsigned long long)cap_train, (unsigned long long)cap_held,
                     (unsigned long long)cap_neg);
     if (!fill) return F2V_OK;
@@ -4971,7 +5006,7 @@ int f2v_edge_split(f2v_handle c, double frac, uint64_t seed, uint32_t ratio, uin
     a.held_v = w.d_hv;
     LinkPlan plan;
     if (negs) {
-        F2VC(link_place(c, "f2v_edge_split", what, total, c->link.short_max, w.d_order, w.d_table_at, w.d_table, l, plan));
+        F2VC(link_place(c, who, what, total, c->link.short_max, w.d_order, w.d_table_at, w.d_table, l, plan));
         l.p = w.d_zero;
         l.total = w.d_total;
         l.offset = w.d_neg_at;
@@ -4980,7 +5015,8 @@ int f2v_edge_split(f2v_handle c, double frac, uint64_t seed, uint32_t ratio, uin
         l.y_out = w.d_ny;
     }
     F2VC(w.timer.start(c->stream));
-    hipLaunchKernelGGL(held_fill_kernel, dim3(rows), dim3(256), 0, c->stream, a);
+    if (forest) hipLaunchKernelGGL(held_forest_fill_kernel, dim3(rows), dim3(256), 0, c->stream, a);
+    else hipLaunchKernelGGL(held_fill_kernel, dim3(rows), dim3(256), 0, c->stream, a);
     if (negs) F2VC(link_draw(c, total, plan, w.d_order, l));
     HIPC(hipGetLastError());
     F2VC(w.timer.stop(c->stream));
@@ -5003,6 +5039,24 @@ int f2v_edge_split(f2v_handle c, double frac, uint64_t seed, uint32_t ratio, uin
         info->drawn = sums[11];
     }
     return F2V_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int f2v_edge_split(f2v_handle c, double frac, uint64_t seed, uint32_t ratio, uint32_t *rowptr_train, uint32_t *colids_train, uint64_t cap_train,
+                   uint32_t *held_u, uint32_t *held_v, uint64_t cap_held, uint32_t *neg_u, uint32_t *neg_v, uint64_t cap_neg, uint64_t *train_nnz_out,
+                   uint64_t *held_out, uint64_t *negatives_out, f2v_split_t *info) {
+    return edge_split_impl(c, "f2v_edge_split", false, frac, seed, ratio, rowptr_train, colids_train, cap_train, held_u, held_v, cap_held, neg_u, neg_v, cap_neg,
+                           train_nnz_out, held_out, negatives_out, info);
+}
+
+int f2v_edge_split_connected(f2v_handle c, double frac, uint64_t seed, uint32_t ratio, uint32_t *rowptr_train, uint32_t *colids_train, uint64_t cap_train,
+                             uint32_t *held_u, uint32_t *held_v, uint64_t cap_held, uint32_t *neg_u, uint32_t *neg_v, uint64_t cap_neg,
+                             uint64_t *train_nnz_out, uint64_t *held_out, uint64_t *negatives_out, f2v_split_t *info) {
+    return edge_split_impl(c, "f2v_edge_split_connected", true, frac, seed, ratio, rowptr_train, colids_train, cap_train, held_u, held_v, cap_held, neg_u, neg_v,
+                           cap_neg, train_nnz_out, held_out, negatives_out, info);
 }
 
 int f2v_pair_scores(f2v_handle c, const uint32_t *u_ids, const uint32_t *v_ids, uint64_t m, int metric, float *scores_out, double *seconds_out) {
@@ -5479,6 +5533,332 @@ int f2v_partition_agreement(f2v_handle c, const uint32_t *la, uint32_t ka, const
     const double sc = (double)out->sum_comb, sa = (double)out->sum_a, sb = (double)out->sum_b, tt = (double)out->total;
     const double den = 0.5 * (sa + sb) - sa * sb / tt;
     out->ari = den == 0.0 ? 1.0 : (sc - sa * sb / tt) / den;
+    return F2V_OK;
+}
+
+}  // extern "C"
+
+// ---- components, spanning forests and subgraphs (f2v_components.hip.h; definition in include/f2v.h) ------------------------------
+namespace {
+
+constexpr const char *kCcWhat = "components";
+
+inline dim3 cc_grid(uint64_t threads) { return dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((threads + 255) / 256, 16384))); }
+
+// What the graph calls share: the graph's arrays, the pieces of the long rows (built once per handle, from the host's rowptr), the
+// two label arrays and the words the kernels report through
+int cc_prepare(f2v_ctx *c, CcArgs &a) {
+    f2v_ctx::Components &w = c->cc;
+    const uint32_t n = c->n;
+    if (!w.items_built) {
+        std::vector<CcItem> items;
+        for (uint32_t u = 0; u < n; u++) {
+            const uint32_t lo = c->rowptr[u], hi = c->rowptr[u + 1];
+            if (hi - lo <= kCcPiece) continue;
+            for (uint32_t q = lo; q < hi; q += std::min(kCcPiece, hi - q)) items.push_back(CcItem{u, q, q + std::min(kCcPiece, hi - q)});
+        }
+        if (items.size() > 0xFFFFFFFFull) return fail(F2V_EINVAL, "components: too many row pieces");
+        F2VC(w.d_items.reserve(c, items.size(), kCcWhat));
+        if (!items.empty()) {
+            HIPC(hipMemcpyAsync(w.d_items, items.data(), items.size() * sizeof(CcItem), hipMemcpyHostToDevice, c->stream));
+            HIPC(hipStreamSynchronize(c->stream));  // (the vector goes out of scope)
+        }
+        w.nitems = (uint32_t)items.size();
+        w.items_built = true;
+    }
+    F2VC(w.d_L.reserve(c, n, kCcWhat));
+    F2VC(w.d_P.reserve(c, n, kCcWhat));
+    F2VC(w.d_sums.reserve(c, 8, kCcWhat));
+    a = CcArgs{};
+    a.rowptr = c->d_rowptr;
+    a.colids = c->d_colids;
+    a.items = w.d_items;
+    a.n = n;
+    a.nitems = w.nitems;
+    a.L = w.d_L;
+    a.P = w.d_P;
+    a.sums = w.d_sums;
+    HIPC(hipMemsetAsync(w.d_sums, 0, 8 * sizeof(unsigned long long), c->stream));
+    return F2V_OK;
+}
+
+inline dim3 cc_piece_grid(const CcArgs &a) { return dim3((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)a.n + a.nitems + 3) / 4, 16384))); }
+
+// P flattened (every vertex names its root), then L = P.  *flag0: what sums[0] held (a hook happened / a pair was found); it is cleared.
+int cc_flatten(f2v_ctx *c, const CcArgs &a, bool *flag0) {
+    f2v_ctx::Components &w = c->cc;
+    for (;;) {
+        hipLaunchKernelGGL(cc_jump_kernel, cc_grid(a.n), dim3(256), 0, c->stream, a);
+        HIPC(hipGetLastError());
+        unsigned long long flags[2];
+        HIPC(hipMemcpyAsync(flags, w.d_sums, sizeof flags, hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipMemsetAsync(w.d_sums, 0, sizeof flags, c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+        if (flags[0]) *flag0 = true;
+        if (!flags[1]) break;
+    }
+    HIPC(hipMemcpyAsync(w.d_L, w.d_P, (size_t)a.n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+    return F2V_OK;
+}
+
+struct ForestRun {
+    uint64_t edges = 0, forest_edges = 0;
+    uint32_t rounds = 0;
+    double seconds = 0.0;
+};
+
+// Boruvka over the order of (seed, "forest_key_bits", greatest): the sorted packed pairs end in c->cc.d_forest[1]
+int forest_run(f2v_ctx *c, uint64_t seed, uint32_t greatest, ForestRun &out) {
+    f2v_ctx::Components &w = c->cc;
+    const uint32_t n = c->n;
+    bool symmetric = false;
+    F2VC(rows_symmetric(c, &symmetric));
+    CcArgs a;
+    F2VC(cc_prepare(c, a));
+    F2VC(w.d_best1.reserve(c, n, kCcWhat));
+    F2VC(w.d_best2.reserve(c, n, kCcWhat));
+    F2VC(w.d_forest[0].reserve(c, n, kCcWhat));
+    F2VC(w.d_forest[1].reserve(c, n, kCcWhat));
+    a.best1 = w.d_best1;
+    a.best2 = w.d_best2;
+    a.forest = w.d_forest[0];
+    a.se = mix64_host(mix64_host(seed) ^ 0x65646765ull);
+    a.shift = 64u - w.key_bits;
+    a.greatest = greatest;
+    a.both = symmetric ? 0u : 1u;
+    w.round_seconds.clear();
+    F2VC(w.timer.start(c->stream));
+    hipLaunchKernelGGL(cc_iota_kernel, cc_grid(n), dim3(256), 0, c->stream, (uint32_t *)w.d_L, (uint32_t *)w.d_P, n);
+    hipLaunchKernelGGL(cc_edges_kernel, cc_piece_grid(a), dim3(256), 0, c->stream, a);
+    HIPC(hipGetLastError());
+    for (;;) {
+        const auto t0 = std::chrono::steady_clock::now();
+        HIPC(hipMemsetAsync(w.d_best1, 0, (size_t)n * sizeof(unsigned long long), c->stream));
+        HIPC(hipMemsetAsync(w.d_best2, 0, (size_t)n * sizeof(unsigned long long), c->stream));
+        hipLaunchKernelGGL(forest_key_kernel, cc_piece_grid(a), dim3(256), 0, c->stream, a);
+        hipLaunchKernelGGL(forest_pair_kernel, cc_piece_grid(a), dim3(256), 0, c->stream, a);
+        hipLaunchKernelGGL(forest_hook_kernel, cc_grid(n), dim3(256), 0, c->stream, a);
+        bool found = false;
+        F2VC(cc_flatten(c, a, &found));
+        out.rounds++;
+        w.round_seconds.push_back(std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+        if (!found) break;
+    }
+    unsigned long long sums[8];
+    HIPC(hipMemcpyAsync(sums, w.d_sums, sizeof sums, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    out.edges = sums[2];
+    out.forest_edges = sums[6];
+    if (out.forest_edges >= n) return fail(F2V_ESTATE, "spanning forest: %llu pairs on %u vertices", (unsigned long long)out.forest_edges, n);
+    if (out.forest_edges) {
+        size_t sort_bytes = 0;
+        HIPC(rocprim::radix_sort_keys(nullptr, sort_bytes, (unsigned long long *)w.d_forest[0], (unsigned long long *)w.d_forest[1], out.forest_edges, 0, 64, c->stream));
+        F2VC(w.d_sort.reserve(c, sort_bytes, kCcWhat));
+        HIPC(rocprim::radix_sort_keys((void *)(uint8_t *)w.d_sort, sort_bytes, (unsigned long long *)w.d_forest[0], (unsigned long long *)w.d_forest[1], out.forest_edges, 0,
+                                      64, c->stream));
+    }
+    F2VC(w.timer.stop(c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    F2VC(w.timer.seconds(&out.seconds));
+    return F2V_OK;
+}
+
+int forest_flags(f2v_ctx *c, const char *who, uint64_t seed, double *seconds) {
+    (void)who;
+    f2v_ctx::Components &w = c->cc;
+    if (w.flag_valid && w.flag_seed == seed && w.flag_bits == w.key_bits) return F2V_OK;  // (the CSR of a handle never changes)
+    w.flag_valid = false;
+    ForestRun run;
+    F2VC(forest_run(c, seed, 1, run));
+    F2VC(w.d_flag.reserve(c, std::max<uint64_t>(c->nnz, 1), kCcWhat));
+    CcArgs a;
+    F2VC(cc_prepare(c, a));
+    a.forest = w.d_forest[1];
+    a.forest_count = run.forest_edges;
+    a.flag = w.d_flag;
+    F2VC(w.timer.start(c->stream));
+    hipLaunchKernelGGL(forest_mark_kernel, cc_piece_grid(a), dim3(256), 0, c->stream, a);
+    HIPC(hipGetLastError());
+    F2VC(w.timer.stop(c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    *seconds += run.seconds;
+    F2VC(w.timer.seconds(seconds));
+    w.flag_valid = true;
+    w.flag_seed = seed;
+    w.flag_bits = w.key_bits;
+    return F2V_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int f2v_components(f2v_handle c, uint32_t *labels_out, uint32_t *sizes_out, f2v_components_t *info) {
+    if (!c || !labels_out || !info) return fail(F2V_EINVAL, "f2v_components: null argument");
+    if (!rows_ascending(c)) return fail(F2V_EINVAL, "f2v_components: the CSR's column ids are not ascending inside every row (needed to search a row)");
+    HIPC(hipSetDevice(c->device));
+    *info = f2v_components_t{};
+    const uint32_t n = c->n;
+    if (n == 0) return F2V_OK;
+    f2v_ctx::Components &w = c->cc;
+    CcArgs a;
+    F2VC(cc_prepare(c, a));
+    F2VC(w.d_size.reserve(c, n, kCcWhat));
+    F2VC(w.d_sizes.reserve(c, n, kCcWhat));
+    a.size = w.d_size;
+    a.sizes_out = w.d_sizes;
+    F2VC(w.timer.start(c->stream));
+    hipLaunchKernelGGL(cc_iota_kernel, cc_grid(n), dim3(256), 0, c->stream, (uint32_t *)w.d_L, (uint32_t *)w.d_P, n);
+    hipLaunchKernelGGL(cc_edges_kernel, cc_piece_grid(a), dim3(256), 0, c->stream, a);
+    HIPC(hipGetLastError());
+    uint32_t rounds = 0;
+    for (;;) {
+        hipLaunchKernelGGL(cc_hook_kernel, cc_piece_grid(a), dim3(256), 0, c->stream, a);
+        bool hooked = false;
+        F2VC(cc_flatten(c, a, &hooked));
+        rounds++;
+        if (!hooked) break;
+    }
+    HIPC(hipMemsetAsync(w.d_size, 0, (size_t)n * sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(cc_size_kernel, cc_grid(n), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(cc_stat_kernel, cc_grid(n), dim3(256), 0, c->stream, a);
+    HIPC(hipGetLastError());
+    F2VC(w.timer.stop(c->stream));
+    unsigned long long sums[8];
+    HIPC(hipMemcpyAsync(sums, w.d_sums, sizeof sums, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipMemcpyAsync(labels_out, w.d_L, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (sizes_out) HIPC(hipMemcpyAsync(sizes_out, w.d_sizes, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    F2VC(w.timer.seconds(&info->seconds));
+    info->edges = sums[2];
+    info->components = (uint32_t)sums[3];
+    info->isolated = (uint32_t)sums[4];
+    info->largest = (uint32_t)(sums[5] >> 32);
+    info->largest_label = 0xFFFFFFFFu - (uint32_t)sums[5];
+    info->rounds = rounds;
+    return F2V_OK;
+}
+
+int f2v_spanning_forest(f2v_handle c, uint64_t seed, uint32_t greatest, uint32_t *u_out, uint32_t *v_out, uint64_t cap, uint64_t *count_out, f2v_forest_t *info) {
+    if (!c || !count_out) return fail(F2V_EINVAL, "f2v_spanning_forest: null argument");
+    if ((u_out != nullptr) != (v_out != nullptr)) return fail(F2V_EINVAL, "f2v_spanning_forest: u_out and v_out are given together or not at all");
+    if (greatest > 1) return fail(F2V_EINVAL, "f2v_spanning_forest: greatest = %u is neither 0 nor 1", greatest);
+    if (!rows_ascending(c)) return fail(F2V_EINVAL, "f2v_spanning_forest: the CSR's column ids are not ascending inside every row (needed to search a row)");
+    HIPC(hipSetDevice(c->device));
+    *count_out = 0;
+    if (info) *info = f2v_forest_t{};
+    const uint32_t n = c->n;
+    if (n == 0) return F2V_OK;
+    ForestRun run;
+    F2VC(forest_run(c, seed, greatest, run));
+    *count_out = run.forest_edges;
+    if (info) {
+        info->seconds = run.seconds;
+        info->edges = run.edges;
+        info->forest_edges = run.forest_edges;
+        info->components = n - (uint32_t)run.forest_edges;
+        info->rounds = run.rounds;
+    }
+    if (!u_out) return F2V_OK;
+    if (cap < run.forest_edges)
+        return fail(F2V_EINVAL, "f2v_spanning_forest: the forest has %llu pairs, the arrays hold %llu", (unsigned long long)run.forest_edges, (unsigned long long)cap);
+    std::vector<unsigned long long> pairs(run.forest_edges);
+    if (run.forest_edges) {
+        HIPC(hipMemcpyAsync(pairs.data(), c->cc.d_forest[1], run.forest_edges * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+    }
+    for (uint64_t i = 0; i < run.forest_edges; i++) {
+        u_out[i] = (uint32_t)(pairs[i] >> 32);
+        v_out[i] = (uint32_t)pairs[i];
+    }
+    return F2V_OK;
+}
+
+int f2v_forest_round_seconds(f2v_handle c, double *seconds_out, uint32_t cap, uint32_t *count_out) {
+    if (!c || !count_out) return fail(F2V_EINVAL, "f2v_forest_round_seconds: null argument");
+    const std::vector<double> &r = c->cc.round_seconds;
+    *count_out = (uint32_t)r.size();
+    if (seconds_out)
+        for (uint32_t i = 0; i < cap && i < r.size(); i++) seconds_out[i] = r[i];
+    return F2V_OK;
+}
+
+int f2v_subgraph(f2v_handle c, const uint8_t *keep, uint32_t *rowptr_out, uint32_t *colids_out, uint64_t cap, uint32_t *new_id_out, uint32_t *rows_out,
+                 uint64_t *nnz_out) {
+    if (!c || !keep || !rows_out || !nnz_out) return fail(F2V_EINVAL, "f2v_subgraph: null argument");
+    if ((rowptr_out != nullptr) != (colids_out != nullptr)) return fail(F2V_EINVAL, "f2v_subgraph: rowptr_out and colids_out are given together or not at all");
+    HIPC(hipSetDevice(c->device));
+    *rows_out = 0;
+    *nnz_out = 0;
+    const uint32_t n = c->n;
+    if (n == 0) return F2V_OK;
+    f2v_ctx::Components &w = c->cc;
+    const uint32_t tiles = (uint32_t)(((uint64_t)n + kLinkScanTile - 1) / kLinkScanTile), rows = std::min((n + 3) / 4, 8192u);
+    F2VC(w.d_keep.reserve(c, n, kCcWhat));
+    F2VC(w.d_kept.reserve(c, n, kCcWhat));
+    F2VC(w.d_cnt.reserve(c, n, kCcWhat));
+    F2VC(w.d_zero.reserve(c, n, kCcWhat));
+    F2VC(w.d_id_at.reserve(c, n, kCcWhat));
+    F2VC(w.d_row_at.reserve(c, n, kCcWhat));
+    F2VC(w.d_tile.reserve(c, tiles, kCcWhat));
+    F2VC(w.d_sums.reserve(c, 8, kCcWhat));
+    SubArgs a{};
+    a.rowptr = c->d_rowptr;
+    a.colids = c->d_colids;
+    a.keep = w.d_keep;
+    a.kept = w.d_kept;
+    a.cnt = w.d_cnt;
+    a.id_at = w.d_id_at;
+    a.row_at = w.d_row_at;
+    a.sums = w.d_sums;
+    a.n = n;
+    LinkArgs l{};  // the 64-bit exclusive prefix sum of f2v_linkpairs.hip.h
+    l.n = n;
+    l.tile = w.d_tile;
+    l.total = w.d_zero;
+    HIPC(hipMemcpyAsync(w.d_keep, keep, n, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipMemsetAsync(w.d_sums, 0, 8 * sizeof(unsigned long long), c->stream));
+    HIPC(hipMemsetAsync(w.d_zero, 0, (size_t)n * sizeof(uint32_t), c->stream));
+    auto scan = [&](uint32_t *p, unsigned long long *offset) {
+        l.p = p;
+        l.offset = offset;
+        hipLaunchKernelGGL(link_scan_tile_kernel, dim3(tiles), dim3(256), 0, c->stream, l);
+        hipLaunchKernelGGL(link_scan_top_kernel, dim3(1), dim3(256), 0, c->stream, l, tiles);
+        hipLaunchKernelGGL(link_scan_apply_kernel, dim3(tiles), dim3(256), 0, c->stream, l);
+    };
+    double seconds = 0.0;
+    F2VC(w.timer.start(c->stream));
+    hipLaunchKernelGGL(sub_count_kernel, dim3(rows), dim3(256), 0, c->stream, a);
+    scan(w.d_kept, w.d_id_at);
+    scan(w.d_cnt, w.d_row_at);
+    HIPC(hipGetLastError());
+    F2VC(w.timer.stop(c->stream));
+    unsigned long long sums[2];
+    HIPC(hipMemcpyAsync(sums, w.d_sums, sizeof sums, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    F2VC(w.timer.seconds(&seconds));
+    c->cc_subgraph_seconds = seconds;
+    *rows_out = (uint32_t)sums[0];
+    *nnz_out = sums[1];
+    if (!rowptr_out) return F2V_OK;
+    if (cap < sums[1]) return fail(F2V_EINVAL, "f2v_subgraph: the subgraph has %llu nonzeros, colids_out holds %llu", sums[1], (unsigned long long)cap);
+    F2VC(w.d_rowptr.reserve(c, (size_t)sums[0] + 1, kCcWhat));
+    F2VC(w.d_colids.reserve(c, std::max<uint64_t>(sums[1], 1), kCcWhat));
+    F2VC(w.d_newid.reserve(c, n, kCcWhat));
+    a.rowptr_out = w.d_rowptr;
+    a.colids_out = w.d_colids;
+    a.new_id = w.d_newid;
+    F2VC(w.timer.start(c->stream));
+    hipLaunchKernelGGL(sub_fill_kernel, dim3(rows), dim3(256), 0, c->stream, a);
+    HIPC(hipGetLastError());
+    F2VC(w.timer.stop(c->stream));
+    if (sums[0]) HIPC(hipMemcpyAsync(rowptr_out, w.d_rowptr, (size_t)sums[0] * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (sums[1]) HIPC(hipMemcpyAsync(colids_out, w.d_colids, (size_t)sums[1] * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (new_id_out) HIPC(hipMemcpyAsync(new_id_out, w.d_newid, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    F2VC(w.timer.seconds(&seconds));
+    c->cc_subgraph_seconds = seconds;
+    rowptr_out[sums[0]] = (uint32_t)sums[1];
     return F2V_OK;
 }
 

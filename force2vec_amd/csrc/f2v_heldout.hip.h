@@ -3,7 +3,9 @@
 // The edge split (integers only: a function of the CSR, frac, seed and ratio, whatever the launch shapes):
 //   held_anchor_kernel   one wavefront per row (grid stride), lanes over the row: the neighbour of smallest (key, id), a
 //                        lexicographic minimum over the wavefront by xor shuffles;
-//   held_count_kernel    one wavefront per row: every nonzero decides "held" from its key and the two anchors; the row's kept
+//   held_count_kernel    one wavefront per row: every nonzero decides "held" from its key and the two anchors (held_forest_count_kernel
+//                        and held_forest_fill_kernel: from its key and its forest flag -- f2v_edge_split_connected, which does not
+//                        run the anchor kernel); the row's kept
 //                        nonzeros, q(u) and |N(u)| ("distinct" is "differs from its predecessor") by ballots, total'(u) by the rule;
 //                        the call's sums go to 64-bit words, one integer atomic per wavefront and word;
 //   link_scan_*_kernel   (f2v_linkpairs.hip.h) the three exclusive prefix sums: kept nonzeros, held pairs, negatives;
@@ -45,6 +47,7 @@ constexpr uint32_t kRankBlock = 1024;        // positions per block of the avera
 struct HeldArgs {
     const uint32_t *rowptr, *colids;
     uint32_t *anchor;                  // per vertex: anchor(u), kHeldNone where N(u) is empty
+    const uint8_t *forest;             // f2v_edge_split_connected: per nonzero, its pair is in the greatest spanning forest (f2v_components.hip.h)
     uint32_t *kept, *q, *total;        // per vertex: nonzeros that stay, held pairs with v > u, negatives
     const unsigned long long *kept_at, *held_at;  // per vertex: the index of its first kept nonzero / held pair
     unsigned long long *sums;          // [0] edges, [1] candidates, [2] held, [3] kept nonzeros, [4] negatives, [5] capped
@@ -58,9 +61,12 @@ __device__ __forceinline__ uint64_t held_key(const HeldArgs &a, uint32_t u, uint
     return mix64(a.se ^ (((uint64_t)lo << 32) | hi));
 }
 
-__device__ __forceinline__ bool held_is(const HeldArgs &a, uint32_t u, uint32_t v) {
+// nonzero q = (u, v): FOREST = false the anchors protect (f2v_edge_split), true the spanning forest does (f2v_edge_split_connected)
+template <bool FOREST>
+__device__ __forceinline__ bool held_is(const HeldArgs &a, uint32_t u, uint32_t v, uint32_t q) {
     if (u == v || held_key(a, u, v) >= a.T) return false;
-    return a.anchor[u] != v && a.anchor[v] != u;
+    if constexpr (FOREST) return a.forest[q] == 0;
+    else return a.anchor[u] != v && a.anchor[v] != u;
 }
 
 __global__ __launch_bounds__(256) void held_anchor_kernel(const HeldArgs a) {
@@ -92,7 +98,8 @@ __global__ __launch_bounds__(256) void held_anchor_kernel(const HeldArgs a) {
     }
 }
 
-__global__ __launch_bounds__(256) void held_count_kernel(const HeldArgs a) {
+template <bool FOREST>
+__device__ __forceinline__ void held_count_rows(const HeldArgs &a) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     unsigned long long edges = 0, cands = 0, held = 0, kept = 0, neg = 0, capped = 0;
     for (uint32_t u = blockIdx.x * 4 + wave; u < a.n; u += gridDim.x * 4) {
@@ -102,7 +109,7 @@ __global__ __launch_bounds__(256) void held_count_kernel(const HeldArgs a) {
             const bool in = lane < hi - q0;
             const uint32_t q = q0 + lane, v = in ? a.colids[q] : 0u;
             const bool nb = in && v != u && (q == lo || a.colids[q - 1] != v), up = nb && v > u;
-            const bool is = in && held_is(a, u, v);
+            const bool is = in && held_is<FOREST>(a, u, v, q);
             nu += (uint32_t)__popcll(__ballot(nb));
             pu += (uint32_t)__popcll(__ballot(up));
             cu += (uint32_t)__popcll(__ballot(up && held_key(a, u, v) < a.T));
@@ -133,7 +140,11 @@ __global__ __launch_bounds__(256) void held_count_kernel(const HeldArgs a) {
     }
 }
 
-__global__ __launch_bounds__(256) void held_fill_kernel(const HeldArgs a) {
+__global__ __launch_bounds__(256) void held_count_kernel(const HeldArgs a) { held_count_rows<false>(a); }
+__global__ __launch_bounds__(256) void held_forest_count_kernel(const HeldArgs a) { held_count_rows<true>(a); }
+
+template <bool FOREST>
+__device__ __forceinline__ void held_fill_rows(const HeldArgs &a) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     for (uint32_t u = blockIdx.x * 4 + wave; u < a.n; u += gridDim.x * 4) {
         const uint32_t lo = a.rowptr[u], hi = a.rowptr[u + 1];
@@ -142,7 +153,7 @@ __global__ __launch_bounds__(256) void held_fill_kernel(const HeldArgs a) {
         for (uint32_t q0 = lo; q0 < hi; q0 += 64) {
             const bool in = lane < hi - q0;
             const uint32_t q = q0 + lane, v = in ? a.colids[q] : 0u;
-            const bool is = in && held_is(a, u, v);
+            const bool is = in && held_is<FOREST>(a, u, v, q);
             const bool pos = is && v > u && (q == lo || a.colids[q - 1] != v);
             const unsigned long long keep = __ballot(in && !is), take = __ballot(pos);
             if (in && !is) a.colids_out[kat + link_lanes_below(keep)] = v;
@@ -156,6 +167,9 @@ __global__ __launch_bounds__(256) void held_fill_kernel(const HeldArgs a) {
         }
     }
 }
+
+__global__ __launch_bounds__(256) void held_fill_kernel(const HeldArgs a) { held_fill_rows<false>(a); }
+__global__ __launch_bounds__(256) void held_forest_fill_kernel(const HeldArgs a) { held_fill_rows<true>(a); }
 
 // ---- pair scores ---------------------------------------------------------------------------------------------------------------
 struct PairArgs {

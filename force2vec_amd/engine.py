@@ -42,6 +42,9 @@ LinkInfo = namedtuple("LinkInfo", "seconds positives negatives candidates capped
 EdgeSplit = namedtuple("EdgeSplit", "rowptr colids held_u held_v neg_u neg_v")
 EdgeSplitDetails = namedtuple("EdgeSplitDetails", "rowptr colids held_u held_v neg_u neg_v info")
 SplitInfo = namedtuple("SplitInfo", "seconds edges candidates_held protected held train_nnz negatives drawn capped")
+Components = namedtuple("Components", "sizes components isolated largest largest_label edges rounds seconds")
+Forest = namedtuple("Forest", "seconds edges forest_edges components rounds round_seconds")
+Subgraph = namedtuple("Subgraph", "rowptr colids ids new_id")
 Ranking = namedtuple("Ranking", "auc ap concordant tied positives negatives groups seconds")
 HeldoutScores = namedtuple("HeldoutScores", "auc ap classifier_auc classifier_ap")
 # Engine.communities, Engine.agreement (include/f2v.h: communities)
@@ -100,6 +103,7 @@ class Engine:
         self.last_fold_seconds = 0.0  # ... / fold_in call
         self.last_link_seconds = 0.0  # ... / link_pairs call (its count and its fill together)
         self.last_louvain_seconds = 0.0  # ... / communities call
+        self.last_components_seconds = self.last_forest_seconds = self.last_subgraph_seconds = 0.0  # ... / components, spanning_forest, subgraph call
 
     def _ck(self, rc):
         check(rc, self._L)  # the error text lives in the library that returned the code
@@ -696,27 +700,90 @@ class Engine:
         return (u, v, y, LinkInfo(seconds, info.positives, info.negatives, info.candidates, info.capped)) if details else (u, v, y)
 
     # -- held-out link prediction (include/f2v.h: definition) --
-    def edge_split(self, frac=0.2, seed=1, ratio=1, details=False):
+    def edge_split(self, frac=0.2, seed=1, ratio=1, details=False, keep="anchor"):
         """Hide a share of the edges (include/f2v.h: a keyed hash of the pair below frac, except every vertex's anchor edge) ->
         EdgeSplit(rowptr, colids: the training CSR; held_u, held_v: the hidden edges, u < v; neg_u, neg_v: `ratio` times as many
         non-edges of the full graph per vertex), with details=True also info = SplitInfo(seconds, edges, candidates_held, protected,
         held, train_nnz, negatives, drawn, capped).  A function of (CSR, frac, seed, ratio) alone; needs no embeddings.
+        keep="forest" (f2v_edge_split_connected) protects the greatest spanning forest of the seed's keys instead of the anchors: the
+        training graph then has exactly the components of the full graph, and no rule that keeps them hides more of the candidates.
         `last_split_seconds` keeps the device time."""
+        if keep not in ("anchor", "forest"):
+            raise ValueError('edge_split: keep must be "anchor" or "forest"')
+        call = self._L.f2v_edge_split if keep == "anchor" else self._L.f2v_edge_split_connected
         counts, info = [C.c_uint64() for _ in range(3)], _lib.SplitInfo()
         refs = [C.byref(x) for x in counts]
-        self._ck(self._L.f2v_edge_split(self._h, frac, seed, ratio, None, None, 0, None, None, 0, None, None, 0, *refs, C.byref(info)))
+        self._ck(call(self._h, frac, seed, ratio, None, None, 0, None, None, 0, None, None, 0, *refs, C.byref(info)))
         nnz, held, neg = (x.value for x in counts)
         seconds = info.seconds
         rowptr, colids = np.empty(self.n + 1, dtype=np.uint32), np.empty(nnz, dtype=np.uint32)
         hu, hv = np.empty(held, dtype=np.uint32), np.empty(held, dtype=np.uint32)
         nu, nv = np.empty(neg, dtype=np.uint32), np.empty(neg, dtype=np.uint32)
-        self._ck(self._L.f2v_edge_split(self._h, frac, seed, ratio, _u32(rowptr), _u32(colids), nnz, _u32(hu), _u32(hv), held, _u32(nu), _u32(nv), neg,
-                                        *refs, C.byref(info)))
+        self._ck(call(self._h, frac, seed, ratio, _u32(rowptr), _u32(colids), nnz, _u32(hu), _u32(hv), held, _u32(nu), _u32(nv), neg, *refs, C.byref(info)))
         self.last_split_seconds = seconds = seconds + info.seconds
         if not details:
             return EdgeSplit(rowptr, colids, hu, hv, nu, nv)
         return EdgeSplitDetails(rowptr, colids, hu, hv, nu, nv, SplitInfo(seconds, info.edges, info.candidates_held, info.protected_edges, info.held,
                                                                           info.train_nnz, info.negatives, info.drawn, info.capped))
+
+    # -- components, spanning forests and subgraphs (include/f2v.h: definition; functions of the CSR, and the seed, alone) --
+    def components(self, details=False):
+        """The connected components of the graph (undirected, duplicates collapsed, self-loops ignored) on the GPU -> labels uint32[n],
+        the smallest vertex id of each vertex's component, or with details=True (labels, Components(sizes uint32[n], components,
+        isolated, largest, largest_label, edges, rounds, seconds)).  Needs no embeddings.  `last_components_seconds` keeps the
+        device time."""
+        labels, sizes, info = np.empty(self.n, dtype=np.uint32), np.empty(self.n, dtype=np.uint32), _lib.ComponentsInfo()
+        self._ck(self._L.f2v_components(self._h, _u32(labels), _u32(sizes) if details else None, C.byref(info)))
+        self.last_components_seconds = info.seconds
+        if not details:
+            return labels
+        return labels, Components(sizes, info.components, info.isolated, info.largest, info.largest_label, info.edges, info.rounds, info.seconds)
+
+    def spanning_forest(self, seed=1, greatest=True, details=False):
+        """The spanning forest of the graph that Kruskal builds over the pairs in descending (greatest=True) or ascending order of
+        (key >> (64 - "forest_key_bits"), a, b), key the pair's hash of edge_split(seed) -> (u uint32[m], v uint32[m]), u < v,
+        ascending by (u, v), m = n - components; with details=True (u, v, Forest(seconds, edges, forest_edges, components, rounds,
+        round_seconds)).  Needs no embeddings.  `last_forest_seconds` keeps the device time."""
+        count, info = C.c_uint64(), _lib.ForestInfo()
+        u, v = np.empty(max(self.n, 1) - 1, dtype=np.uint32), np.empty(max(self.n, 1) - 1, dtype=np.uint32)  # (a forest has at most n - 1 pairs)
+        self._ck(self._L.f2v_spanning_forest(self._h, seed, 1 if greatest else 0, _u32(u), _u32(v), len(u), C.byref(count), C.byref(info)))
+        self.last_forest_seconds = info.seconds
+        u, v = u[:count.value].copy(), v[:count.value].copy()
+        if not details:
+            return u, v
+        rounds = C.c_uint32()
+        self._ck(self._L.f2v_forest_round_seconds(self._h, None, 0, C.byref(rounds)))
+        per_round = np.zeros(rounds.value, dtype=np.float64)
+        self._ck(self._L.f2v_forest_round_seconds(self._h, per_round.ctypes.data_as(_lib.f64p), rounds.value, C.byref(rounds)))
+        return u, v, Forest(info.seconds, info.edges, info.forest_edges, info.components, info.rounds, per_round)
+
+    def subgraph(self, keep):
+        """The subgraph induced on `keep` (a boolean mask of n entries, or a list of vertex ids), relabelled by rank: ascending old id,
+        ascending new id; duplicates and self-loops stay -> Subgraph(rowptr, colids, ids: the old id of each new row, new_id
+        uint32[n]: the new id of each old vertex, 0xFFFFFFFF where it is dropped).  `last_subgraph_seconds` keeps the device time."""
+        keep = np.asarray(keep)
+        if keep.dtype == np.bool_:
+            if keep.shape != (self.n,):
+                raise ValueError("subgraph: a mask has one entry per vertex")
+            mask = keep.astype(np.uint8)
+        else:
+            ids = keep.astype(np.int64).reshape(-1)
+            if len(ids) and (ids.min() < 0 or ids.max() >= self.n):
+                raise ValueError("subgraph: vertex id out of range")
+            mask = np.zeros(self.n, dtype=np.uint8)
+            mask[ids] = 1
+        mask = np.ascontiguousarray(mask)
+        rows, nnz = C.c_uint32(), C.c_uint64()
+        self._ck(self._L.f2v_subgraph(self._h, mask.ctypes.data_as(_lib.u8p), None, None, 0, None, C.byref(rows), C.byref(nnz)))
+        rowptr, colids, new_id = np.empty(rows.value + 1, dtype=np.uint32), np.empty(nnz.value, dtype=np.uint32), np.empty(self.n, dtype=np.uint32)
+        self._ck(self._L.f2v_subgraph(self._h, mask.ctypes.data_as(_lib.u8p), _u32(rowptr), _u32(colids), nnz.value, _u32(new_id), C.byref(rows), C.byref(nnz)))
+        self.last_subgraph_seconds = self.get_param("last_subgraph_us") * 1e-6
+        return Subgraph(rowptr, colids, np.flatnonzero(mask).astype(np.uint32), new_id)
+
+    def largest_component(self):
+        """subgraph() of the largest component (ties to the lowest label) -> Subgraph."""
+        labels, info = self.components(details=True)
+        return self.subgraph(labels == info.largest_label)
 
     def pair_scores(self, u, v, metric="dot"):
         """The similarity of rows u[i] and v[i] of the matrix (metric: "dot" | "l2" | "cos", as `nearest` defines them) -> float32 [m],

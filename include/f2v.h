@@ -1009,6 +1009,104 @@ typedef struct {
 } f2v_ranking_t;
 F2V_API int f2v_ranking(f2v_handle h, const double *scores, const uint8_t *y, uint64_t m, f2v_ranking_t *out);
 
+/* ---- components and spanning forests ----------------------------------------------------------------------------------------------
+ * What the graph is made of: its connected components, a spanning forest of them under a keyed order, a hold-out split that the forest
+ * keeps connected, and the subgraph induced on a vertex set (the largest component, say).  All integers; every result is unique by its
+ * definition, so it is the same bits under every launch shape, schedule and handle.  The calls need no embeddings and run on the
+ * handle's stream as plain launches without in-grid waits or float atomics (integer atomics only: minima, maxima and sums, whose
+ * results do not depend on their order); they touch neither the matrices nor pending minibatches nor the rand() stream nor any later
+ * training result.
+ *   graph       the simple undirected graph f2v_modularity uses: a pair {a < b} is an edge iff (a, b) or (b, a) occurs as a nonzero;
+ *               duplicates collapse, self-loops are ignored.  A CSR that stores an edge in one direction only gives the answers of
+ *               its symmetric form.  Rows must be ascending (the cached check of f2v_link_pairs; F2V_EINVAL otherwise).
+ *
+ * f2v_components: labels_out[v] = the smallest vertex id in v's component; sizes_out[v] (may be NULL) = the size of that component.
+ *   info        components; isolated = the vertices with no neighbour but themselves (components of size 1); largest = the size of
+ *               the largest component and largest_label its label, ties to the lowest label; edges = the distinct pairs; rounds =
+ *               the hooking rounds run, the last of which found nothing to hook: with L(v) = v at first, a round takes P = L, lowers
+ *               P[max(L(u), L(v))] to min(L(u), L(v)) for every nonzero (u, v) with L(u) != L(v) -- all of them against the L the
+ *               round began with -- and sets L(v) = the root of v under P.  (L and P are minima, so `rounds` too is a function of the
+ *               graph alone.)  seconds: device time between events around the call's own launches.
+ *   Launches: per round one hook launch (a wavefront per row piece: rows longer than 256 nonzeros are cut into pieces of 256, each a
+ *   wavefront's of its own; 32-bit atomicMin), pointer-jumping launches until every vertex names its root (a launch moves a vertex up
+ *   to 16 steps; the host reads two words per launch) and a copy; then sizes by 32-bit atomic adds on the labels (one per distinct
+ *   label among a wavefront's non-roots) and one launch of counts.  The distinct pairs: a nonzero that differs from its predecessor
+ *   counts at its lower end, or at its upper end where the lower end's row does not hold it (binary search).  F2V_EINVAL: a null
+ *   handle, labels_out or info, rows not ascending.
+ *
+ * f2v_spanning_forest: S1, SE and key(a, b) = mix64(SE ^ (a * 2^32 | b)) are those of f2v_edge_split for the same seed.  bits =
+ * "forest_key_bits" (f2v_set_param, 1..64, default 64).  The order on the pairs is lexicographic on (key(a, b) >> (64 - bits), a, b):
+ * strict and total.  "forest_key_bits" is a DIAGNOSTIC knob: small values force key ties so that the (a, b) tie-break decides; it
+ * never affects which pairs are hold-out candidates.  greatest = 0: the least forest, Kruskal over the pairs in ascending order;
+ * greatest = 1: the greatest forest, Kruskal in descending order.  Under a strict total order either is unique.  Output: the forest's
+ * pairs with u_out[i] < v_out[i], ascending by (u, v); *count_out = n - components.  With u_out and v_out both NULL only the count and
+ * info are written; with both given `cap` is what each holds: cap < count is F2V_EINVAL with *count_out written.  info: seconds,
+ * edges (the distinct pairs), forest_edges (= count), components, rounds.  F2V_EINVAL also for a null handle or count_out, one of the
+ * two outputs without the other, greatest > 1, rows not ascending.
+ *   Launches: Boruvka.  A round: every component finds its best outgoing pair under the order in two steps, because key and pair
+ *   together are 128 bits -- a wavefront per row piece (as above: hub rows do not serialise a round) reduces the shifted keys of the
+ *   nonzeros whose other end lies in another component and adds its maximum to the component's word (64-bit atomicMax; the least
+ *   forest maximises the complements), then, among the nonzeros that match the component's key, the packed pair the same way.  Where
+ *   the CSR is not structurally symmetric (checked once per handle, as f2v_louvain does) every such nonzero also proposes itself to
+ *   the other end's component, whose rows may not hold it.  Then every root that found a pair hooks to the root at the pair's other
+ *   end and appends the pair to the forest; two roots that chose the same pair are a mutual choice, broken towards the lower root, so
+ *   no cycle forms.  The labels are flattened by pointer jumping as above.  The loop ends with the round in which no component found
+ *   an outgoing pair (`rounds` counts it); every round scans all nonzeros.  The pairs are sorted (rocprim::radix_sort_keys).
+ *   f2v_forest_round_seconds: host wall time of each round of the handle's last forest (seconds_out may be NULL: the count only).
+ *
+ * f2v_edge_split_connected: the argument list, the f2v_split_t and the definition of f2v_edge_split but for the protection rule:
+ *   held        {a, b} is held iff it is a candidate (key(a, b) < T: the full 64-bit key, whatever "forest_key_bits") and is not in
+ *               the greatest forest of the same seed.  `protected_edges` counts the candidates the forest saved.  The forest is a
+ *               property of the pair: both stored directions and every duplicate decide alike, on a one-directional CSR too.
+ *   Negatives, the training CSR, the order of the results and the calling conventions are those of f2v_edge_split, with q(u) taken
+ *   from the new held set; as there, positives are listed, and `edges` and the candidates counted, from the rows as stored (v in N(u),
+ *   v > u).  THE TRAINING GRAPH HAS EXACTLY THE COMPONENTS OF THE FULL GRAPH: the forest spans every component and none of its pairs
+ *   is held.  NO CONNECTIVITY-PRESERVING RULE HOLDS MORE CANDIDATES: with 64 bits the candidates are a lower set of the order (key < T),
+ *   so Kruskal in descending order takes every non-candidate it can before the first candidate and uses a candidate only where no
+ *   non-candidate joins the two parts: as few candidates as any spanning forest can contain, and a training graph that keeps the
+ *   components must contain a spanning forest.  (f2v_edge_split, its anchors and its bits are unchanged.)
+ *   Launches: the forest as above (kept per handle for the last seed and "forest_key_bits": a second call with them does not run it
+ *   again), one launch that flags every nonzero whose pair is in the sorted forest (binary search: both stored directions and every
+ *   duplicate), then the launches of f2v_edge_split without the anchor launch, the decisions reading the flag.
+ *
+ * f2v_subgraph: keep u8[n], nonzero = kept.  The induced subgraph on the kept vertices, relabelled by rank among them: ascending old
+ * id gives ascending new id, so rows stay ascending; duplicates and self-loops are kept as stored.  rowptr_out u32[rows + 1] (rows =
+ * the number of kept vertices: the caller knows it), colids_out of `cap` entries, new_id_out u32[n] (may be NULL): the new id of v, or
+ * 0xFFFFFFFF where v is dropped.  *rows_out and *nnz_out are always written; with rowptr_out and colids_out both NULL nothing else is
+ * (count only; new_id_out is then not written either); cap < nnz is F2V_EINVAL with the counts written.  F2V_EINVAL also for a null
+ * handle, keep, rows_out or nnz_out, and one of the two arrays without the other.  Launches: a count (a wavefront per row), the 64-bit
+ * exclusive prefix sum of the link-pair code twice (new ids, row starts), a fill.  "last_subgraph_us" (f2v_get_param): its device time.
+ *
+ * Workspace of its own (no other call's buffers are used or resized), allocated on first use, grown for a larger call and freed by
+ * f2v_destroy: 12 bytes per piece of a row longer than 256 nonzeros; components 4 x 4 bytes per vertex; the forest 2 x 4 + 4 x 8 bytes
+ * per vertex plus the sort's, and 1 byte per nonzero for the split's flags; the subgraph 1 + 4 x 4 + 2 x 8 bytes per vertex, 8 per
+ * 1024 vertices and 4 (rows + 1 + nnz) of results. */
+typedef struct {
+    double seconds;          /* device time between events around the call's own launches */
+    uint64_t edges;          /* distinct pairs */
+    uint32_t components;
+    uint32_t isolated;       /* vertices with no neighbour but themselves */
+    uint32_t largest;        /* size of the largest component */
+    uint32_t largest_label;  /* ... and its label, ties to the lowest */
+    uint32_t rounds;
+} f2v_components_t;
+F2V_API int f2v_components(f2v_handle h, uint32_t *labels_out /* n */, uint32_t *sizes_out /* n, may be NULL */, f2v_components_t *info);
+typedef struct {
+    double seconds;
+    uint64_t edges;          /* distinct pairs */
+    uint64_t forest_edges;   /* n - components */
+    uint32_t components;
+    uint32_t rounds;
+} f2v_forest_t;
+F2V_API int f2v_spanning_forest(f2v_handle h, uint64_t seed, uint32_t greatest /* 0 | 1 */, uint32_t *u_out, uint32_t *v_out /* both NULL: count only */,
+                        uint64_t cap, uint64_t *count_out, f2v_forest_t *info /* may be NULL */);
+F2V_API int f2v_forest_round_seconds(f2v_handle h, double *seconds_out /* may be NULL */, uint32_t cap, uint32_t *count_out);
+F2V_API int f2v_edge_split_connected(f2v_handle h, double frac, uint64_t seed, uint32_t ratio, uint32_t *rowptr_train /* n + 1 */, uint32_t *colids_train,
+                             uint64_t cap_train, uint32_t *held_u, uint32_t *held_v, uint64_t cap_held, uint32_t *neg_u, uint32_t *neg_v,
+                             uint64_t cap_neg, uint64_t *train_nnz_out, uint64_t *held_out, uint64_t *negatives_out, f2v_split_t *info /* may be NULL */);
+F2V_API int f2v_subgraph(f2v_handle h, const uint8_t *keep /* n */, uint32_t *rowptr_out /* rows + 1 */, uint32_t *colids_out /* both NULL: count only */,
+                 uint64_t cap, uint32_t *new_id_out /* n, may be NULL */, uint32_t *rows_out, uint64_t *nnz_out);
+
 /* ---- communities ----------------------------------------------------------------------------------------------------------------
  * What the graph itself achieves, to hold the modularity of an embedding's clusters against: the reference colours its pictures by
  * the graph's communities and prints their modularity (performancescores/runvisualization.py:127-152) and sweeps k-means for the best
