@@ -122,8 +122,8 @@ static_assert(sizeof(PushExport) == F2V_PUSH_EXPORT_BYTES, "export blob layout")
 static_assert(kMaxRanks == F2V_PUSH_MAX_RANKS, "rank limit");
 constexpr uint32_t kPushMagic = 0x46325650u;  // "F2VP"
 
-// ---- what the scorers' host code shares: a grown-on-demand device buffer, a pair of timing events, and (further
-// down) settled_enter and allow_lds.  A new scorer uses these, it does not bring its own.
+// ---- what the host code shares: the owners of device memory, pinned memory and events, the resident plan arrays,
+// and (further down) settled_enter and allow_lds.  New host code uses these, it does not bring its own.
 #define F2VC(expr)                        \
     do {                                  \
         int rc__ = (expr);                \
@@ -131,7 +131,7 @@ constexpr uint32_t kPushMagic = 0x46325650u;  // "F2VP"
     } while (0)
 
 // A device array and the elements it holds: allocated on first use, grown (never shrunk, never rounded up) for a larger call, freed
-// with the handle (f2v_destroy has made the handle's device current by then)
+// with its owner -- the handle (f2v_destroy has made the handle's device current by then) or the call whose local it is
 template <class T>
 struct DevBuf {
     T *p = nullptr;
@@ -144,23 +144,83 @@ struct DevBuf {
     // Room for `count` elements.  Growing waits for the handle's stream first (launches may still read the old array) and leaves the
     // buffer empty where the allocation fails: "<what> workspace: <hip error>".
     int reserve(f2v_ctx *c, size_t count, const char *what);
+    // ... without a handle (a local of a call that takes a device number) or behind a wait the caller has made: no stream is waited for.
+    // `finegrained`: memory whose stores the peers of the push exchange see while a kernel runs (the flags)
+    int reserve(size_t count, const char *what, bool finegrained = false) {
+        if (p && cap >= count) return F2V_OK;
+        const hipError_t e = grow(count, finegrained);
+        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? F2V_ENOMEM : F2V_ENODEV, "%s workspace: %s", what, hipGetErrorString(e));
+        return F2V_OK;
+    }
+    // ... for a buffer the call can do without: did the device have room?  No error text is left behind.
+    bool try_reserve(size_t count) {
+        if (p && cap >= count) return true;
+        if (grow(count, false) == hipSuccess) return true;
+        (void)hipGetLastError();
+        return false;
+    }
     void release() {
         if (p) (void)hipFree(p);
         p = nullptr;
         cap = 0;
+    }
+
+private:
+    hipError_t grow(size_t count, bool finegrained) {  // the capacity is set where the allocation succeeded, and only there
+        release();
+        const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+        const hipError_t e = finegrained ? hipExtMallocWithFlags((void **)&p, bytes, hipDeviceMallocFinegrained) : hipMalloc((void **)&p, bytes);
+        if (e != hipSuccess) p = nullptr;
+        else cap = count;
+        return e;
+    }
+};
+
+// A pinned host array: what asynchronous copies read and write while the host goes on
+template <class T>
+struct HostBuf {
+    T *p = nullptr;
+    HostBuf() = default;
+    HostBuf(const HostBuf &) = delete;
+    HostBuf &operator=(const HostBuf &) = delete;
+    ~HostBuf() { release(); }
+    operator T *() const { return p; }
+    int reserve(size_t count) {  // once: a pinned array is never grown
+        if (!p) HIPC(hipHostMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault));
+        return F2V_OK;
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+    }
+};
+
+// A set of events, destroyed together: on every way out of the function whose local it is
+struct DevEvents {
+    std::vector<hipEvent_t> all;
+    DevEvents() = default;
+    DevEvents(const DevEvents &) = delete;
+    DevEvents &operator=(const DevEvents &) = delete;
+    ~DevEvents() { release(); }
+    int make(hipEvent_t *e, unsigned flags = hipEventDefault) {
+        hipEvent_t made = nullptr;
+        HIPC(hipEventCreateWithFlags(&made, flags));
+        all.push_back(*e = made);
+        return F2V_OK;
+    }
+    void release() {
+        for (hipEvent_t e : all) (void)hipEventDestroy(e);
+        all.clear();
     }
 };
 
 // Device time between two points of a stream: start, stop, and -- once the stream has been synchronised -- seconds
 struct DevTimer {
     hipEvent_t ev[2] = {nullptr, nullptr};
-    DevTimer() = default;
-    DevTimer(const DevTimer &) = delete;
-    DevTimer &operator=(const DevTimer &) = delete;
-    ~DevTimer() { release(); }
+    DevEvents made;
     int start(hipStream_t stream) {
         for (hipEvent_t &e : ev)
-            if (!e) HIPC(hipEventCreate(&e));
+            if (!e) F2VC(made.make(&e));
         HIPC(hipEventRecord(ev[0], stream));
         return F2V_OK;
     }
@@ -174,12 +234,30 @@ struct DevTimer {
         *sum += ms * 1e-3;
         return F2V_OK;
     }
-    void release() {
-        for (hipEvent_t &e : ev) {
-            if (e) (void)hipEventDestroy(e);
-            e = nullptr;
+};
+
+// One of the launch plans' arrays: the host's copy, which the planners append to, the device's, and how many elements of it are resident
+template <class T>
+struct PlanArray {
+    PlanVec<T> h;
+    DevBuf<T> d;
+    size_t resident = 0;
+    // Make everything appended so far resident (the caller has waited for the launches that read the array): an array that has
+    // outgrown the device's is given half as much again, at least `floor` elements, and copied whole; otherwise only its new tail is.
+    int upload(size_t floor) {
+        if (h.size() > d.cap) {
+            resident = 0;
+            F2VC(d.reserve(std::max<size_t>(h.size() * 3 / 2, floor), "launch plan"));
         }
+        if (h.size() > resident) HIPC(hipMemcpy(d + resident, h.data() + resident, (h.size() - resident) * sizeof(T), hipMemcpyHostToDevice));
+        resident = h.size();
+        return F2V_OK;
     }
+    void clear() {  // the device's array keeps its capacity
+        h.clear();
+        resident = 0;
+    }
+    size_t bytes() const { return h.size() * sizeof(T); }
 };
 
 struct f2v_ctx {
@@ -190,11 +268,12 @@ struct f2v_ctx {
     int vec = 1;
     bool exact = false;
     std::vector<uint32_t> rowptr, colids;  // host copies: hub planning, walk generation, statistics
-    uint32_t *d_rowptr = nullptr, *d_colids = nullptr, *d_walks = nullptr, *d_ids = nullptr;
-    uint32_t *d_walks_alt = nullptr;  // second walk buffer: f2v_train (option 7) alternates between the two, epoch by epoch
-    size_t ids_cap = 0, ids_valid = 0;  // ids_valid: prefix uploaded by f2v_upload_sample_ids
-    float *d_X[2] = {nullptr, nullptr}, *d_partials = nullptr, *d_table = nullptr;
-    uint32_t *d_ready = nullptr, *d_kerr = nullptr;  // combine-tree flags (one per partial slot), kernel error word
+    DevBuf<uint32_t> d_rowptr, d_colids, d_ids;
+    DevBuf<uint32_t> d_walk_buf[2];  // two walk buffers: f2v_train (option 7) alternates between them, epoch by epoch
+    uint32_t *d_walks = nullptr;     // ... and the one that holds the current walks (not an owner)
+    size_t ids_valid = 0;  // prefix of d_ids uploaded by f2v_upload_sample_ids
+    DevBuf<float> d_X[2], d_partials, d_table;  // (d_X: allocated once, by f2v_create -- their addresses are exported)
+    DevBuf<uint32_t> d_ready, d_kerr;  // combine-tree flags (one per partial slot), kernel error word
     uint32_t launch_seq = 0;
     uint32_t xcc_count = 0;      // XCDs seen by the dispatch probe of f2v_create
     bool xcc_round_robin = false;  // ... and workgroup b ran on the XCD of workgroup b mod 8
@@ -202,8 +281,8 @@ struct f2v_ctx {
     int64_t chain_timeout_ms = 200;  // chained launches: a healthy one lasts a millisecond or two, so a lost one is noticed in milliseconds
     // f2v_train survives a give-up ("recover"): the matrix and the rand() state as they were when the call began
     bool recover = true;
-    float *d_snap = nullptr;
-    hipEvent_t ev_snap[2] = {nullptr, nullptr};  // around the snapshot copy: f2v_stats.snapshot_seconds
+    DevBuf<float> d_snap;
+    DevTimer snap_timer;  // around the snapshot copy: f2v_stats.snapshot_seconds
     // in-grid waits that were switched off by a RECOVERED give-up come back by themselves: after `waits_backoff` healthy f2v_train
     // calls (1, then 2, 4 ... 64: a card that keeps losing launches is asked less and less often); a give-up that was not recovered
     // from, the dispatch probe's verdict and the caller's own "merge_finalize" = 0 stay
@@ -215,9 +294,9 @@ struct f2v_ctx {
     std::vector<double> marks;     // f2v_train_marks
     // the training objective (f2v_objective, "loss_every"): row-piece items (built once, from rowptr alone), one ObjPartial per
     // workgroup, and the results -- slot k < kLossLogMax: entry k of f2v_train's log, slot kLossLogMax: f2v_objective's
-    Item *d_obj_items = nullptr;
+    DevBuf<Item> d_obj_items;
     uint32_t obj_items = 0;
-    ObjPartial *d_obj_part = nullptr, *d_obj_out = nullptr;
+    DevBuf<ObjPartial> d_obj_part, d_obj_out;
     uint32_t loss_every = 0;                      // "loss_every"
     uint64_t loss_seed = 1;                       // "loss_seed"
     double last_loss_us = 0.0;                    // "last_loss_us"
@@ -378,13 +457,13 @@ struct f2v_ctx {
     bool last_wide_early = false;  // ... and whether it ran the kernel's EARLY form ("last_wide_early")
     int last_train_form = 0;  // how the last f2v_train launched: 0 one launch per minibatch, 1 chained, 2 chained in the wide form ("last_train_form")
     bool plan_overflow = false;  // a launch plan needed more than 2^28 partial-sum slots (kItemSlotMask)
-    uint32_t *h_kerr = nullptr;  // pinned: the kernel error words as of the last completed epoch-end copy (train_impl)
+    HostBuf<uint32_t> h_kerr;  // pinned: the kernel error words as of the last completed epoch-end copy (train_impl)
 #ifdef F2V_TEST_HOOKS
     struct Hooks {  // what include/f2v_test.h switches on (fill_hooks hands it to the launches)
         uint32_t withhold_slot = kNoSlot, withhold_row = kNoSlot;  // f2v_test_withhold_flag, f2v_test_withhold_row
         uint32_t chain_mode = 0;                 // f2v_test_chain_nowait's argument as given: bit 0 -- chained launches without their row waits (results are then wrong)
-        unsigned long long *d_xcd = nullptr;     // f2v_test_xcd_times (StepArgs::xcd_times)
-        unsigned long long *d_stamps = nullptr;  // f2v_test_stamps: 4 wall-clock words per row (StepArgs::stamps)
+        DevBuf<unsigned long long> d_xcd;        // f2v_test_xcd_times (StepArgs::xcd_times)
+        DevBuf<unsigned long long> d_stamps;     // f2v_test_stamps: 4 wall-clock words per row (StepArgs::stamps)
         uint32_t stub = 0;                       // f2v_test_interaction_stub (StepArgs::test_stub)
     } hooks;
 #endif
@@ -400,16 +479,11 @@ struct f2v_ctx {
     std::map<std::tuple<uint32_t, uint32_t, int>, Plan> plans;
     // chained minibatches ("chain_batches"): one launch per group of minibatches of f2v_train
     std::map<std::tuple<uint32_t, uint32_t, uint32_t, int>, ChainPlan> chains;  // (first minibatch, minibatches, batch size, walk samples instead of CSR neighbours)
-    std::vector<WgDesc> h_wg;
-    WgDesc *d_wg = nullptr;
-    size_t d_wg_cap = 0, d_wg_valid = 0;
+    PlanArray<WgDesc> plan_wg;
     // ... in the wide form ("chain_wide", the default where the fan-in allows it): workgroup programs and their jobs
     std::map<std::tuple<uint32_t, uint32_t, uint32_t, int>, WidePlan> wides;
-    PlanVec<WideDesc> h_wide;
-    PlanVec<WJob> h_jobs;
-    WideDesc *d_wide = nullptr;
-    WJob *d_jobs = nullptr;
-    size_t d_wide_cap = 0, d_wide_valid = 0, d_jobs_cap = 0, d_jobs_valid = 0;
+    PlanArray<WideDesc> plan_wide;
+    PlanArray<WJob> plan_jobs;
     bool wide = true;
     uint32_t wide_max_batch = 2048;  // larger chained minibatches are throughput-bound: they keep the HBM form (tools/wide_sweep.py)
     uint32_t wide_rows = 262144;     // rows one launch of the wide form covers ("chain_rows" is the HBM form's)
@@ -419,8 +493,8 @@ struct f2v_ctx {
     // "wide_epochs": up to this many EPOCHS of a small graph in one wide-form launch (WideArgs::wgs_per_epoch): ring of matrices, per-epoch
     // row flags / partial-sum slots / their flags; 0 = automatic (32 for graphs of up to 2 M nonzeros that fit one launch, else 1)
     uint32_t wide_epochs = 0, last_wide_epochs = 1;
-    float *d_ring = nullptr, *d_ring_partials = nullptr;
-    uint32_t *d_ring_flags = nullptr, *d_ring_ready = nullptr;
+    DevBuf<float> d_ring, d_ring_partials;
+    DevBuf<uint32_t> d_ring_flags, d_ring_ready;
     uint32_t ring_epochs = 0;   // epochs the ring buffers are sized for
     bool ring_refused = false;  // the device had no room for them
     size_t ring_slots = 0;      // partial-sum slots per epoch they are sized for
@@ -439,15 +513,12 @@ struct f2v_ctx {
     uint32_t wide_rounds = 0;   // rounds per phase of such a workgroup (0: one for minibatches of up to 512 rows, else as many as fill the piece slots)
     uint32_t wide_span = 2;     // fan-in groups per helper workgroup
     uint32_t wide_finish = 4;   // fan-in groups the finisher workgroup keeps for itself (the ones that wait longest)
-    uint32_t *d_rowflag = nullptr;  // per row: sequence number of the chained launch that last wrote it
+    DevBuf<uint32_t> d_rowflag;  // per row: sequence number of the chained launch that last wrote it
     bool chain = true;            // "chain_batches"
     uint32_t chain_max_batch = 4096, chain_rows = 65536;  // measured on RMAT-20 (tools/small_batch.py, tools/chain_sweep.py)
-    PlanVec<Item> h_items;
-    PlanVec<FinItem> h_hubs;
-    Item *d_items = nullptr;
-    FinItem *d_hubs = nullptr;
-    size_t d_items_cap = 0, d_hubs_cap = 0, d_items_valid = 0, d_hubs_valid = 0;
-    size_t partial_slots = 0, max_slots = 0;
+    PlanArray<Item> plan_items;
+    PlanArray<FinItem> plan_hubs;  // the nodes of the combine trees
+    size_t max_slots = 0;  // partial-sum slots the plans need (d_partials and d_ready hold at least as many)
     // rows [upd_lo, upd_hi) have been updated since the last swap/fold and live in d_X[cur^1]
     uint32_t upd_lo = 0, upd_hi = 0;
     bool pending = false;             // a minibatch has been stepped since the last flush
@@ -469,16 +540,16 @@ struct f2v_ctx {
         bool exported = false, attached = false, local = false;  // local: peers are handles of this process (self-test)
         uint32_t rank = 0, world = 1;
         float *peer_X[2][kMaxRanks] = {};
-        unsigned long long *flags = nullptr, *peer_flags[kMaxRanks] = {};
-        uint32_t *d_err = nullptr;
+        DevBuf<unsigned long long> flags;  // fine-grained, a fresh array per f2v_push_export (its address is exported)
+        unsigned long long *peer_flags[kMaxRanks] = {};
+        DevBuf<uint32_t> d_err;
         unsigned long long seq = 0;
         int64_t timeout_ms = 20000;
         bool fused = true;  // rows are pushed by the step / finalize kernels themselves ("push_fused" = 0: by a kernel after them)
         // reader masks: neighbour part cached per (batch, world), sampled vertices patched in per run
         std::vector<uint32_t> base_masks, patched_ids;
         uint32_t mask_batch = 0, mask_world = 0;
-        uint32_t *d_masks = nullptr, *d_patch = nullptr;
-        size_t patch_cap = 0;
+        DevBuf<uint32_t> d_masks, d_patch;
         uint64_t pushed_per_epoch = 0, rows_pushed = 0, rows_allgather = 0;
         bool any_shared = false, all_chain = true;  // over all attached ranks (f2v_push_attach): "replicate_small"
         // Landing-buffer mode: hipIpcOpenMemHandle never returns for an allocation of 2 GiB or more (ROCm 7.x), so a
@@ -486,7 +557,8 @@ struct f2v_ctx {
         // mapped buffer (two halves, alternating per exchange) and unpack_rows_kernel moves them into the matrix
         // behind the barrier.
         bool landing = false, force_landing = false;
-        float *landing_buf = nullptr, *peer_landing[kMaxRanks] = {};
+        DevBuf<float> landing_buf;  // a fresh one per f2v_push_export in this mode (its address is exported)
+        float *peer_landing[kMaxRanks] = {};
         uint32_t landing_cap = 0;  // rows per half
         uint32_t round = 0;        // exchanges done: (round & 1) is the half in use
     } push;
@@ -496,14 +568,7 @@ template <class T>
 int DevBuf<T>::reserve(f2v_ctx *c, size_t count, const char *what) {
     if (p && cap >= count) return F2V_OK;
     HIPC(hipStreamSynchronize(c->stream));
-    release();
-    hipError_t e = hipMalloc((void **)&p, std::max<size_t>(count, 1) * sizeof(T));
-    if (e != hipSuccess) {
-        p = nullptr;
-        return fail(e == hipErrorOutOfMemory ? F2V_ENOMEM : F2V_ENODEV, "%s workspace: %s", what, hipGetErrorString(e));
-    }
-    cap = count;
-    return F2V_OK;
+    return reserve(count, what);
 }
 
 namespace {
@@ -532,16 +597,20 @@ uint32_t auto_chunk(const f2v_ctx *c, uint32_t batch) {
 void drop_plans(f2v_ctx *c) {
     c->plans.clear();
     c->chains.clear();
-    c->h_wg.clear();
-    c->d_wg_valid = 0;
     c->wides.clear();
-    c->h_wide.clear();
-    c->h_jobs.clear();
-    c->d_wide_valid = c->d_jobs_valid = 0;
     c->max_slots = 0;
-    c->h_items.clear();
-    c->h_hubs.clear();
-    c->d_items_valid = c->d_hubs_valid = 0;
+    c->plan_wg.clear();
+    c->plan_wide.clear();
+    c->plan_jobs.clear();
+    c->plan_items.clear();
+    c->plan_hubs.clear();
+}
+
+int current_walks(f2v_ctx *c) {  // d_walks exists: the first walk buffer where none is current yet
+    if (c->d_walks) return F2V_OK;
+    F2VC(c->d_walk_buf[0].reserve((size_t)c->n * kWalkLength, "walks"));
+    c->d_walks = c->d_walk_buf[0];
+    return F2V_OK;
 }
 
 // Width of the sub-wave layout that serves this D -- the smallest of 16, 32, 64, 128, 256 that holds it, for any D that
@@ -692,11 +761,11 @@ const Plan &plan_for(f2v_ctx *c, uint32_t row_lo, uint32_t row_hi, bool walk) {
     const auto key = std::make_tuple(row_lo, row_hi, walk ? 1 : 0);
     auto itp = c->plans.find(key);
     if (itp != c->plans.end()) return itp->second;
-    if (c->h_items.size() > plan_cache_limit(c)) drop_plans(c);  // bound the cache
+    if (c->plan_items.h.size() > plan_cache_limit(c)) drop_plans(c);  // bound the cache
     constexpr uint32_t kXcds = 8;
     const uint32_t ipb = items_per_block(c), npb = (uint32_t)c->waves_per_block;
     Plan p;
-    p.item_off = c->h_items.size();
+    p.item_off = c->plan_items.h.size();
     std::vector<Item> whole;  // rows that stay one item
     whole.reserve(row_hi - row_lo);
     struct Node { uint32_t row, in_slot, n, cut; };  // cut: index of the row's first piece boundary in `cuts`
@@ -796,48 +865,48 @@ const Plan &plan_for(f2v_ctx *c, uint32_t row_lo, uint32_t row_hi, bool walk) {
         items.insert(items.end(), whole.begin() + wpos, whole.end());
         // the nodes' workgroups follow the items': their first one must again be a multiple of 8
         while (items.size() % ((size_t)kXcds * ipb) != 0) { items.push_back(pad_item); padded = true; }
-        p.fin_off[0] = c->h_hubs.size();
+        p.fin_off[0] = c->plan_hubs.h.size();
         size_t npos[kXcds] = {};
         for (bool more = true; more;) {
             more = false;
             for (uint32_t k = 0; k < kXcds; k++) {
-                for (uint32_t j = 0; j < npb; j++) c->h_hubs.push_back(npos[k] < nq[k].size() ? nq[k][npos[k]++] : pad_node);
+                for (uint32_t j = 0; j < npb; j++) c->plan_hubs.h.push_back(npos[k] < nq[k].size() ? nq[k][npos[k]++] : pad_node);
                 more = more || npos[k] < nq[k].size();
             }
         }
-        p.fin_cnt[0] = (uint32_t)(c->h_hubs.size() - p.fin_off[0]);
+        p.fin_cnt[0] = (uint32_t)(c->plan_hubs.h.size() - p.fin_off[0]);
         p.n_levels = 1;
         cur.swap(nxt);
     } else {
         items.insert(items.end(), whole.begin(), whole.end());
     }
-    const size_t items_at = c->h_items.size();
-    c->h_items.insert(c->h_items.end(), items.begin(), items.end());
+    const size_t items_at = c->plan_items.h.size();
+    c->plan_items.h.insert(c->plan_items.h.end(), items.begin(), items.end());
     p.n_items = (uint32_t)items.size();
     // upper levels: groups of `fanin` sums are added in order until one is left.  Their nodes are few (1/fanin of the
     // level below): wherever they wait, they cannot fill an XCD, so they are packed without regard to classes.
     while (!cur.empty() && p.n_levels < kMaxFinLevels) {
-        p.fin_off[p.n_levels] = c->h_hubs.size();
+        p.fin_off[p.n_levels] = c->plan_hubs.h.size();
         nxt.clear();
         for (const Node &nd : cur) {
             const uint32_t G = (p.n_levels == kMaxFinLevels - 1 || c->fanin < 2) ? nd.n : c->fanin;
             const uint32_t nout = (nd.n + G - 1) / G;
             if (nout == 1) {
-                c->h_hubs.push_back(FinItem{nd.in_slot, nd.n, kFinToStage, nd.row});
+                c->plan_hubs.h.push_back(FinItem{nd.in_slot, nd.n, kFinToStage, nd.row});
             } else {
                 for (uint32_t o = 0; o < nout; o++)
-                    c->h_hubs.push_back(FinItem{nd.in_slot + o * G, std::min(G, nd.n - o * G), slots + o, nd.row});
+                    c->plan_hubs.h.push_back(FinItem{nd.in_slot + o * G, std::min(G, nd.n - o * G), slots + o, nd.row});
                 nxt.push_back(Node{nd.row, slots, nout, 0});
                 slots += nout;
             }
         }
-        p.fin_cnt[p.n_levels] = (uint32_t)(c->h_hubs.size() - p.fin_off[p.n_levels]);
+        p.fin_cnt[p.n_levels] = (uint32_t)(c->plan_hubs.h.size() - p.fin_off[p.n_levels]);
         p.n_levels++;
         cur.swap(nxt);
     }
     if (padded) {  // the fillers' slot: one past every slot a node reads
         for (size_t k = items_at; k < items_at + p.n_items; k++)
-            if (c->h_items[k].cnt == 0 && c->h_items[k].flags == kItemPartial) c->h_items[k].flags = kItemPartial | slots;
+            if (c->plan_items.h[k].cnt == 0 && c->plan_items.h[k].flags == kItemPartial) c->plan_items.h[k].flags = kItemPartial | slots;
         slots++;
     }
     p.n_slots = slots;
@@ -890,14 +959,14 @@ const ChainPlan &chain_plan_for(f2v_ctx *c, uint32_t b0, uint32_t K, uint32_t ba
     const auto key = std::make_tuple(b0, K, batch, walk ? 1 : 0);
     auto itp = c->chains.find(key);
     if (itp != c->chains.end()) return itp->second;
-    if (c->h_items.size() > plan_cache_limit(c)) drop_plans(c);  // bound the cache
+    if (c->plan_items.h.size() > plan_cache_limit(c)) drop_plans(c);  // bound the cache
     const uint32_t ipb = items_per_block(c), npb = (uint32_t)c->waves_per_block;
     ChainPlan p;
     p.first_batch = b0;
     p.n_batches = K;
-    p.item_off = c->h_items.size();
-    p.fin_off = c->h_hubs.size();
-    p.wg_off = c->h_wg.size();
+    p.item_off = c->plan_items.h.size();
+    p.fin_off = c->plan_hubs.h.size();
+    p.wg_off = c->plan_wg.h.size();
     p.lo = (uint32_t)std::min<uint64_t>((uint64_t)b0 * batch, c->n);
     uint32_t slots = 0;
     struct DI { Item it; uint64_t dep; };
@@ -958,14 +1027,14 @@ const ChainPlan &chain_plan_for(f2v_ctx *c, uint32_t b0, uint32_t K, uint32_t ba
         WgDesc bd{};
         bd.lo = lo;
         p.last_lo = lo;
-        bd.item_off = (uint32_t)(c->h_items.size() - p.item_off);
+        bd.item_off = (uint32_t)(c->plan_items.h.size() - p.item_off);
         bd.n_items = (uint32_t)items.size();
         bd.step_blocks = bd.n_items / ipb;
-        bd.fin_off = (uint32_t)(c->h_hubs.size() - p.fin_off);
+        bd.fin_off = (uint32_t)(c->plan_hubs.h.size() - p.fin_off);
         bd.index = b0 + k;
-        const size_t wg_at = c->h_wg.size();  // (fin_n is known only below: the descriptors are patched then)
-        for (uint32_t w = 0; w < bd.step_blocks; w++) { bd.blk = w; c->h_wg.push_back(bd); }
-        for (const DI &d : items) c->h_items.push_back(d.it);
+        const size_t wg_at = c->plan_wg.h.size();  // (fin_n is known only below: the descriptors are patched then)
+        for (uint32_t w = 0; w < bd.step_blocks; w++) { bd.blk = w; c->plan_wg.h.push_back(bd); }
+        for (const DI &d : items) c->plan_items.h.push_back(d.it);
         // the combine trees of this minibatch's split rows, level by level (fan-in groups in chunk order, as plan_for)
         uint32_t fin_n = 0;
         for (int level = 0; !cur.empty(); level++) {
@@ -974,11 +1043,11 @@ const ChainPlan &chain_plan_for(f2v_ctx *c, uint32_t b0, uint32_t K, uint32_t ba
                 const uint32_t G = (level == kMaxFinLevels - 1 || c->fanin < 2) ? nd.n : c->fanin;
                 const uint32_t nout = (nd.n + G - 1) / G;
                 if (nout == 1) {
-                    c->h_hubs.push_back(FinItem{nd.in_slot, nd.n, kFinToStage, nd.row});
+                    c->plan_hubs.h.push_back(FinItem{nd.in_slot, nd.n, kFinToStage, nd.row});
                     fin_n++;
                 } else {
                     for (uint32_t o = 0; o < nout; o++) {
-                        c->h_hubs.push_back(FinItem{nd.in_slot + o * G, std::min(G, nd.n - o * G), slots + o, nd.row});
+                        c->plan_hubs.h.push_back(FinItem{nd.in_slot + o * G, std::min(G, nd.n - o * G), slots + o, nd.row});
                         fin_n++;
                     }
                     nxt.push_back(Node{nd.row, slots, nout});
@@ -987,14 +1056,14 @@ const ChainPlan &chain_plan_for(f2v_ctx *c, uint32_t b0, uint32_t K, uint32_t ba
             }
             cur.swap(nxt);
         }
-        while (fin_n % npb != 0) { c->h_hubs.push_back(FinItem{0, 0, kFinToStage, 0}); fin_n++; }
+        while (fin_n % npb != 0) { c->plan_hubs.h.push_back(FinItem{0, 0, kFinToStage, 0}); fin_n++; }
         bd.fin_n = fin_n;
         const uint32_t node_blocks = fin_n / npb;
         // (the nodes must directly follow their minibatch's items: later minibatches' items wait for the rows the roots write,
         // and a waiter may only ever wait for a SMALLER workgroup index -- letting the nodes trail by a few minibatches, so that
         // they poll less, was tried: it buys 3-9 % without the row waits and deadlocks with them, caught by the bounded waits)
-        for (uint32_t w = 0; w < node_blocks; w++) { bd.blk = bd.step_blocks + w; c->h_wg.push_back(bd); }
-        for (size_t w = wg_at; w < c->h_wg.size(); w++) c->h_wg[w].fin_n = fin_n;
+        for (uint32_t w = 0; w < node_blocks; w++) { bd.blk = bd.step_blocks + w; c->plan_wg.h.push_back(bd); }
+        for (size_t w = wg_at; w < c->plan_wg.h.size(); w++) c->plan_wg.h[w].fin_n = fin_n;
         p.n_wgs += bd.step_blocks + node_blocks;
         p.n_fin += fin_n;
         p.nnz += nnz;
@@ -1318,14 +1387,14 @@ WidePlan build_wide_plan(const f2v_ctx *c, uint32_t b0, uint32_t K, uint32_t bat
 
 // a built plan joins the handle's resident arrays
 const WidePlan &wide_plan_append(f2v_ctx *c, uint32_t b0, uint32_t K, uint32_t batch, bool walk, WidePlan p, const WideParts &parts) {
-    p.item_off = c->h_items.size();
-    p.fin_off = c->h_hubs.size();
-    p.wg_off = c->h_wide.size();
-    p.job_off = c->h_jobs.size();
-    c->h_items.insert(c->h_items.end(), parts.items.begin(), parts.items.end());
-    c->h_jobs.insert(c->h_jobs.end(), parts.jobs.begin(), parts.jobs.end());
-    c->h_wide.insert(c->h_wide.end(), parts.wide.begin(), parts.wide.end());
-    c->h_hubs.insert(c->h_hubs.end(), parts.hubs.begin(), parts.hubs.end());
+    p.item_off = c->plan_items.h.size();
+    p.fin_off = c->plan_hubs.h.size();
+    p.wg_off = c->plan_wide.h.size();
+    p.job_off = c->plan_jobs.h.size();
+    c->plan_items.h.insert(c->plan_items.h.end(), parts.items.begin(), parts.items.end());
+    c->plan_jobs.h.insert(c->plan_jobs.h.end(), parts.jobs.begin(), parts.jobs.end());
+    c->plan_wide.h.insert(c->plan_wide.h.end(), parts.wide.begin(), parts.wide.end());
+    c->plan_hubs.h.insert(c->plan_hubs.h.end(), parts.hubs.begin(), parts.hubs.end());
     // (the helpers' group sums are imported at 32-bit byte offsets: load16_agent)
     if (p.n_slots > kItemSlotMask || (uint64_t)p.n_slots * c->D * sizeof(float) > 0xFFFFFFFFull) c->plan_overflow = true;
     c->max_slots = std::max<size_t>(c->max_slots, p.n_slots);
@@ -1335,7 +1404,7 @@ const WidePlan &wide_plan_append(f2v_ctx *c, uint32_t b0, uint32_t K, uint32_t b
 const WidePlan &wide_plan_for(f2v_ctx *c, uint32_t b0, uint32_t K, uint32_t batch, bool walk) {
     auto itp = c->wides.find(std::make_tuple(b0, K, batch, walk ? 1 : 0));
     if (itp != c->wides.end()) return itp->second;
-    if (c->h_items.size() > plan_cache_limit(c)) drop_plans(c);
+    if (c->plan_items.h.size() > plan_cache_limit(c)) drop_plans(c);
     WideParts parts;
     const WidePlan p = build_wide_plan(c, b0, K, batch, walk, parts, c->seen_scratch);
     return wide_plan_append(c, b0, K, batch, walk, p, parts);
@@ -1350,7 +1419,7 @@ void wide_plans_for_epoch(f2v_ctx *c, uint32_t nb, uint32_t K, uint32_t batch, b
     for (uint32_t b0 = 0; b0 < nb; b0 += K)
         if (!c->wides.count(std::make_tuple(b0, std::min(K, nb - b0), batch, walk ? 1 : 0))) todo.push_back(b0);
     if (todo.empty()) return;
-    if (c->h_items.size() > plan_cache_limit(c)) {
+    if (c->plan_items.h.size() > plan_cache_limit(c)) {
         drop_plans(c);
         todo.clear();
         for (uint32_t b0 = 0; b0 < nb; b0 += K) todo.push_back(b0);
@@ -1380,18 +1449,18 @@ void wide_plans_for_epoch(f2v_ctx *c, uint32_t nb, uint32_t K, uint32_t batch, b
     const auto t_1 = std::chrono::steady_clock::now();
     // the resident arrays get their final size once (no regrowth copies), the parts are moved in by the threads -- side by side: every
     // part has its place (prefix sums of the sizes), and a part is released as soon as it has been copied
-    std::vector<size_t> at_items(todo.size() + 1, c->h_items.size()), at_jobs(todo.size() + 1, c->h_jobs.size()), at_wide(todo.size() + 1, c->h_wide.size()),
-        at_hubs(todo.size() + 1, c->h_hubs.size());
+    std::vector<size_t> at_items(todo.size() + 1, c->plan_items.h.size()), at_jobs(todo.size() + 1, c->plan_jobs.h.size()), at_wide(todo.size() + 1, c->plan_wide.h.size()),
+        at_hubs(todo.size() + 1, c->plan_hubs.h.size());
     for (size_t k = 0; k < todo.size(); k++) {
         at_items[k + 1] = at_items[k] + parts[k].items.size();
         at_jobs[k + 1] = at_jobs[k] + parts[k].jobs.size();
         at_wide[k + 1] = at_wide[k] + parts[k].wide.size();
         at_hubs[k + 1] = at_hubs[k] + parts[k].hubs.size();
     }
-    c->h_items.resize(at_items.back());
-    c->h_jobs.resize(at_jobs.back());
-    c->h_wide.resize(at_wide.back());
-    c->h_hubs.resize(at_hubs.back());
+    c->plan_items.h.resize(at_items.back());
+    c->plan_jobs.h.resize(at_jobs.back());
+    c->plan_wide.h.resize(at_wide.back());
+    c->plan_hubs.h.resize(at_hubs.back());
     const auto t_2 = std::chrono::steady_clock::now();
     next = 0;
     th.clear();
@@ -1399,10 +1468,10 @@ void wide_plans_for_epoch(f2v_ctx *c, uint32_t nb, uint32_t K, uint32_t batch, b
         th.emplace_back([&] {
             for (size_t k; (k = next.fetch_add(1)) < todo.size();) {
                 WideParts &q = parts[k];
-                if (!q.items.empty()) memcpy(c->h_items.data() + at_items[k], q.items.data(), q.items.size() * sizeof(Item));
-                if (!q.jobs.empty()) memcpy(c->h_jobs.data() + at_jobs[k], q.jobs.data(), q.jobs.size() * sizeof(WJob));
-                if (!q.wide.empty()) memcpy(c->h_wide.data() + at_wide[k], q.wide.data(), q.wide.size() * sizeof(WideDesc));
-                if (!q.hubs.empty()) memcpy(c->h_hubs.data() + at_hubs[k], q.hubs.data(), q.hubs.size() * sizeof(FinItem));
+                if (!q.items.empty()) memcpy(c->plan_items.h.data() + at_items[k], q.items.data(), q.items.size() * sizeof(Item));
+                if (!q.jobs.empty()) memcpy(c->plan_jobs.h.data() + at_jobs[k], q.jobs.data(), q.jobs.size() * sizeof(WJob));
+                if (!q.wide.empty()) memcpy(c->plan_wide.h.data() + at_wide[k], q.wide.data(), q.wide.size() * sizeof(WideDesc));
+                if (!q.hubs.empty()) memcpy(c->plan_hubs.h.data() + at_hubs[k], q.hubs.data(), q.hubs.size() * sizeof(FinItem));
                 q = WideParts{};
             }
         });
@@ -1421,7 +1490,7 @@ void wide_plans_for_epoch(f2v_ctx *c, uint32_t nb, uint32_t K, uint32_t batch, b
         const auto t_3 = std::chrono::steady_clock::now();
         auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
         fprintf(stderr, "f2v plan timing: %zu plans on %u threads: built %.0f ms, resident arrays sized %.0f ms, parts moved in %.0f ms (%.1f MB of items)\n", todo.size(), T, ms(t_0, t_1), ms(t_1, t_2),
-                ms(t_2, t_3), c->h_items.size() * sizeof(Item) / 1e6);
+                ms(t_2, t_3), c->plan_items.h.size() * sizeof(Item) / 1e6);
     }
 }
 
@@ -1433,90 +1502,29 @@ int upload_plans(f2v_ctx *c) {
         return fail(F2V_EINVAL, "a launch plan needs more than 2^28 partial-sum slots (or, in the wide form, 4 GiB of them): use a larger \"hub_chunk\" or fewer \"chain_rows\" / \"wide_rows\"");
     }
     const size_t need_slots = c->max_slots;
-    const bool grow_items = c->h_items.size() > c->d_items_cap, grow_hubs = c->h_hubs.size() > c->d_hubs_cap;
-    const bool grow_slots = need_slots > c->partial_slots;
-    if (c->h_items.size() == c->d_items_valid && c->h_hubs.size() == c->d_hubs_valid && c->h_wg.size() == c->d_wg_valid &&
-        c->h_wide.size() == c->d_wide_valid && c->h_jobs.size() == c->d_jobs_valid && !grow_slots)
+    const bool grow_slots = need_slots > c->d_ready.cap;  // (d_partials holds D floats for each of d_ready's slots)
+    if (c->plan_items.h.size() == c->plan_items.resident && c->plan_hubs.h.size() == c->plan_hubs.resident && c->plan_wg.h.size() == c->plan_wg.resident &&
+        c->plan_wide.h.size() == c->plan_wide.resident && c->plan_jobs.h.size() == c->plan_jobs.resident && !grow_slots)
         return F2V_OK;  // O(1) steady state
     HIPC(hipStreamSynchronize(c->stream));  // launches in flight read these buffers
     const auto t_up0 = std::chrono::steady_clock::now();
-    if (c->h_wide.size() > c->d_wide_cap) {
-        if (c->d_wide) (void)hipFree(c->d_wide);
-        c->d_wide = nullptr;
-        c->d_wide_cap = std::max<size_t>(c->h_wide.size() * 3 / 2, 1024);
-        HIPC(hipMalloc((void **)&c->d_wide, c->d_wide_cap * sizeof(WideDesc)));
-        c->d_wide_valid = 0;
-    }
-    if (c->h_wide.size() > c->d_wide_valid)
-        HIPC(hipMemcpy(c->d_wide + c->d_wide_valid, c->h_wide.data() + c->d_wide_valid, (c->h_wide.size() - c->d_wide_valid) * sizeof(WideDesc), hipMemcpyHostToDevice));
-    c->d_wide_valid = c->h_wide.size();
-    if (c->h_jobs.size() > c->d_jobs_cap) {
-        if (c->d_jobs) (void)hipFree(c->d_jobs);
-        c->d_jobs = nullptr;
-        c->d_jobs_cap = std::max<size_t>(c->h_jobs.size() * 3 / 2, 1024);
-        HIPC(hipMalloc((void **)&c->d_jobs, c->d_jobs_cap * sizeof(WJob)));
-        c->d_jobs_valid = 0;
-    }
-    if (c->h_jobs.size() > c->d_jobs_valid)
-        HIPC(hipMemcpy(c->d_jobs + c->d_jobs_valid, c->h_jobs.data() + c->d_jobs_valid, (c->h_jobs.size() - c->d_jobs_valid) * sizeof(WJob), hipMemcpyHostToDevice));
-    c->d_jobs_valid = c->h_jobs.size();
-    if (c->h_wg.size() > c->d_wg_cap) {
-        if (c->d_wg) (void)hipFree(c->d_wg);
-        c->d_wg = nullptr;
-        c->d_wg_cap = std::max<size_t>(c->h_wg.size() * 3 / 2, 1024);
-        HIPC(hipMalloc((void **)&c->d_wg, c->d_wg_cap * sizeof(WgDesc)));
-        c->d_wg_valid = 0;
-    }
-    if (c->h_wg.size() > c->d_wg_valid)
-        HIPC(hipMemcpy(c->d_wg + c->d_wg_valid, c->h_wg.data() + c->d_wg_valid, (c->h_wg.size() - c->d_wg_valid) * sizeof(WgDesc), hipMemcpyHostToDevice));
-    c->d_wg_valid = c->h_wg.size();
-    if (grow_items) {
-        if (c->d_items) (void)hipFree(c->d_items);
-        c->d_items = nullptr;
-        c->d_items_cap = std::max<size_t>(c->h_items.size() * 3 / 2, 1024);
-        HIPC(hipMalloc((void **)&c->d_items, c->d_items_cap * sizeof(Item)));
-        c->d_items_valid = 0;
-    }
-    if (grow_hubs) {
-        if (c->d_hubs) (void)hipFree(c->d_hubs);
-        c->d_hubs = nullptr;
-        c->d_hubs_cap = std::max<size_t>(c->h_hubs.size() * 3 / 2, 256);
-        HIPC(hipMalloc((void **)&c->d_hubs, c->d_hubs_cap * sizeof(FinItem)));
-        c->d_hubs_valid = 0;
-    }
+    F2VC(c->plan_wide.upload(1024));
+    F2VC(c->plan_jobs.upload(1024));
+    F2VC(c->plan_wg.upload(1024));
+    F2VC(c->plan_items.upload(1024));
+    F2VC(c->plan_hubs.upload(256));
     if (grow_slots) {
-        if (c->d_partials) (void)hipFree(c->d_partials);
-        c->d_partials = nullptr;
-        HIPC(hipMalloc((void **)&c->d_partials, need_slots * (size_t)c->D * sizeof(float)));
-        if (c->d_ready) (void)hipFree(c->d_ready);
-        c->d_ready = nullptr;
-        HIPC(hipMalloc((void **)&c->d_ready, need_slots * sizeof(uint32_t)));
+        F2VC(c->d_partials.reserve(need_slots * (size_t)c->D, "partial sums"));
+        F2VC(c->d_ready.reserve(need_slots, "partial sums"));
         // hipMemset on device memory may return before the fill has run (it is ordered on the NULL stream, which this
         // engine's non-blocking stream does not wait for): a late fill would wipe the first launch's flags
         HIPC(hipMemsetAsync(c->d_ready, 0, need_slots * sizeof(uint32_t), c->stream));
         HIPC(hipStreamSynchronize(c->stream));
-        c->partial_slots = need_slots;
     }
-    if (c->h_items.size() > c->d_items_valid)
-        HIPC(hipMemcpy(c->d_items + c->d_items_valid, c->h_items.data() + c->d_items_valid,
-                       (c->h_items.size() - c->d_items_valid) * sizeof(Item), hipMemcpyHostToDevice));
-    if (c->h_hubs.size() > c->d_hubs_valid)
-        HIPC(hipMemcpy(c->d_hubs + c->d_hubs_valid, c->h_hubs.data() + c->d_hubs_valid,
-                       (c->h_hubs.size() - c->d_hubs_valid) * sizeof(FinItem), hipMemcpyHostToDevice));
-    c->d_items_valid = c->h_items.size();
-    c->d_hubs_valid = c->h_hubs.size();
     if (getenv("F2V_PLAN_TIMING"))
-        fprintf(stderr, "f2v plan timing: upload %.0f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_up0).count());
-    return F2V_OK;
-}
-
-int reserve_ids(f2v_ctx *c, size_t count) {
-    if (count <= c->ids_cap) return F2V_OK;
-    HIPC(hipStreamSynchronize(c->stream));
-    if (c->d_ids) (void)hipFree(c->d_ids);
-    c->d_ids = nullptr;
-    HIPC(hipMalloc((void **)&c->d_ids, count * sizeof(uint32_t)));
-    c->ids_cap = count;
+        fprintf(stderr, "f2v plan timing: upload %.0f ms (resident: %zu items, %zu tree nodes, %zu chain workgroups, %zu wide workgroups, %zu jobs, %zu partial-sum slots)\n",
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_up0).count(), c->plan_items.d.cap, c->plan_hubs.d.cap,
+                c->plan_wg.d.cap, c->plan_wide.d.cap, c->plan_jobs.d.cap, c->d_ready.cap);
     return F2V_OK;
 }
 
@@ -1644,9 +1652,9 @@ int objective_prepare(f2v_ctx *c) {
         }
     }
     const uint32_t wgs = (uint32_t)((total + kObjItemsPerWg - 1) / kObjItemsPerWg);
-    HIPC(hipMalloc((void **)&c->d_obj_items, std::max<size_t>(total, 1) * sizeof(Item)));
-    HIPC(hipMalloc((void **)&c->d_obj_part, std::max<size_t>(wgs, 1) * sizeof(ObjPartial)));
-    HIPC(hipMalloc((void **)&c->d_obj_out, (kLossLogMax + 1) * sizeof(ObjPartial)));
+    F2VC(c->d_obj_part.reserve(wgs, "objective"));
+    F2VC(c->d_obj_out.reserve(kLossLogMax + 1, "objective"));
+    F2VC(c->d_obj_items.reserve(total, "objective"));  // (the last one: its presence says that all three exist)
     if (total) HIPC(hipMemcpy(c->d_obj_items, items.data(), total * sizeof(Item), hipMemcpyHostToDevice));
     c->obj_items = (uint32_t)total;
     return F2V_OK;
@@ -1759,7 +1767,7 @@ void fill_step_args(const f2v_ctx *c, StepArgs &a, int math, size_t item_off, ui
     a.rowptr = c->d_rowptr;
     a.nbr_ids = math == 7 ? c->d_walks : c->d_colids;
     a.partials = c->d_partials;
-    a.items = c->d_items + item_off;
+    a.items = c->plan_items.d + item_off;
     a.sm_table = c->d_table;
     a.D = c->D;
     a.upd_lo = upd_lo;
@@ -1868,7 +1876,7 @@ int launch_step(f2v_ctx *c, int math, uint32_t batch_lo, uint32_t batch_hi, uint
     // sub-wave kernel: the combine trees ride in the same grid (one launch per minibatch)
     const bool fused_tree = quarter && c->merge_fin && !c->capturing && plan.n_levels >= 1 && blocks > 0;
     if (fused_tree) {
-        a.fin_items = c->d_hubs + plan.fin_off[0];
+        a.fin_items = c->plan_hubs.d + plan.fin_off[0];
         a.fin_n = tree_nodes;
         arm_waits(c, a, false);
         blocks += (a.fin_n + wpb - 1) / wpb;
@@ -1895,7 +1903,7 @@ int launch_step(f2v_ctx *c, int math, uint32_t batch_lo, uint32_t batch_hi, uint
     const bool tree = !fused_tree && c->merge_fin && !c->capturing && plan.n_levels >= 2;
     if (tree) {
         FinalizeTreeArgs t{};
-        t.f = finalize_args(c, a, c->d_hubs + plan.fin_off[0], tree_nodes);
+        t.f = finalize_args(c, a, c->plan_hubs.d + plan.fin_off[0], tree_nodes);
         t.ready = c->d_ready;
         t.err = c->d_kerr;
         t.timeout_ticks = tree_timeout_ticks(c);
@@ -1909,7 +1917,7 @@ int launch_step(f2v_ctx *c, int math, uint32_t batch_lo, uint32_t batch_hi, uint
         HIPC(hipGetLastError());
     }
     for (int lev = 0; lev < plan.n_levels && !tree && !fused_tree; lev++) {
-        const FinalizeArgs f = finalize_args(c, a, c->d_hubs + plan.fin_off[lev], plan.fin_cnt[lev]);
+        const FinalizeArgs f = finalize_args(c, a, c->plan_hubs.d + plan.fin_off[lev], plan.fin_cnt[lev]);
         const uint32_t fb = (f.n_items + 3) / 4;
         rc = dispatch_math_layout(c, math, [&](auto O, auto V, auto E) {
             hipLaunchKernelGGL((hub_finalize_kernel<decltype(O)::value, decltype(V)::value, decltype(E)::value>), dim3(fb), dim3(256), 0, c->stream, f);
@@ -1925,7 +1933,7 @@ int launch_step(f2v_ctx *c, int math, uint32_t batch_lo, uint32_t batch_hi, uint
 template <class P>
 void fill_chain_args(f2v_ctx *c, StepArgs &a, int math, const P &plan, uint32_t ns, float lr, int bs_mode) {
     fill_step_args(c, a, math, plan.item_off, chain_upd_lo(c, plan.lo), ns, lr, bs_mode);
-    a.fin_items = c->d_hubs + plan.fin_off;
+    a.fin_items = c->plan_hubs.d + plan.fin_off;
     arm_waits(c, a, true);
     a.rowflag = c->d_rowflag;
     a.chain_lo = plan.lo;
@@ -1939,7 +1947,7 @@ int launch_chain(f2v_ctx *c, int math, const ChainPlan &plan, const uint32_t *d_
     if ((rc = flush_unless_continued(c, plan.lo)) != F2V_OK) return rc;
     ChainArgs ca{};
     fill_chain_args(c, ca.base, math, plan, ns, lr, bs_mode);
-    ca.wg = c->d_wg + plan.wg_off;
+    ca.wg = c->plan_wg.d + plan.wg_off;
     ca.ids = d_ids_epoch;
     ca.ids_stride = ids_stride;
     const uint32_t wpb = (uint32_t)c->waves_per_block;
@@ -1956,10 +1964,10 @@ int launch_chain(f2v_ctx *c, int math, const ChainPlan &plan, const uint32_t *d_
 }
 
 void free_ring(f2v_ctx *c) {
-    for (void *p : {(void *)c->d_ring, (void *)c->d_ring_partials, (void *)c->d_ring_flags, (void *)c->d_ring_ready})
-        if (p) (void)hipFree(p);
-    c->d_ring = c->d_ring_partials = nullptr;
-    c->d_ring_flags = c->d_ring_ready = nullptr;
+    c->d_ring.release();
+    c->d_ring_partials.release();
+    c->d_ring_flags.release();
+    c->d_ring_ready.release();
 }
 
 // One launch of the wide form (qwide_chain_kernel): minibatches [plan.first_batch, +plan.n_batches)
@@ -1982,11 +1990,8 @@ int launch_wide(f2v_ctx *c, int math, const WidePlan &plan, const uint32_t *d_id
 #ifdef F2V_TEST_HOOKS
         refuse = getenv("F2V_TEST_RING_REFUSE") != nullptr;  // fault injection: as if the device had no room for the ring
 #endif
-        if (refuse || hipMalloc((void **)&c->d_ring, (size_t)(cap + 1) * mat * sizeof(float)) != hipSuccess ||
-            hipMalloc((void **)&c->d_ring_partials, (size_t)cap * slots * c->D * sizeof(float)) != hipSuccess ||
-            hipMalloc((void **)&c->d_ring_flags, (size_t)cap * c->n * sizeof(uint32_t)) != hipSuccess ||
-            hipMalloc((void **)&c->d_ring_ready, (size_t)cap * slots * sizeof(uint32_t)) != hipSuccess) {
-            (void)hipGetLastError();
+        if (refuse || !c->d_ring.try_reserve((size_t)(cap + 1) * mat) || !c->d_ring_partials.try_reserve((size_t)cap * slots * c->D) ||
+            !c->d_ring_flags.try_reserve((size_t)cap * c->n) || !c->d_ring_ready.try_reserve((size_t)cap * slots)) {
             free_ring(c);
             c->ring_refused = true;  // (f2v_train stops asking)
             epochs = 1;
@@ -2020,8 +2025,8 @@ int launch_wide(f2v_ctx *c, int math, const WidePlan &plan, const uint32_t *d_id
         wa.ring_stride = matrix;
         wa.ids_epoch_stride = ids_epoch_stride;
     }
-    wa.wg = c->d_wide + plan.wg_off;
-    wa.jobs = c->d_jobs + plan.job_off;
+    wa.wg = c->plan_wide.d + plan.wg_off;
+    wa.jobs = c->plan_jobs.d + plan.job_off;
     wa.ids = d_ids_epoch;
     wa.ids_stride = ids_stride;
     // "wide_samples_early" (-1 = automatic): on for graphs of up to 2 M nonzeros, whose launches are one dependency chain
@@ -2185,7 +2190,7 @@ int prepare_masks(f2v_ctx *c, uint32_t batch, const std::vector<uint32_t> &ids) 
         int rc = f2v_push_masks(c->rowptr.data(), c->colids.data(), c->n, batch, P.world, nullptr, 0, P.base_masks.data());
         if (rc != F2V_OK) return rc;
         HIPC(hipStreamSynchronize(c->stream));
-        if (!P.d_masks) HIPC(hipMalloc((void **)&P.d_masks, (size_t)c->n * sizeof(uint32_t)));
+        F2VC(P.d_masks.reserve(c->n, "reader masks"));
         HIPC(hipMemcpy(P.d_masks, P.base_masks.data(), (size_t)c->n * sizeof(uint32_t), hipMemcpyHostToDevice));
         P.patched_ids.clear();
         P.mask_batch = batch;
@@ -2208,12 +2213,7 @@ int prepare_masks(f2v_ctx *c, uint32_t batch, const std::vector<uint32_t> &ids) 
     const uint32_t everyone = (P.world >= 32 ? 0xFFFFFFFFu : ((1u << P.world) - 1u));
     for (size_t k = 0; k < ns; k++) { h[2 * nr + k] = uniq[k]; h[2 * nr + ns + k] = everyone; }
     HIPC(hipStreamSynchronize(c->stream));
-    if (h.size() > P.patch_cap) {
-        if (P.d_patch) (void)hipFree(P.d_patch);
-        P.d_patch = nullptr;
-        P.patch_cap = h.size() * 2;
-        HIPC(hipMalloc((void **)&P.d_patch, P.patch_cap * sizeof(uint32_t)));
-    }
+    if (h.size() > P.d_patch.cap) F2VC(P.d_patch.reserve(h.size() * 2, "reader masks"));
     HIPC(hipMemcpy(P.d_patch, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     if (nr) hipLaunchKernelGGL(mask_patch_kernel, dim3((uint32_t)((nr + 255) / 256)), dim3(256), 0, c->stream, P.d_masks, P.d_patch, P.d_patch + nr, (uint32_t)nr);
     if (ns) hipLaunchKernelGGL(mask_patch_kernel, dim3((uint32_t)((ns + 255) / 256)), dim3(256), 0, c->stream, P.d_masks, P.d_patch + 2 * nr, P.d_patch + 2 * nr + ns, (uint32_t)ns);
@@ -2282,8 +2282,7 @@ int set_recover(f2v_ctx *c, int64_t value) {
     if (!c->recover && c->d_snap) {  // the snapshot matrix goes with the net
         HIPC(hipSetDevice(c->device));
         HIPC(hipStreamSynchronize(c->stream));
-        (void)hipFree(c->d_snap);
-        c->d_snap = nullptr;
+        c->d_snap.release();
     }
     return F2V_OK;
 }
@@ -2397,8 +2396,7 @@ const Param kParams[] = {
     {"last_wide_early", F2V_GET(last_wide_early)},
     {"last_wide_epochs", F2V_GET(last_wide_epochs)},
     // launch plans resident on the host (and, uploaded, in HBM): items, jobs, workgroup descriptors, tree nodes
-    {"plan_resident_bytes", [](const f2v_ctx *c) { return (int64_t)(c->h_items.size() * sizeof(Item) + c->h_jobs.size() * sizeof(WJob) + c->h_wide.size() * sizeof(WideDesc) +
-                                                                    c->h_wg.size() * sizeof(WgDesc) + c->h_hubs.size() * sizeof(FinItem)); }, nullptr},
+    {"plan_resident_bytes", [](const f2v_ctx *c) { return (int64_t)(c->plan_items.bytes() + c->plan_jobs.bytes() + c->plan_wide.bytes() + c->plan_wg.bytes() + c->plan_hubs.bytes()); }, nullptr},
     {"xcc_count", F2V_GET(xcc_count)},
     {"xcc_round_robin", F2V_GET(xcc_round_robin)},
     {"dim", F2V_GET(D)},
@@ -2458,12 +2456,17 @@ int f2v_create(const uint32_t *rowptr, const uint32_t *colids, uint32_t n, uint6
         if (e__ != hipSuccess)                                                                                       \
             return bail(fail(e__ == hipErrorOutOfMemory ? F2V_ENOMEM : F2V_ENODEV, "%s: %s", #expr, hipGetErrorString(e__))); \
     } while (0)
+#define F2VB(expr)                              \
+    do {                                        \
+        int rc__ = (expr);                      \
+        if (rc__ != F2V_OK) return bail(rc__);  \
+    } while (0)
     HIPB(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    HIPB(hipMalloc((void **)&c->d_rowptr, ((size_t)n + 1) * sizeof(uint32_t)));
-    HIPB(hipMalloc((void **)&c->d_colids, std::max<size_t>(nnz, 1) * sizeof(uint32_t)));
-    for (int k = 0; k < 2; k++) HIPB(hipMalloc((void **)&c->d_X[k], ((size_t)n + kPadRows) * dim * sizeof(float)));
-    HIPB(hipMalloc((void **)&c->d_table, kSmTableSize * sizeof(float)));
-    HIPB(hipMalloc((void **)&c->d_kerr, 64));
+    F2VB(c->d_rowptr.reserve((size_t)n + 1, "graph"));
+    F2VB(c->d_colids.reserve(nnz, "graph"));
+    for (int k = 0; k < 2; k++) F2VB(c->d_X[k].reserve(((size_t)n + kPadRows) * dim, "embedding"));
+    F2VB(c->d_table.reserve(kSmTableSize, "sigmoid table"));
+    F2VB(c->d_kerr.reserve(16, "kernel error words"));
     HIPB(hipMemsetAsync(c->d_kerr, 0, 64, c->stream));
     HIPB(hipStreamSynchronize(c->stream));
     HIPB(hipMemcpy(c->d_rowptr, rowptr, ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -2471,7 +2474,7 @@ int f2v_create(const uint32_t *rowptr, const uint32_t *colids, uint32_t n, uint6
     float table[kSmTableSize];
     sm_table_host(table);
     HIPB(hipMemcpy(c->d_table, table, sizeof table, hipMemcpyHostToDevice));
-    HIPB(hipHostMalloc((void **)&c->h_kerr, 4 * 64, hipHostMallocDefault));
+    F2VB(c->h_kerr.reserve(4 * 16));
     memset(c->h_kerr, 0, 4 * 64);
     if (const char *e = getenv("F2V_TREE_TIMEOUT_MS")) {
         const long ms = atol(e);
@@ -2487,13 +2490,13 @@ int f2v_create(const uint32_t *rowptr, const uint32_t *colids, uint32_t n, uint6
         // 8 XCDs taking workgroups round robin.  Checked here, on this device as this process sees it; if it does not
         // hold the handle starts with "merge_finalize" = 0 (one launch per tree level: no in-grid waits at all).
         constexpr uint32_t kProbe = 256;
-        uint32_t *d_x = nullptr, h_x[kProbe];
-        HIPB(hipMalloc((void **)&d_x, kProbe * sizeof(uint32_t)));
+        DevBuf<uint32_t> d_x;
+        uint32_t h_x[kProbe];
+        F2VB(d_x.reserve(kProbe, "dispatch probe"));
         hipLaunchKernelGGL(xcc_probe_kernel, dim3(kProbe), dim3(64), 0, c->stream, d_x);
         HIPB(hipGetLastError());
         HIPB(hipMemcpyAsync(h_x, d_x, sizeof h_x, hipMemcpyDeviceToHost, c->stream));
         HIPB(hipStreamSynchronize(c->stream));
-        (void)hipFree(d_x);
         uint32_t seen = 0;
         bool rr = true;
         for (uint32_t b = 0; b < kProbe; b++) {
@@ -2507,6 +2510,7 @@ int f2v_create(const uint32_t *rowptr, const uint32_t *colids, uint32_t n, uint6
         c->xcc_round_robin = rr && c->xcc_count == 8u;
         if (!c->xcc_round_robin) c->merge_fin = false;
     }
+#undef F2VB
 #undef HIPB
     *out = c;
     return F2V_OK;
@@ -2515,20 +2519,9 @@ int f2v_create(const uint32_t *rowptr, const uint32_t *colids, uint32_t n, uint6
 int f2v_destroy(f2v_handle c) {
     if (!c) return F2V_OK;
     (void)hipSetDevice(c->device);
-    (void)push_detach(c);
-    void *ptrs[] = {c->d_rowptr, c->d_colids, c->d_walks, c->d_walks_alt, c->d_ids, c->d_X[0], c->d_X[1],
-                    c->d_partials, c->d_table, c->d_items, c->d_hubs, c->d_ready, c->d_kerr, c->d_wg, c->d_rowflag, c->d_snap, c->d_wide, c->d_jobs, c->d_ring, c->d_ring_partials, c->d_ring_flags, c->d_ring_ready, c->d_obj_items, c->d_obj_part, c->d_obj_out, c->push.flags, c->push.d_err, c->push.d_masks, c->push.d_patch, c->push.landing_buf};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-#ifdef F2V_TEST_HOOKS
-    for (void *p : {(void *)c->hooks.d_stamps, (void *)c->hooks.d_xcd})
-        if (p) (void)hipFree(p);
-#endif
-    if (c->h_kerr) (void)hipHostFree(c->h_kerr);
-    for (hipEvent_t e : c->ev_snap)
-        if (e) (void)hipEventDestroy(e);
+    (void)push_detach(c);  // the peers' IPC mappings are closed before anything is freed
     const hipStream_t stream = c->stream;
-    delete c;  // the scorers' buffers and timers (DevBuf, DevTimer) go with it: before their stream, as every other buffer and event
+    delete c;  // every buffer, pinned array and event of the handle owns itself and goes with it: before their stream
     if (stream) (void)hipStreamDestroy(stream);
     return F2V_OK;
 }
@@ -2580,12 +2573,13 @@ int f2v_init_embeddings(f2v_handle c, int kind) {
         // Large matrices (8 GiB at RMAT-24): the one serial rand() stream is filled piece by piece into two pinned staging
         // buffers by the fill threads (jump-ahead states, bit-identical to the serial stream) while the previous piece
         // travels to HBM -- the pageable-memory copy of the whole matrix used to take longer than generating it.
-        float *stage[2] = {nullptr, nullptr};
+        HostBuf<float> stage[2];
+        DevEvents events;
         hipEvent_t done[2];
         bool used[2] = {false, false};
         for (int k = 0; k < 2; k++) {
-            HIPC(hipHostMalloc((void **)&stage[k], kPiece * sizeof(float), hipHostMallocDefault));
-            HIPC(hipEventCreateWithFlags(&done[k], hipEventDisableTiming));
+            F2VC(stage[k].reserve(kPiece));
+            F2VC(events.make(&done[k], hipEventDisableTiming));
         }
         int k = 0;
         for (size_t off = 0; off < total; off += kPiece, k ^= 1) {
@@ -2597,7 +2591,6 @@ int f2v_init_embeddings(f2v_handle c, int kind) {
             used[k] = true;
         }
         HIPC(hipStreamSynchronize(c->stream));
-        for (int j = 0; j < 2; j++) { (void)hipEventDestroy(done[j]); (void)hipHostFree(stage[j]); }
     } else {
         std::unique_ptr<float[]> x(new float[total]);  // not value-initialised: the fill threads are the first to touch it
         init_embeddings_host(c->rng, x.get(), total, kind);
@@ -2662,7 +2655,7 @@ int f2v_set_walks(f2v_handle c, const uint32_t *walks) {
     const size_t cnt = (size_t)c->n * kWalkLength;
     for (size_t k = 0; k < cnt; k++)
         if (walks[k] >= c->n) return fail(F2V_EINVAL, "f2v_set_walks: walks[%zu] = %u is not a vertex", k, walks[k]);
-    if (!c->d_walks) HIPC(hipMalloc((void **)&c->d_walks, cnt * sizeof(uint32_t)));
+    F2VC(current_walks(c));
     // stream-ordered after every step that still reads the previous epoch's walks
     HIPC(hipMemcpyAsync(c->d_walks, walks, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
@@ -2672,8 +2665,7 @@ int f2v_set_walks(f2v_handle c, const uint32_t *walks) {
 
 // non-parity walks generated in HBM (see fast_walks_kernel)
 static int fast_walks(f2v_ctx *c) {
-    const size_t cnt = (size_t)c->n * kWalkLength;
-    if (!c->d_walks) HIPC(hipMalloc((void **)&c->d_walks, cnt * sizeof(uint32_t)));
+    F2VC(current_walks(c));
     hipLaunchKernelGGL(fast_walks_kernel, dim3((c->n + 255) / 256), dim3(256), 0, c->stream, c->d_rowptr, c->d_colids, c->n, c->nnz,
                        c->d_walks, c->fast_seed * 0xD1342543DE82EF95ull + 5, c->fast_epoch++);
     HIPC(hipGetLastError());
@@ -2717,7 +2709,7 @@ int f2v_minibatch_step(f2v_handle c, int option, uint32_t batch_lo, uint32_t bat
     for (uint32_t k = 0; k < need; k++)
         if (sample_ids[k] >= c->n) return fail(F2V_EINVAL, "f2v_minibatch_step: sample id %u is not a vertex", sample_ids[k]);
     HIPC(hipSetDevice(c->device));
-    int rc = reserve_ids(c, std::max<size_t>(need, 64));
+    int rc = c->d_ids.reserve(c, std::max<size_t>(need, 64), "sample ids");
     if (rc != F2V_OK) return rc;
     // the previous step may still be reading d_ids: order the copy behind it on the stream
     c->ids_valid = 0;
@@ -2733,7 +2725,7 @@ int f2v_upload_sample_ids(f2v_handle c, const uint32_t *ids, uint64_t count) {
     for (uint64_t k = 0; k < count; k++)
         if (ids[k] >= c->n) return fail(F2V_EINVAL, "f2v_upload_sample_ids: id %u is not a vertex", ids[k]);
     HIPC(hipSetDevice(c->device));
-    int rc = reserve_ids(c, std::max<size_t>(count, 64));
+    int rc = c->d_ids.reserve(c, std::max<size_t>(count, 64), "sample ids");
     if (rc != F2V_OK) return rc;
     HIPC(hipStreamSynchronize(c->stream));  // steps in flight still read the previous ids
     if (count) HIPC(hipMemcpy(c->d_ids, ids, count * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -2831,7 +2823,7 @@ int f2v_rows_write(f2v_handle c, const uint32_t *ids, uint32_t count, const floa
 
 int f2v_embeddings_device_ptr(f2v_handle c, uint64_t *out) {
     if (!c || !out) return fail(F2V_EINVAL, "null argument");
-    *out = (uint64_t)(uintptr_t)c->d_X[c->cur];  // the whole matrix only after f2v_flush
+    *out = (uint64_t)(uintptr_t)c->d_X[c->cur].p;  // the whole matrix only after f2v_flush
     return F2V_OK;
 }
 
@@ -2876,24 +2868,18 @@ int f2v_train(f2v_handle c, int option, uint32_t iters, uint32_t batch, uint32_t
         int rc = flush_pending(c);
         if (rc != F2V_OK) return rc;
         const size_t bytes = (size_t)c->n * c->D * sizeof(float);
-        if (!c->d_snap && hipMalloc((void **)&c->d_snap, bytes) != hipSuccess) {
-            (void)hipGetLastError();  // no room for it: the call runs without the net
-            c->d_snap = nullptr;
-        }
-        if (c->d_snap) {
-            for (auto &e : c->ev_snap)
-                if (!e) HIPC(hipEventCreateWithFlags(&e, hipEventDefault));
-            HIPC(hipEventRecord(c->ev_snap[0], c->stream));
+        if (c->d_snap.try_reserve((size_t)c->n * c->D)) {  // (no room for it: the call runs without the net)
+            F2VC(c->snap_timer.start(c->stream));
             HIPC(hipMemcpyAsync(c->d_snap, c->d_X[c->cur], bytes, hipMemcpyDeviceToDevice, c->stream));
-            HIPC(hipEventRecord(c->ev_snap[1], c->stream));
+            F2VC(c->snap_timer.stop(c->stream));
             snap = true;
         }
     }
     const bool waits_before = c->merge_fin;
     int rc = train_impl(c, option, iters, batch, ns, lr, bs_mode, seconds_out, false);
-    if (snap && hipEventQuery(c->ev_snap[1]) == hipSuccess) {  // (train_impl has synchronised the stream on every healthy way out)
+    if (snap && hipEventQuery(c->snap_timer.ev[1]) == hipSuccess) {  // (train_impl has synchronised the stream on every healthy way out)
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, c->ev_snap[0], c->ev_snap[1]) == hipSuccess) snap_seconds = ms * 1e-3;
+        if (hipEventElapsedTime(&ms, c->snap_timer.ev[0], c->snap_timer.ev[1]) == hipSuccess) snap_seconds = ms * 1e-3;
     }
     (void)hipGetLastError();
     bool recovered = false;
@@ -3055,7 +3041,7 @@ int train_impl(f2v_ctx *c, int option, uint32_t iters, uint32_t batch, uint32_t 
     // reservation further down would hipFree the first, and hipFree waits for every stream of the device: with the ranks of a push
     // exchange as engines of ONE process (tools/push_world_local.py) that is a peer's spinning barrier kernel, which waits for this rank)
     const uint64_t dev_ids = std::max<uint64_t>(all_upfront ? per_epoch * std::max(iters, 1u) : 2 * per_epoch, 64);
-    if ((rc = reserve_ids(c, dev_ids)) != F2V_OK) return rc;
+    if ((rc = c->d_ids.reserve(c, dev_ids, "sample ids")) != F2V_OK) return rc;
     c->ids_valid = 0;
     std::vector<uint32_t> ids;
     auto draw_epoch = [&](std::vector<uint32_t> &v, size_t off) {
@@ -3075,7 +3061,7 @@ int train_impl(f2v_ctx *c, int option, uint32_t iters, uint32_t batch, uint32_t 
         }
     };
     if (chained && !c->d_rowflag) {
-        HIPC(hipMalloc((void **)&c->d_rowflag, (size_t)c->n * sizeof(uint32_t)));
+        F2VC(c->d_rowflag.reserve(c->n, "row flags"));
         HIPC(hipMemsetAsync(c->d_rowflag, 0, (size_t)c->n * sizeof(uint32_t), c->stream));  // 0 is no launch's sequence number
         HIPC(hipStreamSynchronize(c->stream));
     }
@@ -3099,15 +3085,7 @@ int train_impl(f2v_ctx *c, int option, uint32_t iters, uint32_t batch, uint32_t 
         d_masks = c->push.d_masks;
     }
     if (sharded) c->push.rows_pushed = c->push.rows_allgather = 0;
-    struct Events {  // destroyed on every way out of this function
-        std::vector<hipEvent_t> all;
-        int make(hipEvent_t *e, unsigned flags) {
-            HIPC(hipEventCreateWithFlags(e, flags));
-            all.push_back(*e);
-            return F2V_OK;
-        }
-        ~Events() { for (hipEvent_t e : all) (void)hipEventDestroy(e); }
-    } events;
+    DevEvents events;  // destroyed on every way out of this function
     hipEvent_t ev0, ev1;
     std::vector<hipEvent_t> mark_ev;  // "epoch_marks"
     c->marks.clear();
@@ -3207,17 +3185,17 @@ int train_impl(f2v_ctx *c, int option, uint32_t iters, uint32_t batch, uint32_t 
     // stream-ordered asynchronous copies into alternating device buffers, and nothing in the loop waits for the device.
     // Epoch time = max(host generation, device), instead of their sum plus two synchronisations.
     struct HostEpoch {
-        uint32_t *walks = nullptr, *ids = nullptr;  // pinned
-        hipEvent_t copied = nullptr;                // the H2D copies out of this slot have completed
+        HostBuf<uint32_t> walks, ids;
+        hipEvent_t copied = nullptr;  // the H2D copies out of this slot have completed (one of `events`)
         bool full = false, copy_pending = false;
-    } slot[2];
+    } slot[2];  // (declared before producer_guard: freed behind it, once the thread has ended and no copy reads them)
     std::mutex mu;
     std::condition_variable cv;
     std::thread producer;
     bool stop_producer = false;
     const bool host_walks = (math == 7 && !c->fast_rng);
     const bool produced = !all_upfront && !graphed && iters > 0;
-    uint32_t *d_walk_buf[2] = {nullptr, nullptr};
+    uint32_t *walks_at[2] = {nullptr, nullptr};  // the device's walk buffers: epoch `it` of this call uses walks_at[it & 1]
     auto end_producer = [&] {
         if (producer.joinable()) {
             { std::lock_guard<std::mutex> lk(mu); stop_producer = true; }
@@ -3225,30 +3203,24 @@ int train_impl(f2v_ctx *c, int option, uint32_t iters, uint32_t batch, uint32_t 
             producer.join();
         }
         if (slot[0].copy_pending || slot[1].copy_pending) (void)hipStreamSynchronize(c->stream);  // no copy still reads the pinned buffers
-        for (auto &sl : slot) {
-            if (sl.walks) (void)hipHostFree(sl.walks);
-            if (sl.ids) (void)hipHostFree(sl.ids);
-            if (sl.copied) (void)hipEventDestroy(sl.copied);
-            sl = HostEpoch{};
-        }
     };
     struct AtExit {
         std::function<void()> f;
         ~AtExit() { f(); }
-    } producer_guard{end_producer};  // every return below joins the thread and frees the pinned buffers
+    } producer_guard{end_producer};  // every return below joins the thread and waits for the copies out of the pinned buffers
     if (produced) {
         const size_t nwalk = (size_t)n * kWalkLength;
         if (host_walks) {
-            if (!c->d_walks) HIPC(hipMalloc((void **)&c->d_walks, nwalk * sizeof(uint32_t)));
-            if (!c->d_walks_alt) HIPC(hipMalloc((void **)&c->d_walks_alt, nwalk * sizeof(uint32_t)));
-            d_walk_buf[0] = c->d_walks;
-            d_walk_buf[1] = c->d_walks_alt;
+            for (auto &b : c->d_walk_buf) F2VC(b.reserve(nwalk, "walks"));
+            const int first = c->d_walks == c->d_walk_buf[1] ? 1 : 0;  // the current buffer takes the first epoch's walks
+            walks_at[0] = c->d_walk_buf[first];
+            walks_at[1] = c->d_walk_buf[first ^ 1];
         }
-        if ((rc = reserve_ids(c, std::max<uint64_t>(2 * per_epoch, 64))) != F2V_OK) return rc;
+        if ((rc = c->d_ids.reserve(c, std::max<uint64_t>(2 * per_epoch, 64), "sample ids")) != F2V_OK) return rc;
         for (auto &sl : slot) {
-            if (host_walks) HIPC(hipHostMalloc((void **)&sl.walks, nwalk * sizeof(uint32_t), hipHostMallocDefault));
-            HIPC(hipHostMalloc((void **)&sl.ids, std::max<size_t>(per_epoch, 1) * sizeof(uint32_t), hipHostMallocDefault));
-            HIPC(hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming));
+            if (host_walks) F2VC(sl.walks.reserve(nwalk));
+            F2VC(sl.ids.reserve(per_epoch));
+            F2VC(events.make(&sl.copied, hipEventDisableTiming));
         }
         const int dev = c->device;
         producer = std::thread([&, dev] {
@@ -3287,9 +3259,8 @@ int train_impl(f2v_ctx *c, int option, uint32_t iters, uint32_t batch, uint32_t 
             // stream-ordered behind epoch it-2's kernels, the last readers of these device buffers
             hipError_t he = hipSuccess;
             if (host_walks) {
-                he = hipMemcpyAsync(d_walk_buf[it & 1], sl.walks, (size_t)n * kWalkLength * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-                c->d_walks = d_walk_buf[it & 1];
-                c->d_walks_alt = d_walk_buf[(it & 1) ^ 1];
+                he = hipMemcpyAsync(walks_at[it & 1], sl.walks, (size_t)n * kWalkLength * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+                c->d_walks = walks_at[it & 1];
                 c->have_walks = true;
             }
             if (he == hipSuccess && per_epoch)
@@ -3507,15 +3478,7 @@ int train_exact(f2v_ctx *c, uint32_t iters, uint32_t batch, int bs_mode, double 
     c->stats = f2v_stats{};
     c->last_train_form = 0;
     c->last_wide_epochs = 1;
-    struct Events {  // destroyed on every way out of this function
-        std::vector<hipEvent_t> all;
-        int make(hipEvent_t *e) {
-            HIPC(hipEventCreateWithFlags(e, hipEventDefault));
-            all.push_back(*e);
-            return F2V_OK;
-        }
-        ~Events() { for (hipEvent_t e : all) (void)hipEventDestroy(e); }
-    } events;
+    DevEvents events;  // destroyed on every way out of this function
     hipEvent_t ev0, ev1;
     F2VC(events.make(&ev0));
     F2VC(events.make(&ev1));
@@ -6624,11 +6587,10 @@ int f2v_push_export(f2v_handle c, void *handles_out) {
     if (rc != F2V_OK) return rc;
     HIPC(hipStreamSynchronize(c->stream));
     // fresh, zeroed flags for every attachment: no peer can write them before it has seen this export
-    if (c->push.flags) (void)hipFree(c->push.flags);
-    c->push.flags = nullptr;
-    HIPC(hipExtMallocWithFlags((void **)&c->push.flags, 4096, hipDeviceMallocFinegrained));
+    c->push.flags.release();
+    F2VC(c->push.flags.reserve(4096 / sizeof(unsigned long long), "push flags", true));
     HIPC(hipMemset(c->push.flags, 0, 4096));
-    if (!c->push.d_err) HIPC(hipMalloc((void **)&c->push.d_err, 64));
+    F2VC(c->push.d_err.reserve(16, "push error words"));
     HIPC(hipMemset(c->push.d_err, 0, 64));
     HIPC(hipDeviceSynchronize());
     c->push.seq = 0;
@@ -6647,9 +6609,8 @@ int f2v_push_export(f2v_handle c, void *handles_out) {
         // two halves of at most 512 MiB; room for the self-test's `world` pattern rows in any case
         const size_t per_row = (size_t)c->D * sizeof(float);
         c->push.landing_cap = (uint32_t)std::max<size_t>(std::min<size_t>(((size_t)512 << 20) / per_row, (size_t)c->n + kPadRows), 64);
-        if (c->push.landing_buf) (void)hipFree(c->push.landing_buf);
-        c->push.landing_buf = nullptr;
-        HIPC(hipMalloc((void **)&c->push.landing_buf, 2 * (size_t)c->push.landing_cap * per_row));
+        c->push.landing_buf.release();
+        F2VC(c->push.landing_buf.reserve(2 * (size_t)c->push.landing_cap * c->D, "landing buffer"));
         HIPC(hipIpcGetMemHandle(&e.x[0], c->push.landing_buf));
     } else {
         for (int k = 0; k < 2; k++) HIPC(hipIpcGetMemHandle(&e.x[k], c->d_X[k]));
@@ -6825,10 +6786,10 @@ int f2v_test_wide_plan_check(const uint32_t *rowptr, const uint32_t *colids, uin
         uint32_t last_lo = 0;
         // pass 1: who produces which slot
         for (uint32_t wgi = 0; wgi < p.n_wgs; wgi++) {
-            const WideDesc &d = c->h_wide[p.wg_off + wgi];
+            const WideDesc &d = c->plan_wide.h[p.wg_off + wgi];
             if (d.kind == 0) {
                 for (uint32_t j = 0; j < d.d; j++) {
-                    const WJob &jb = c->h_jobs[p.job_off + d.c + j];
+                    const WJob &jb = c->plan_jobs.h[p.job_off + d.c + j];
                     if (jb.kind == kJobPart) {
                         if (jb.dst >= p.n_slots || producer[jb.dst] != -1) F2V_PLAN_FAIL("partial-sum slot %u produced twice or out of range", jb.dst);
                         producer[jb.dst] = 4 * (int64_t)wgi + 3;
@@ -6836,7 +6797,7 @@ int f2v_test_wide_plan_check(const uint32_t *rowptr, const uint32_t *colids, uin
                 }
             } else {
                 for (uint32_t w = 0; w < 4 && d.c * 4 + w < d.b; w++) {
-                    const FinItem &h = c->h_hubs[p.fin_off + d.a + d.c * 4 + w];
+                    const FinItem &h = c->plan_hubs.h[p.fin_off + d.a + d.c * 4 + w];
                     if (h.n == 0) continue;
                     if (h.out != kFinToStage) {
                         if (h.out >= p.n_slots || producer[h.out] != -1) F2V_PLAN_FAIL("tree node output slot %u produced twice or out of range", h.out);
@@ -6847,13 +6808,13 @@ int f2v_test_wide_plan_check(const uint32_t *rowptr, const uint32_t *colids, uin
         }
         // pass 2: every workgroup
         for (uint32_t wgi = 0; wgi < p.n_wgs; wgi++) {
-            const WideDesc &d = c->h_wide[p.wg_off + wgi];
+            const WideDesc &d = c->plan_wide.h[p.wg_off + wgi];
             if (d.lo < last_lo || d.lo < p.lo || d.lo >= p.hi) F2V_PLAN_FAIL("workgroup %u: minibatch at row %u out of order", wgi, d.lo);
             last_lo = d.lo;
             const uint32_t mb_hi = (uint32_t)std::min<uint64_t>((uint64_t)d.lo + batch, n);
             if (d.kind == 1) {
                 for (uint32_t w = 0; w < 4 && d.c * 4 + w < d.b; w++) {
-                    const FinItem &h = c->h_hubs[p.fin_off + d.a + d.c * 4 + w];
+                    const FinItem &h = c->plan_hubs.h[p.fin_off + d.a + d.c * 4 + w];
                     if (h.n == 0) continue;
                     for (uint32_t k = 0; k < h.n; k++)
                         if (h.in_slot + k >= p.n_slots || producer[h.in_slot + k] < 0 || producer[h.in_slot + k] >= 4 * (int64_t)wgi + w)
@@ -6865,8 +6826,8 @@ int f2v_test_wide_plan_check(const uint32_t *rowptr, const uint32_t *colids, uin
                 }
                 continue;
             }
-            const Item *items = c->h_items.data() + p.item_off + d.a;
-            const WJob *jobs = c->h_jobs.data() + p.job_off + d.c;
+            const Item *items = c->plan_items.h.data() + p.item_off + d.a;
+            const WJob *jobs = c->plan_jobs.h.data() + p.job_off + d.c;
             if (d.b == 0) F2V_PLAN_FAIL("workgroup %u has no round", wgi);
             // phases: rounds up to a round whose items carry kItemPhaseEnd
             std::vector<std::vector<const Item *>> phase_items(1);
@@ -6949,10 +6910,10 @@ int f2v_test_wide_plan_check(const uint32_t *rowptr, const uint32_t *colids, uin
             const unsigned char *q = static_cast<const unsigned char *>(p);
             for (size_t k = 0; k < bytes; k++) h = (h ^ q[k]) * 1099511628211ull;
         };
-        mix(c->h_items.data(), c->h_items.size() * sizeof(Item));
-        mix(c->h_jobs.data(), c->h_jobs.size() * sizeof(WJob));
-        mix(c->h_wide.data(), c->h_wide.size() * sizeof(WideDesc));
-        mix(c->h_hubs.data(), c->h_hubs.size() * sizeof(FinItem));
+        mix(c->plan_items.h.data(), c->plan_items.h.size() * sizeof(Item));
+        mix(c->plan_jobs.h.data(), c->plan_jobs.h.size() * sizeof(WJob));
+        mix(c->plan_wide.h.data(), c->plan_wide.h.size() * sizeof(WideDesc));
+        mix(c->plan_hubs.h.data(), c->plan_hubs.h.size() * sizeof(FinItem));
         st[6] = h;
     }
     if (stats_out) memcpy(stats_out, st, sizeof st);
@@ -6969,12 +6930,11 @@ int f2v_test_stamps(f2v_handle c, int on, unsigned long long *out) {
         HIPC(hipMemcpy(out, c->hooks.d_stamps, bytes, hipMemcpyDeviceToHost));
     }
     if (on) {
-        if (!c->hooks.d_stamps) HIPC(hipMalloc((void **)&c->hooks.d_stamps, bytes));
+        F2VC(c->hooks.d_stamps.reserve(4 * (size_t)c->n, "stamps"));
         HIPC(hipMemsetAsync(c->hooks.d_stamps, 0, bytes, c->stream));
         HIPC(hipStreamSynchronize(c->stream));
-    } else if (c->hooks.d_stamps) {
-        (void)hipFree(c->hooks.d_stamps);
-        c->hooks.d_stamps = nullptr;
+    } else {
+        c->hooks.d_stamps.release();
     }
     return F2V_OK;
 }
@@ -7061,11 +7021,11 @@ int f2v_test_gather_calibration(int device, uint32_t rows, uint32_t reps) {
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(F2V_ENODEV, "no HIP device visible");
     if (rows < 4) return fail(F2V_EINVAL, "rows");
     HIPC(hipSetDevice(device));
-    float *d_t = nullptr, *d_o = nullptr;
-    uint32_t *d_i = nullptr;
-    HIPC(hipMalloc((void **)&d_t, (size_t)rows * 128 * sizeof(float)));
-    HIPC(hipMalloc((void **)&d_i, (size_t)rows * sizeof(uint32_t)));
-    HIPC(hipMalloc((void **)&d_o, 64));
+    DevBuf<float> d_t, d_o;
+    DevBuf<uint32_t> d_i;
+    F2VC(d_t.reserve((size_t)rows * 128, "calibration"));
+    F2VC(d_i.reserve(rows, "calibration"));
+    F2VC(d_o.reserve(16, "calibration"));
     HIPC(hipMemset(d_t, 0, (size_t)rows * 128 * sizeof(float)));
     std::vector<uint32_t> perm(rows);
     for (uint32_t i = 0; i < rows; i++) perm[i] = i;
@@ -7077,7 +7037,6 @@ int f2v_test_gather_calibration(int device, uint32_t rows, uint32_t reps) {
         hipLaunchKernelGGL((gather_calibration_kernel<2>), dim3(4096), dim3(256), 0, 0, d_t, d_i, rows, d_o);
     HIPC(hipGetLastError());
     HIPC(hipDeviceSynchronize());
-    (void)hipFree(d_t); (void)hipFree(d_i); (void)hipFree(d_o);
     return F2V_OK;
 }
 
@@ -7089,13 +7048,12 @@ int f2v_test_xcd_times(f2v_handle c, int on, unsigned long long *out) {
     HIPC(hipStreamSynchronize(c->stream));
     if (out && c->hooks.d_xcd) HIPC(hipMemcpy(out, c->hooks.d_xcd, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     if (on) {
-        if (!c->hooks.d_xcd) HIPC(hipMalloc((void **)&c->hooks.d_xcd, 32 * sizeof(unsigned long long)));
+        F2VC(c->hooks.d_xcd.reserve(32, "XCD times"));
         unsigned long long init[32];
         for (int k = 0; k < 32; k++) init[k] = (k >= 8 && k < 16) ? ~0ull : 0ull;
         HIPC(hipMemcpy(c->hooks.d_xcd, init, sizeof init, hipMemcpyHostToDevice));
-    } else if (c->hooks.d_xcd) {
-        (void)hipFree(c->hooks.d_xcd);
-        c->hooks.d_xcd = nullptr;
+    } else {
+        c->hooks.d_xcd.release();
     }
     return F2V_OK;
 }
@@ -7111,26 +7069,23 @@ int f2v_test_plan_gather(f2v_handle c, uint32_t row_lo, uint32_t row_hi, uint32_
     if (rc != F2V_OK) return rc;
     const Plan plan = plan_for(c, row_lo, row_hi, false);
     if ((rc = upload_plans(c)) != F2V_OK) return rc;
-    float *d_o = nullptr;
-    HIPC(hipMalloc((void **)&d_o, 64));
-    hipEvent_t e0, e1;
-    HIPC(hipEventCreate(&e0));
-    HIPC(hipEventCreate(&e1));
+    DevBuf<float> d_o;
+    F2VC(d_o.reserve(16, "plan gather"));
+    DevTimer t;
     const uint32_t G = 1u << ((mode >> 2) & 3u);  // mode bits 2-3: a wavefront takes 1 / 2 / 4 / 8 consecutive groups of items
     const uint32_t blocks = ((plan.n_items + 16u * 8u * G - 1u) / (16u * 8u * G)) * 8u;  // (plan_gather_kernel: workgroup B takes the plan's workgroups B % 8 + 8 (G (B / 8) + k))
     float best = 1e30f;
     for (uint32_t r = 0; r < reps + 2; r++) {
-        HIPC(hipEventRecord(e0, c->stream));
-#define F2V_PG(GG) hipLaunchKernelGGL((plan_gather_kernel<16, 2, 4, GG>), dim3(blocks), dim3(256), 0, c->stream, c->d_X[c->cur], c->d_X[c->cur ^ 1], c->d_items + plan.item_off, plan.n_items, c->d_colids, mode & 3u, d_o)
+        F2VC(t.start(c->stream));
+#define F2V_PG(GG) hipLaunchKernelGGL((plan_gather_kernel<16, 2, 4, GG>), dim3(blocks), dim3(256), 0, c->stream, c->d_X[c->cur], c->d_X[c->cur ^ 1], c->plan_items.d + plan.item_off, plan.n_items, c->d_colids, mode & 3u, d_o)
         if (G == 1) F2V_PG(1); else if (G == 2) F2V_PG(2); else if (G == 4) F2V_PG(4); else F2V_PG(8);
 #undef F2V_PG
-        HIPC(hipEventRecord(e1, c->stream));
-        HIPC(hipEventSynchronize(e1));
+        F2VC(t.stop(c->stream));
+        HIPC(hipEventSynchronize(t.ev[1]));
         float ms = 0.f;
-        HIPC(hipEventElapsedTime(&ms, e0, e1));
+        HIPC(hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
         if (r >= 2 && ms < best) best = ms;
     }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(d_o);
     *us_out = best * 1e3;
     return F2V_OK;
 }
@@ -7147,12 +7102,12 @@ int f2v_diag_ipc_preflight(int device, uint32_t rank, uint32_t world, const char
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(F2V_ENODEV, "f2v_diag_ipc_preflight: device %d of %d", device, ndev);
     HIPC(hipSetDevice(device));
-    uint32_t *data = nullptr;
-    unsigned long long *flags = nullptr;
-    HIPC(hipMalloc((void **)&data, bytes));
+    DevBuf<uint32_t> data;
+    DevBuf<unsigned long long> flags;
+    F2VC(data.reserve((bytes + 3) / 4, "preflight"));
     HIPC(hipMemset(data, 0, 4096));
-    HIPC(hipMemset((char *)data + bytes - 4096, 0, 4096));
-    HIPC(hipExtMallocWithFlags((void **)&flags, 4096, hipDeviceMallocFinegrained));
+    HIPC(hipMemset((char *)data.p + bytes - 4096, 0, 4096));
+    F2VC(flags.reserve(4096 / sizeof(unsigned long long), "preflight flags", true));
     HIPC(hipMemset(flags, 0, 4096));
     HIPC(hipDeviceSynchronize());
     struct Blob { hipIpcMemHandle_t data, flags; } mine, theirs;
@@ -7214,8 +7169,6 @@ int f2v_diag_ipc_preflight(int device, uint32_t rank, uint32_t world, const char
         if (r != rank && !await("checked", r, &one, 1)) break;
     for (uint32_t r = 0; r < world; r++)
         if (r != rank) { (void)hipIpcCloseMemHandle(a.data[r]); (void)hipIpcCloseMemHandle(a.flags[r]); }
-    (void)hipFree(data);
-    (void)hipFree(flags);
     if (bad) return fail(F2V_ENODEV, "f2v_diag_ipc_preflight: %d of %u peers' stores did not arrive intact", bad, world);
     return F2V_OK;
 }
@@ -7242,28 +7195,24 @@ int f2v_diag_gather_rate(int device, uint64_t table_bytes, uint32_t reps, double
         const uint32_t rot = (uint32_t)(big() % rows);
         for (uint32_t i = 0; i < rows; i++) ids[(size_t)p * rows + i] = ids[(i + rot) % rows] ^ 0u;
     }
-    float *d_t = nullptr, *d_o = nullptr;
-    uint32_t *d_i = nullptr;
-    HIPC(hipMalloc((void **)&d_t, (size_t)rows * 512));
-    HIPC(hipMalloc((void **)&d_i, n_ids * sizeof(uint32_t)));
-    HIPC(hipMalloc((void **)&d_o, 64));
+    DevBuf<float> d_t, d_o;
+    DevBuf<uint32_t> d_i;
+    F2VC(d_t.reserve((size_t)rows * 128, "gather rate"));
+    F2VC(d_i.reserve(n_ids, "gather rate"));
+    F2VC(d_o.reserve(16, "gather rate"));
     HIPC(hipMemset(d_t, 0, (size_t)rows * 512));
     HIPC(hipMemcpy(d_i, ids.data(), n_ids * sizeof(uint32_t), hipMemcpyHostToDevice));
-    hipEvent_t e0, e1;
-    HIPC(hipEventCreate(&e0));
-    HIPC(hipEventCreate(&e1));
+    DevTimer t;
     double best = 0.0;
     for (uint32_t r = 0; r < reps + 2; r++) {
-        HIPC(hipEventRecord(e0, 0));
+        F2VC(t.start(0));
         hipLaunchKernelGGL((gather_calibration_kernel<2>), dim3(4096), dim3(256), 0, 0, d_t, d_i, (uint32_t)n_ids, d_o);
-        HIPC(hipEventRecord(e1, 0));
-        HIPC(hipEventSynchronize(e1));
+        F2VC(t.stop(0));
+        HIPC(hipEventSynchronize(t.ev[1]));
         float ms = 0.f;
-        HIPC(hipEventElapsedTime(&ms, e0, e1));
+        HIPC(hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
         if (r >= 2 && ms > 0.f) best = std::max(best, (double)n_ids * 516.0 / (ms * 1e-3) * 1e-9);
     }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    (void)hipFree(d_t); (void)hipFree(d_i); (void)hipFree(d_o);
     *gbps_out = best;
     return F2V_OK;
 }
@@ -7274,26 +7223,22 @@ int f2v_diag_stream_copy(int device, uint64_t bytes, uint32_t reps, double *gbps
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(F2V_ENODEV, "no such HIP device");
     HIPC(hipSetDevice(device));
-    float4 *a = nullptr, *b = nullptr;
-    HIPC(hipMalloc((void **)&a, bytes));
-    HIPC(hipMalloc((void **)&b, bytes));
+    DevBuf<f32x4_copy_t> a, b;
+    F2VC(a.reserve((bytes + 15) / 16, "stream copy"));
+    F2VC(b.reserve((bytes + 15) / 16, "stream copy"));
     HIPC(hipMemset(a, 1, bytes));
     HIPC(hipDeviceSynchronize());
-    hipEvent_t e0, e1;
-    HIPC(hipEventCreate(&e0));
-    HIPC(hipEventCreate(&e1));
+    DevTimer t;
     double best = 0.0;
     for (uint32_t r = 0; r < reps + 2; r++) {
-        HIPC(hipEventRecord(e0, 0));
-        hipLaunchKernelGGL((stream_copy_kernel<4>), dim3((uint32_t)((bytes / 16 + 1023) / 1024)), dim3(256), 0, 0, (const f32x4_copy_t *)a, (f32x4_copy_t *)b, (uint64_t)(bytes / 16));
-        HIPC(hipEventRecord(e1, 0));
-        HIPC(hipEventSynchronize(e1));
+        F2VC(t.start(0));
+        hipLaunchKernelGGL((stream_copy_kernel<4>), dim3((uint32_t)((bytes / 16 + 1023) / 1024)), dim3(256), 0, 0, a, b, (uint64_t)(bytes / 16));
+        F2VC(t.stop(0));
+        HIPC(hipEventSynchronize(t.ev[1]));
         float ms = 0.f;
-        HIPC(hipEventElapsedTime(&ms, e0, e1));
+        HIPC(hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
         if (r >= 2 && ms > 0.f) best = std::max(best, 2.0 * (double)bytes / (ms * 1e-3) * 1e-9);
     }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    (void)hipFree(a); (void)hipFree(b);
     *gbps_out = best;
     return F2V_OK;
 }
@@ -7304,16 +7249,14 @@ int f2v_test_wave_reduce(int device, const float *in, uint32_t rows, uint32_t wi
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(F2V_ENODEV, "no HIP device visible");
     HIPC(hipSetDevice(device));
-    float *d_in = nullptr, *d_out = nullptr;
-    HIPC(hipMalloc((void **)&d_in, (size_t)rows * width * sizeof(float)));
-    HIPC(hipMalloc((void **)&d_out, (size_t)rows * sizeof(float)));
+    DevBuf<float> d_in, d_out;
+    F2VC(d_in.reserve((size_t)rows * width, "wave reduce"));
+    F2VC(d_out.reserve(rows, "wave reduce"));
     HIPC(hipMemcpy(d_in, in, (size_t)rows * width * sizeof(float), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(wave_reduce_test_kernel, dim3((rows + 3) / 4), dim3(256), 0, 0, d_in, rows, width, d_out);
     HIPC(hipGetLastError());
     HIPC(hipDeviceSynchronize());
     HIPC(hipMemcpy(out, d_out, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost));
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
     return F2V_OK;
 }
 #endif  // F2V_TEST_HOOKS
