@@ -373,7 +373,8 @@ F2V_API int f2v_train_losses(f2v_handle h, uint32_t *epochs_out, double *values_
  *   F2V_SIM_L2      s = -chain_d fma(t_d, t_d, acc), t_d = q_d - c_d (one rounded subtraction) -- always from differences, never
  *                   |q|^2 + |c|^2 - 2 q.c: that form cancels for exactly the pairs a nearest-neighbour query is about;
  *   F2V_SIM_COSINE  s = (dot * r_q) * r_c (two rounded multiplications), dot as above, r_v = 1 / sqrt(n_v), n_v = chain_d fma(v_d, v_d,
- *                   acc), square root and division correctly rounded, r_v = 0 where n_v == 0.
+ *                   acc), square root and division correctly rounded, r_v = 0 where n_v == 0.  Where n_v overflows, r_v = 1 / sqrt(inf)
+ *                   = 0 by that very arithmetic: the score is a zero where dot is finite and a NaN where dot is infinite (inf x 0).
  * Subnormals are kept.  Ranking is a strict total order: score descending (-0 and +0 are one score), equal scores by ascending
  * vertex id, a NaN score below every number (NaNs among themselves by ascending id).  A query's result is the first k candidates of
  * that order after the exclusions; where fewer than k are left the tail holds id 0xFFFFFFFF and score -inf.  The result is a function
@@ -762,7 +763,9 @@ F2V_API int f2v_trustworthiness(f2v_handle h, const float *Y /* n x d2 */, uint3
  *   KL          = the sum over the nonzeros of p_ij * (flog(p_ij) - (flog((double)w) - flog(Z))) with P unexaggerated, flog the logarithm
  *               of "exact all-pairs Force2Vec" above, w and Z those of the Y the sum is asked for; a row's entries in pieces of 64 as in
  *               the attraction, the row sums in pieces of 64 rows as in Z.  Evaluated after the last iteration (info->kl, info->z) and
- *               after every kl_every-th (f2v_tsne_kl_log, 1-based iteration numbers).
+ *               after every kl_every-th (f2v_tsne_kl_log, 1-based iteration numbers).  A pair with a = inf has w = 0, outside flog's
+ *               domain: flog takes its steps on the bits of 0.0 all the same (k = -1023, m = 1) and returns -709.0895657128241, a
+ *               finite term.
  *
  * f2v_tsne_affinities returns P: rowptr_out m + 1 words, colids_out and values_out `cap` entries (2 m k always suffice); *nnz_out
  * answers also where cap is too small (F2V_EINVAL then).  f2v_tsne runs the iteration from P -- the caller's (all three arrays; its

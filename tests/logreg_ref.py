@@ -36,15 +36,17 @@ def features(X, a, b=None, feature=HADAMARD):
 
 
 def fma24(f, w, acc):
-    """round(f * w + acc) with one rounding, elementwise; f holds fp32 values (as float64), w and acc any doubles"""
+    """round(f * w + acc) with one rounding, elementwise; f holds fp32 values (as float64), w and acc any doubles.  An infinite or NaN
+    operand: the plain f * w + acc, which has the fma's value there (the error terms of the two-sum would be inf - inf)."""
     f, w, acc = np.broadcast_arrays(np.asarray(f, dtype=np.float64), np.asarray(w, dtype=np.float64), np.asarray(acc, dtype=np.float64))
-    wh = (np.ascontiguousarray(w).view(np.int64) & ~np.int64((1 << 27) - 1)).view(np.float64)
-    wl = w - wh                 # exact: at most 27 bits
-    ph, pl = f * wh, f * wl     # exact: 24 + 26 and 24 + 27 bits
-    s = ph + acc                # two-sum: s + e == ph + acc exactly
-    bb = s - ph
-    e = (ph - (s - bb)) + (acc - bb)
-    return s + (e + pl)
+    with np.errstate(invalid="ignore", over="ignore"):
+        wh = (np.ascontiguousarray(w).view(np.int64) & ~np.int64((1 << 27) - 1)).view(np.float64)
+        wl = w - wh                 # exact: at most 27 bits
+        ph, pl = f * wh, f * wl     # exact: 24 + 26 and 24 + 27 bits
+        s = ph + acc                # two-sum: s + e == ph + acc exactly
+        bb = s - ph
+        e = (ph - (s - bb)) + (acc - bb)
+        return np.where(np.isfinite(s), s + (e + pl), f * w + acc)
 
 
 def logits(F, W):
