@@ -36,6 +36,8 @@ non-neighbours per vertex, shuffled; deterministic, include/f2v.h) and `Engine.l
 Held-out link prediction: `Engine.edge_split(frac=0.2)` hides a share of the edges (and draws as many non-edges), an engine built on
 the returned training CSR is trained as usual, and its `heldout_scores(split)` ranks the hidden edges against the non-edges by the
 embedding's own similarity (`Engine.pair_scores`) -> ROC-AUC and average precision (`Engine.ranking`, sorted and tallied on the GPU).
+The yardstick beside it: `heldout_baselines(split)` ranks the same pairs by the classic neighbourhood scores of the training graph --
+common neighbours, Jaccard, Adamic-Adar, resource allocation, preferential attachment (`Engine.pair_neighbourhood`, on the GPU).
 
 What the graph itself achieves: `Engine.communities()` finds the graph's communities with the Louvain method on the GPU (integers only:
 the same labels on every run; `details=True` adds their modularity, the yardstick for `modularity(kmeans(k).labels)`), and

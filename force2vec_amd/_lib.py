@@ -190,6 +190,7 @@ SIGNATURES = {
     "f2v_subgraph": (C.c_int, [C.c_void_p, u8p, u32p, u32p, C.c_uint64, u32p, u32p, C.POINTER(C.c_uint64)]),
     "f2v_pair_scores": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint64, C.c_int, f32p, C.POINTER(C.c_double)]),
     "f2v_ranking": (C.c_int, [C.c_void_p, f64p, u8p, C.c_uint64, C.POINTER(RankingInfo)]),
+    "f2v_pair_neighbourhood": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint64, C.c_uint32, f64p, C.POINTER(C.c_double)]),
     "f2v_louvain": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, u32p, u32p, C.POINTER(LouvainLevel), C.POINTER(LouvainInfo)]),
     "f2v_partition_agreement": (C.c_int, [C.c_void_p, u32p, C.c_uint32, u32p, C.c_uint32, C.POINTER(AgreementInfo)]),
     "f2v_push_export": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -626,6 +626,26 @@ class algorithms {
         return HeldScores{own.auc, own.ap, clf.auc, clf.ap};
     }
 
+    // -holdout-baselines 1: the yardstick of heldOut.  The neighbourhood scores of the same pairs on the training graph (this object's
+    // handle: f2v_pair_neighbourhood), each kind ranked by f2v_ranking; prints, in kind order, "Held-out baseline(<cn|jaccard|aa|ra|pa>):
+    // <H> edges :AUC: <a> AP: <p>".  Computed as Engine.heldout_baselines computes them.
+    void heldOutBaselines(const Holdout &split) {
+        static const char *const names[] = {"cn", "jaccard", "aa", "ra", "pa"};
+        const size_t H = split.held_u.size(), m = H + split.neg_u.size();
+        std::vector<uint32_t> u(split.held_u), v(split.held_v);
+        u.insert(u.end(), split.neg_u.begin(), split.neg_u.end());
+        v.insert(v.end(), split.neg_v.begin(), split.neg_v.end());
+        std::vector<uint8_t> y(m, 0);
+        std::fill(y.begin(), y.begin() + H, (uint8_t)1);
+        std::vector<double> s(5 * m);
+        check(f2v_pair_neighbourhood(h, u.data(), v.data(), m, F2V_NB_ALL, s.data(), nullptr));
+        for (size_t k = 0; k < 5; k++) {
+            f2v_ranking_t r{};
+            check(f2v_ranking(h, s.data() + k * m, y.data(), m, &r));
+            printf("Held-out baseline(%s): %zu edges :AUC: %.17g AP: %.17g\n", names[k], H, r.auc, r.ap);
+        }
+    }
+
     // writeToFile, sample/algorithms.h:118-136 (file name rule in f2v_output_name)
     void writeToFile(int option, int bs, INDEXTYPE B, INDEXTYPE IT, INDEXTYPE ns) {
         char name[4096];

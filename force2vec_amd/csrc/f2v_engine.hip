@@ -43,6 +43,7 @@
 #include "f2v_foldin.hip.h"
 #include "f2v_linkpairs.hip.h"
 #include "f2v_heldout.hip.h"
+#include "f2v_neighbourhood.hip.h"
 #include "f2v_louvain.hip.h"
 #include "f2v_components.hip.h"
 #include "f2v_tsne.hip.h"
@@ -411,6 +412,18 @@ struct f2v_ctx {
         DevTimer timer;
         uint32_t pairs_chunk = 1u << 20;
     } held;
+    // neighbourhood scores of pairs (f2v_pair_neighbourhood): the workspace f2v.h states, allocated on first use and grown for a larger
+    // call; d_deg holds d(u) once degrees_built; "neighbourhood_spread" (1 | 0): the pieces of a pair of several pieces are work items
+    // of their own, or every pair is one wavefront's -- placement only
+    struct Neighbourhood {
+        DevBuf<uint32_t> d_deg, d_u, d_v, d_items_of, d_zero, d_piece_c;
+        DevBuf<unsigned long long> d_offset, d_tile, d_sums, d_item;
+        DevBuf<double> d_piece_aa, d_piece_ra, d_out;
+        DevTimer timer;
+        bool degrees_built = false;
+        bool spread = true;
+        uint64_t last_items = 0;  // "last_neighbourhood_items": the piece items of the last call
+    } nb;
     // communities (f2v_louvain, f2v_partition_agreement): the workspace f2v.h states, allocated on first use and grown for a larger call;
     // "louvain_short_max": the longest row of a unit that 16 lanes gather, "louvain_lds_slots": the largest table kept in LDS --
     // placement only.  rows_symmetric: -1 not checked yet (checked once per handle, on the device)
@@ -2375,6 +2388,9 @@ const Param kParams[] = {
     {"link_short_max", F2V_FIELD(link.short_max), kValue, kKeep, in<0, kLinkShortLimit>, "link_short_max must be 0..1024"},
     // f2v_pair_scores: pairs per upload and launch: bounds its workspace (12 bytes a pair); results do not depend on it
     {"pairs_chunk", F2V_FIELD(held.pairs_chunk), kValue, kKeep, in<1, 1 << 26>, "pairs_chunk must be 1..67108864"},
+    // f2v_pair_neighbourhood: 1 = the pieces of a pair whose S row has several are work items of their own, 0 = one wavefront walks them; placement only
+    {"neighbourhood_spread", F2V_FIELD(nb.spread), kFlag},
+    {"last_neighbourhood_items", F2V_GET(nb.last_items)},
     // f2v_louvain: a unit whose rows hold at most this many nonzeros is gathered by 16 lanes (table in LDS), a longer one by a workgroup; placement only
     {"louvain_short_max", F2V_FIELD(lv.short_max), kValue, kKeep, in<0, kLouvainShortLimit>, "louvain_short_max must be 0..256"},
     // f2v_louvain: the largest table (slots) a workgroup keeps in LDS; a longer one lies in the workspace; placement only
@@ -5142,6 +5158,116 @@ int f2v_ranking(f2v_handle c, const double *scores, const uint8_t *y, uint64_t m
     out->auc = (double)(2 * out->concordant + out->tied) / (2.0 * (double)P * (double)N);
     out->ap = sum / (double)P;
     out->seconds = seconds;
+    return F2V_OK;
+}
+
+}  // extern "C"
+
+// ---- neighbourhood scores of pairs (f2v_neighbourhood.hip.h; definition in include/f2v.h) -----------------------------------------
+extern "C" {
+
+int f2v_pair_neighbourhood(f2v_handle c, const uint32_t *u_ids, const uint32_t *v_ids, uint64_t m, uint32_t kinds, double *scores_out, double *seconds_out) {
+    if (!c) return fail(F2V_EINVAL, "f2v_pair_neighbourhood: null argument");
+    if (kinds == 0 || (kinds & ~(uint32_t)F2V_NB_ALL)) return fail(F2V_EINVAL, "f2v_pair_neighbourhood: kinds = 0x%x names no score or an unknown one", kinds);
+    if (seconds_out) *seconds_out = 0.0;
+    if (m == 0) return F2V_OK;
+    if (!u_ids || !v_ids || !scores_out) return fail(F2V_EINVAL, "f2v_pair_neighbourhood: null argument");
+    for (uint64_t i = 0; i < m; i++)
+        if (u_ids[i] >= c->n || v_ids[i] >= c->n)
+            return fail(F2V_EINVAL, "f2v_pair_neighbourhood: pair %llu = (%u, %u) names a vertex that is not one of the %u", (unsigned long long)i, u_ids[i], v_ids[i], c->n);
+    if (!rows_ascending(c)) return fail(F2V_EINVAL, "f2v_pair_neighbourhood: the CSR's column ids are not ascending inside every row (needed to search a row)");
+    HIPC(hipSetDevice(c->device));
+
+    f2v_ctx::Neighbourhood &w = c->nb;
+    const char *what = "neighbourhood scores";
+    const uint32_t n = c->n, nk = (uint32_t)__builtin_popcount(kinds), rows = std::min((n + 3) / 4, 8192u);
+    const bool search = (kinds & ~(uint32_t)F2V_NB_PREFERENTIAL) != 0, terms = (kinds & (F2V_NB_ADAMIC_ADAR | F2V_NB_RESOURCE)) != 0;
+    const uint64_t chunk = std::min<uint64_t>(c->held.pairs_chunk, m);
+    const uint32_t tiles = (uint32_t)((chunk + kLinkScanTile - 1) / kLinkScanTile);
+    F2VC(w.d_deg.reserve(c, n, what));
+    F2VC(w.d_u.reserve(c, chunk, what));
+    F2VC(w.d_v.reserve(c, chunk, what));
+    F2VC(w.d_out.reserve(c, chunk * nk, what));
+    if (search) {
+        F2VC(w.d_items_of.reserve(c, chunk, what));
+        F2VC(w.d_zero.reserve(c, chunk, what));
+        F2VC(w.d_offset.reserve(c, chunk, what));
+        F2VC(w.d_tile.reserve(c, tiles, what));
+        F2VC(w.d_sums.reserve(c, 1, what));
+    }
+    NbArgs a{};
+    a.rowptr = c->d_rowptr;
+    a.colids = c->d_colids;
+    a.deg = w.d_deg;
+    a.u = w.d_u;
+    a.v = w.d_v;
+    a.items_of = w.d_items_of;
+    a.zero = w.d_zero;
+    a.offset = w.d_offset;
+    a.sums = w.d_sums;
+    a.out = w.d_out;
+    a.n = n;
+    a.kinds = kinds;
+    a.spread = w.spread ? 1u : 0u;
+    LinkArgs l{};  // the scan of f2v_linkpairs.hip.h over the chunk's pairs
+    l.p = w.d_items_of;
+    l.total = w.d_zero;
+    l.offset = w.d_offset;
+    l.tile = w.d_tile;
+    double seconds = 0.0;
+    w.last_items = 0;
+    for (uint64_t i0 = 0; i0 < m; i0 += chunk) {
+        const uint32_t cm = (uint32_t)std::min<uint64_t>(chunk, m - i0), ctiles = (cm + kLinkScanTile - 1) / kLinkScanTile;
+        const dim3 per_pair(std::min((cm + 255u) / 256u, kNbThreadCap));
+        a.m = l.n = cm;
+        a.items = 0;
+        HIPC(hipMemcpyAsync(w.d_u, u_ids + i0, (size_t)cm * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIPC(hipMemcpyAsync(w.d_v, v_ids + i0, (size_t)cm * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        if (search) HIPC(hipMemsetAsync(w.d_sums, 0, sizeof(unsigned long long), c->stream));
+        F2VC(w.timer.start(c->stream));
+        if (!w.degrees_built) hipLaunchKernelGGL(nb_degree_kernel, dim3(rows), dim3(256), 0, c->stream, a);
+        if (search) {
+            hipLaunchKernelGGL(nb_count_kernel, per_pair, dim3(256), 0, c->stream, a);
+            hipLaunchKernelGGL(link_scan_tile_kernel, dim3(ctiles), dim3(256), 0, c->stream, l);
+            hipLaunchKernelGGL(link_scan_top_kernel, dim3(1), dim3(256), 0, c->stream, l, ctiles);
+            hipLaunchKernelGGL(link_scan_apply_kernel, dim3(ctiles), dim3(256), 0, c->stream, l);
+            HIPC(hipGetLastError());
+            F2VC(w.timer.stop(c->stream));
+            unsigned long long items = 0;
+            HIPC(hipMemcpyAsync(&items, w.d_sums, sizeof items, hipMemcpyDeviceToHost, c->stream));
+            HIPC(hipStreamSynchronize(c->stream));
+            F2VC(w.timer.seconds(&seconds));
+            w.degrees_built = true;
+            if (items) {
+                F2VC(w.d_item.reserve(c, items, what));
+                F2VC(w.d_piece_c.reserve(c, items, what));
+                F2VC(w.d_piece_aa.reserve(c, items, what));
+                F2VC(w.d_piece_ra.reserve(c, items, what));
+            }
+            a.items = items;
+            a.item = w.d_item;
+            a.piece_c = w.d_piece_c;
+            a.piece_aa = w.d_piece_aa;
+            a.piece_ra = w.d_piece_ra;
+            w.last_items += items;
+            const dim3 grid((unsigned)std::min<uint64_t>((items + cm + 3) / 4, kNbGridCap));
+            F2VC(w.timer.start(c->stream));
+            if (items) hipLaunchKernelGGL(nb_fill_kernel, per_pair, dim3(256), 0, c->stream, a);
+            if (terms) hipLaunchKernelGGL(nb_pair_kernel<true>, grid, dim3(256), 0, c->stream, a);
+            else hipLaunchKernelGGL(nb_pair_kernel<false>, grid, dim3(256), 0, c->stream, a);
+            if (items) hipLaunchKernelGGL(nb_finish_kernel, per_pair, dim3(256), 0, c->stream, a, 0u);
+        } else {
+            hipLaunchKernelGGL(nb_finish_kernel, per_pair, dim3(256), 0, c->stream, a, 1u);  // the degree product alone: nothing is searched
+        }
+        HIPC(hipGetLastError());
+        F2VC(w.timer.stop(c->stream));
+        for (uint32_t k = 0; k < nk; k++)
+            HIPC(hipMemcpyAsync(scores_out + (size_t)k * m + i0, w.d_out + (size_t)k * cm, (size_t)cm * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+        F2VC(w.timer.seconds(&seconds));
+        w.degrees_built = true;
+    }
+    if (seconds_out) *seconds_out = seconds;
     return F2V_OK;
 }
 

@@ -72,6 +72,8 @@ def _f1(true, pred, classes):
 
 
 METRICS = {"dot": _lib.SIM_DOT, "l2": _lib.SIM_L2, "cos": _lib.SIM_COSINE, "cosine": _lib.SIM_COSINE}
+# the kinds of f2v_pair_neighbourhood (F2V_NB_*), in the order of their bits: the order of the result arrays
+NEIGHBOURHOOD_KINDS = {"cn": 1, "jaccard": 2, "aa": 4, "ra": 8, "pa": 16}
 
 
 def _u32(a):
@@ -824,6 +826,36 @@ class Engine:
         model = self.logreg_fit(pairs=(tu, tv), y=ty.reshape(-1, 1), feature=feature, lam=lam, tol=tol, max_iter=max_iter)
         clf = self.ranking(self.logreg_decision(model, pairs=(u, v))[:, 0], y)
         return HeldoutScores(own.auc, own.ap, clf.auc, clf.ap)
+
+    # -- neighbourhood scores of pairs (include/f2v.h: definition; a function of the CSR, the pair and the kinds alone) --
+    def pair_neighbourhood(self, u, v, kinds=("cn", "jaccard", "aa", "ra", "pa")):
+        """The classic neighbourhood scores of the pairs (u[i], v[i]) on this engine's graph, on the GPU -> dict of name -> float64
+        [m] for the names in `kinds`: "cn" common neighbours, "jaccard", "aa" Adamic-Adar, "ra" resource allocation, "pa"
+        preferential attachment.  Needs no embeddings.  `last_neighbourhood_seconds` keeps the device time."""
+        u, v = np.ascontiguousarray(u, dtype=np.uint32).reshape(-1), np.ascontiguousarray(v, dtype=np.uint32).reshape(-1)
+        if len(u) != len(v):
+            raise ValueError("pair_neighbourhood: u and v must be two arrays of one length")
+        names = [kinds] if isinstance(kinds, str) else list(kinds)
+        unknown = [k for k in names if k not in NEIGHBOURHOOD_KINDS]
+        if unknown or not names:
+            raise ValueError("pair_neighbourhood: kinds are taken from %s" % ", ".join(NEIGHBOURHOOD_KINDS))
+        mask = 0
+        for k in names:
+            mask |= NEIGHBOURHOOD_KINDS[k]
+        asked = [k for k, bit in NEIGHBOURHOOD_KINDS.items() if mask & bit]  # ascending bit: the layout of the result
+        out, sec = np.empty((len(asked), len(u)), dtype=np.float64), C.c_double()
+        self._ck(self._L.f2v_pair_neighbourhood(self._h, _u32(u), _u32(v), len(u), mask, out.ctypes.data_as(_lib.f64p), C.byref(sec)))
+        self.last_neighbourhood_seconds = sec.value
+        return {k: out[asked.index(k)] for k in names}
+
+    def heldout_baselines(self, split, kinds=("cn", "jaccard", "aa", "ra", "pa")):
+        """The yardstick of `heldout_scores`.  Called on the engine that was built on split.rowptr / split.colids: scores the split's
+        hidden edges and its negatives by `pair_neighbourhood(kinds)` on the training graph and ranks each kind with `ranking`
+        -> dict of name -> Ranking.  Needs no embeddings."""
+        u = np.concatenate([split.held_u, split.neg_u]).astype(np.uint32)
+        v = np.concatenate([split.held_v, split.neg_v]).astype(np.uint32)
+        y = np.concatenate([np.ones(len(split.held_u), dtype=np.uint8), np.zeros(len(split.neg_u), dtype=np.uint8)])
+        return {k: self.ranking(s, y) for k, s in self.pair_neighbourhood(u, v, kinds).items()}
 
     # -- communities (include/f2v.h: definition; a function of the CSR, seed, max_levels and max_sweeps alone) --
     def communities(self, seed=1, max_levels=32, max_sweeps=64, details=False):

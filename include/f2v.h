@@ -1012,6 +1012,60 @@ typedef struct {
 } f2v_ranking_t;
 F2V_API int f2v_ranking(f2v_handle h, const double *scores, const uint8_t *y, uint64_t m, f2v_ranking_t *out);
 
+/* ---- neighbourhood scores of pairs ------------------------------------------------------------------------------------------------
+ * The yardstick of a held-out link prediction: the classic scores of a pair from the graph alone -- common neighbours, Jaccard,
+ * Adamic-Adar, resource allocation, preferential attachment -- computed on the training graph's handle for the hidden edges and the
+ * negatives and ranked by f2v_ranking like the embedding's own similarity.  The result is a function of (the CSR, the pair, kinds)
+ * alone: bitwise identical between calls, handles and GPUs and under every tunable; no float atomics.
+ *   graph       N(u) is that of the link prediction pairs: the distinct ids of CSR row u other than u itself; d(u) = |N(u)|.  Rows must
+ *               be ascending (checked once per handle).  The call needs no embeddings; it runs on the handle's stream as plain launches
+ *               without in-grid waits and touches neither the matrices nor pending minibatches nor the rand() stream nor any later
+ *               training result;
+ *   pair        any u, v < n; u == v is legal.  W(u, v) = N(u) n N(v), the common neighbours; no member of W is u or v;
+ *   S and L     S = the one of u, v whose STORED row has fewer nonzeros (rowptr[x + 1] - rowptr[x]), ties to the lower vertex id; L =
+ *               the other one; for u == v both are u.  S's stored row is cut into pieces of F2V_NB_PIECE = 1024 consecutive nonzeros:
+ *               duplicates and a self-loop keep their places;
+ *   kinds       bits, every value fp64, c = |W|:
+ *               F2V_NB_COMMON        (double)c, exact;
+ *               F2V_NB_JACCARD       (double)c / (double)(d(u) + d(v) - c), one rounded division; +0 where the denominator is 0;
+ *               F2V_NB_ADAMIC_ADAR   the sum over w in W of 1.0 / flog((double)d(w)), flog that of the exact objective (option 1); a
+ *                                    w with d(w) < 2 adds nothing (on a CSR that stores a nonzero in one direction only a common
+ *                                    neighbour can have d(w) of 0 or 1);
+ *               F2V_NB_RESOURCE      the sum over w in W of 1.0 / (double)d(w); a w with d(w) = 0 adds nothing;
+ *               F2V_NB_PREFERENTIAL  (double)d(u) * (double)d(v), one rounded multiplication;
+ *   order       of the two sums: a nonzero of S's stored row is a member of W iff it is the first of its run of equal ids, is
+ *               neither u nor v, and is in L's row.  Inside a piece the members' terms are added sequentially from +0 in ascending
+ *               position; the piece sums are added sequentially from +0 in ascending piece order.  A pair whose S row has at most 1024
+ *               nonzeros is therefore one plain sequential sum;
+ *   symmetry    every score of (u, v) equals that of (v, u) bit for bit: the choice of S is symmetric.
+ * scores_out holds popcount(kinds) arrays of m doubles, kind-major, in ascending order of the kinds' bits: with kinds = JACCARD | RESOURCE
+ * the Jaccard values are scores_out[0 .. m) and the resource-allocation values scores_out[m .. 2m).  seconds_out (may be NULL): device
+ * time between events around the call's own launches.  F2V_EINVAL for null pointers, kinds == 0 or a bit above 16, an id >= n (checked
+ * on the host before anything is uploaded: no kernel sees one) and rows that are not ascending.  m = 0 is F2V_OK and touches nothing.
+ * The call works on a handle without embeddings: it never returns F2V_ESTATE.
+ * Launches: d(u) for every vertex by one wavefront per row, once per handle, kept in n words of the handle's own.  Pairs are uploaded
+ * and run in chunks of "pairs_chunk" (see f2v_pair_scores); the chunk size never changes a bit.  Per chunk: one thread per pair counts
+ * the pair's pieces, the 64-bit exclusive prefix sum of the link-pair code gives the place of its first work item, one launch fills the
+ * item list, then one wavefront per work item (grid stride; at most 8192 workgroups of four wavefronts) takes a piece of a pair with
+ * several pieces, or a whole pair: 64 consecutive nonzeros of S's row a round, a lower-bound search of each lane's id in L's row (as
+ * many steps as the row length has bits, at most 32), a ballot for the round's members, every member lane its own two terms, and the
+ * terms added in ascending lane order, one cross-lane read per set bit.  A last launch, one thread per pair, adds the piece results
+ * of the pairs with several pieces in ascending piece order.  Only F2V_NB_PREFERENTIAL asked for: nothing is searched.  Neither
+ * Adamic-Adar nor resource allocation asked for: no term is formed.  "neighbourhood_spread" (f2v_set_param, default 1; 0: one wavefront
+ * walks all pieces of its pair) is placement only; "last_neighbourhood_items" reads the piece items of the last call.
+ * Workspace of its own (no other call's buffers are used or resized), allocated on first use, grown for a larger call and freed by
+ * f2v_destroy: 4 n bytes of degrees; per pair of a chunk 16 bytes of ids and counts, 8 of offset and 8 per kind asked for; 8 bytes
+ * per 1024 pairs of the prefix sum; 28 bytes per piece item. */
+#define F2V_NB_PIECE 1024
+#define F2V_NB_COMMON 1u
+#define F2V_NB_JACCARD 2u
+#define F2V_NB_ADAMIC_ADAR 4u
+#define F2V_NB_RESOURCE 8u
+#define F2V_NB_PREFERENTIAL 16u
+#define F2V_NB_ALL 31u
+F2V_API int f2v_pair_neighbourhood(f2v_handle h, const uint32_t *u_ids, const uint32_t *v_ids, uint64_t m, uint32_t kinds,
+                           double *scores_out /* popcount(kinds) arrays of m, kind-major, ascending bit */, double *seconds_out /* may be NULL */);
+
 /* ---- components and spanning forests ----------------------------------------------------------------------------------------------
  * What the graph is made of: its connected components, a spanning forest of them under a keyed order, a hold-out split that the forest
  * keeps connected, and the subgraph induced on a vertex set (the largest component, say).  All integers; every result is unique by its
