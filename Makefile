@@ -15,7 +15,7 @@ HIPFLAGS = --offload-arch=$(ARCH) $(CXXFLAGS) $(LIBFLAGS)
 LIB = force2vec_amd/libf2v.so
 # the same sources with the self-test hooks of include/f2v_test.h compiled in (tests/, tools/ only)
 TESTLIB = force2vec_amd/libf2v_selftest.so
-SRCS = $(CSRC)/f2v_engine.hip $(CSRC)/f2v_kernels.hip.h $(CSRC)/f2v_nearest.hip.h $(CSRC)/f2v_kmeans.hip.h $(CSRC)/f2v_index.hip.h $(CSRC)/f2v_logreg.hip.h $(CSRC)/f2v_separation.hip.h $(CSRC)/f2v_layout.hip.h $(CSRC)/f2v_exact.hip.h $(CSRC)/f2v_foldin.hip.h $(CSRC)/f2v_linkpairs.hip.h $(CSRC)/f2v_heldout.hip.h $(CSRC)/f2v_neighbourhood.hip.h $(CSRC)/f2v_louvain.hip.h $(CSRC)/f2v_components.hip.h $(CSRC)/f2v_tsne.hip.h $(CSRC)/f2v_host.cpp $(CSRC)/f2v_internal.h include/f2v.h $(CSRC)/libf2v.map
+SRCS = $(CSRC)/f2v_engine.hip $(CSRC)/f2v_kernels.hip.h $(CSRC)/f2v_nearest.hip.h $(CSRC)/f2v_kmeans.hip.h $(CSRC)/f2v_index.hip.h $(CSRC)/f2v_logreg.hip.h $(CSRC)/f2v_separation.hip.h $(CSRC)/f2v_layout.hip.h $(CSRC)/f2v_exact.hip.h $(CSRC)/f2v_foldin.hip.h $(CSRC)/f2v_linkpairs.hip.h $(CSRC)/f2v_heldout.hip.h $(CSRC)/f2v_neighbourhood.hip.h $(CSRC)/f2v_pairranks.hip.h $(CSRC)/f2v_louvain.hip.h $(CSRC)/f2v_components.hip.h $(CSRC)/f2v_tsne.hip.h $(CSRC)/f2v_host.cpp $(CSRC)/f2v_internal.h include/f2v.h $(CSRC)/libf2v.map
 
 all: $(LIB) $(TESTLIB) bin/Force2Vec bin/Force2Vec_selftest
 

@@ -38,6 +38,8 @@ the returned training CSR is trained as usual, and its `heldout_scores(split)` r
 embedding's own similarity (`Engine.pair_scores`) -> ROC-AUC and average precision (`Engine.ranking`, sorted and tallied on the GPU).
 The yardstick beside it: `heldout_baselines(split)` ranks the same pairs by the classic neighbourhood scores of the training graph --
 common neighbours, Jaccard, Adamic-Adar, resource allocation, preferential attachment (`Engine.pair_neighbourhood`, on the GPU).
+The harder question: `heldout_ranks(split)` places every hidden edge (u, v) among ALL vertices ordered by similarity to u, the training
+edges of u filtered out -> MRR, mean rank and Hits@K (`Engine.pair_ranks`: two exact counts per pair, no top-k, no limit on the rank).
 
 What the graph itself achieves: `Engine.communities()` finds the graph's communities with the Louvain method on the GPU (integers only:
 the same labels on every run; `details=True` adds their modularity, the yardstick for `modularity(kmeans(k).labels)`), and
@@ -56,7 +58,7 @@ from ._lib import FOLD_INIT_GIVEN, FOLD_INIT_MEAN, FOLD_INIT_RANDOM  # noqa: F40
 from ._lib import LOGREG_BLOCK, LOGREG_MAX_CLASSES, PAIR_AVERAGE, PAIR_HADAMARD, PAIR_L1, PAIR_L2  # noqa: F401
 from ._lib import NEAREST_EXCLUDE_NEIGHBOURS, NEAREST_EXCLUDE_SELF, NEAREST_MAX_K, NEAREST_PAD_ID, SIM_COSINE, SIM_DOT, SIM_L2  # noqa: F401
 from .engine import FoldInfo, LinkInfo, Pca, Trust  # noqa: F401
-from .engine import EdgeSplit, HeldoutScores, Ranking, SplitInfo  # noqa: F401
+from .engine import EdgeSplit, HeldoutScores, PairRanks, Ranking, SplitInfo  # noqa: F401
 from .engine import Agreement, Communities, LouvainLevel  # noqa: F401
 from .engine import Components, Forest, Subgraph  # noqa: F401
 from .engine import Engine, KMeans, LogregModel, Modularity, algorithms, output_name, push_masks, read_embd, read_embd_bin, sm_table, write_embd, write_embd_bin  # noqa: F401

@@ -99,6 +99,11 @@ class RankingInfo(C.Structure):  # f2v_ranking_t
                 ("negatives", C.c_uint64), ("groups", C.c_uint64), ("seconds", C.c_double)]
 
 
+class PairRanksInfo(C.Structure):  # f2v_pair_ranks_t
+    _fields_ = [("seconds", C.c_double), ("pairs", C.c_uint64), ("rank2_sum", C.c_uint64), ("mean_rank", C.c_double), ("mrr", C.c_double),
+                ("candidates", C.c_uint64), ("tied_pairs", C.c_uint64)]
+
+
 class ComponentsInfo(C.Structure):  # f2v_components_t
     _fields_ = [("seconds", C.c_double), ("edges", C.c_uint64), ("components", C.c_uint32), ("isolated", C.c_uint32), ("largest", C.c_uint32),
                 ("largest_label", C.c_uint32), ("rounds", C.c_uint32)]
@@ -191,6 +196,8 @@ SIGNATURES = {
     "f2v_pair_scores": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint64, C.c_int, f32p, C.POINTER(C.c_double)]),
     "f2v_ranking": (C.c_int, [C.c_void_p, f64p, u8p, C.c_uint64, C.POINTER(RankingInfo)]),
     "f2v_pair_neighbourhood": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint64, C.c_uint32, f64p, C.POINTER(C.c_double)]),
+    "f2v_pair_ranks": (C.c_int, [C.c_void_p, u32p, u32p, C.c_uint64, C.c_int, C.c_uint32, u32p, u32p, u32p, C.c_uint32, C.POINTER(C.c_uint64),
+                                 C.POINTER(PairRanksInfo)]),
     "f2v_louvain": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, u32p, u32p, C.POINTER(LouvainLevel), C.POINTER(LouvainInfo)]),
     "f2v_partition_agreement": (C.c_int, [C.c_void_p, u32p, C.c_uint32, u32p, C.c_uint32, C.POINTER(AgreementInfo)]),
     "f2v_push_export": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -646,6 +646,39 @@ class algorithms {
         }
     }
 
+    // -holdout-ranks <s>: the filtered rank of the hidden edges among all vertices (this object's handle, the training graph's:
+    // f2v_pair_ranks with both exclusions).  sample < 0: every hidden edge; 0 < sample < H: those of index floor(j H / sample).  Each
+    // edge {a, b} gives the pairs (a, b) and (b, a).  Writes "<embd output name>.rank", one line "u v greater equal" per pair (1-based
+    // ids), and prints "Held-out ranks(<metric>): <P> pairs :MRR: <m> MeanRank: <r> Hits@1: <a> Hits@10: <b> Hits@50: <c> Hits@100: <d>",
+    // the hits as fractions of P.  Computed as Engine.heldout_ranks computes them.
+    void heldOutRanks(const Holdout &split, int metric, const char *metric_name, long sample) {
+        const uint64_t H = split.held_u.size(), take = sample > 0 && (uint64_t)sample < H ? (uint64_t)sample : H;
+        std::vector<uint32_t> u, v;
+        u.reserve(2 * take);
+        v.reserve(2 * take);
+        for (uint64_t j = 0; j < take; j++) {
+            const uint64_t e = take == H ? j : (uint64_t)(((unsigned __int128)j * H) / take);
+            u.push_back(split.held_u[e]);
+            v.push_back(split.held_v[e]);
+            u.push_back(split.held_v[e]);
+            v.push_back(split.held_u[e]);
+        }
+        const uint64_t P = u.size();
+        static const uint32_t ks[4] = {1, 10, 50, 100};
+        std::vector<uint32_t> greater(P), equal(P);
+        uint64_t hits[4] = {0, 0, 0, 0};
+        f2v_pair_ranks_t info{};
+        check(f2v_pair_ranks(h, u.data(), v.data(), P, metric, F2V_NEAREST_EXCLUDE_SELF | F2V_NEAREST_EXCLUDE_NEIGHBOURS, greater.data(), equal.data(), ks, 4, hits, &info));
+        const std::string name = last_output + ".rank";
+        FILE *f = fopen(name.c_str(), "w");
+        if (!f) throw std::runtime_error("cannot write " + name);
+        for (uint64_t i = 0; i < P; i++) fprintf(f, "%u %u %u %u\n", u[i] + 1, v[i] + 1, greater[i], equal[i]);
+        if (fclose(f) != 0) throw std::runtime_error("cannot write " + name);
+        const double p = P ? (double)P : 1.0;
+        printf("Held-out ranks(%s): %llu pairs :MRR: %.17g MeanRank: %.17g Hits@1: %.17g Hits@10: %.17g Hits@50: %.17g Hits@100: %.17g\n", metric_name,
+               (unsigned long long)P, P ? info.mrr : 0.0, P ? info.mean_rank : 0.0, hits[0] / p, hits[1] / p, hits[2] / p, hits[3] / p);
+    }
+
     // writeToFile, sample/algorithms.h:118-136 (file name rule in f2v_output_name)
     void writeToFile(int option, int bs, INDEXTYPE B, INDEXTYPE IT, INDEXTYPE ns) {
         char name[4096];

@@ -25,7 +25,8 @@
 // -holdout <f> [-holdout-ratio <r>] [-holdout-metric dot|l2|cos] [-holdout-keep anchor|forest] (held-out link prediction: a share of the edges is hidden BEFORE training,
 // the run trains on the rest -- the .embd is then the training graph's embedding -- and the hidden edges are ranked against non-edges:
 // "<embd output name>.held" and ROC-AUC / average precision; with -linkpredict also by the classifier's decision values; with
-// -holdout-baselines 1 also by the five neighbourhood scores of the training graph, the yardstick).
+// -holdout-baselines 1 also by the five neighbourhood scores of the training graph, the yardstick; with -holdout-ranks <s> every hidden
+// edge -- or s of them -- is also placed among ALL vertices: "<embd output name>.rank", MRR, mean rank and Hits@K).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -61,6 +62,7 @@ struct Settings {
     double holdout = -1.0;  // not given
     long holdout_ratio = 1;
     long holdout_baselines = 0;
+    long holdout_ranks = 0;
     std::string holdout_metric;
     long classify_splits = 10, separation_sample = 0, layout = 0, layout_neighbours = 5, layout_sample = 0;
     double gamma = 1.0, lr = 0.02, classify_frac = 0.1;
@@ -159,6 +161,7 @@ int main(int argc, char *argv[]) {
         {"-holdout-ratio", Kind::Integer, &s.holdout_ratio, "<int>, 0..16: non-edges per hidden edge of a vertex in the -holdout test set. (default:1)"},
         {"-holdout-keep", Kind::Text, &s.holdout_keep, "<string>, anchor | forest: what a -holdout split never hides. anchor: every vertex's edge of lowest hash (connectivity is not promised). forest: the spanning forest of greatest hashes, found on the GPU -- the training graph keeps exactly the components of the input graph, and no rule that keeps them hides more edges. (default:anchor)"},
         {"-components", Kind::Integer, &s.components, "<int>, 1: after the run (it needs no training: -iter 0 will do) find the connected components of the run's graph on the GPU, write <output file>.cc, one line per vertex \"v label\" (0-based; the label is the smallest id of the vertex's component), and print \"Components: <c> Largest: <s> Isolated: <z>\" (one GPU). (default:0)"},
+        {"-holdout-ranks", Kind::Integer, &s.holdout_ranks, "<int>, with -holdout: the filtered rank of the hidden edges among ALL vertices, on the GPU. 0: off, -1: every hidden edge, s > 0: s of them, those of index floor(j H / s) of the H hidden edges. Each edge (u, v) is ranked from both ends by -holdout-metric, u itself and its training neighbours left out; prints \"Held-out ranks(<metric>): <P> pairs :MRR: <m> MeanRank: <r> Hits@1: <a> Hits@10: <b> Hits@50: <c> Hits@100: <d>\" (ties count half; hits as fractions of P) and writes <output file>.rank, one line \"u v greater equal\" per pair (1-based ids). (default:0)"},
         {"-holdout-metric", Kind::Text, &s.holdout_metric, "<string>, similarity that ranks the -holdout pairs: dot | l2 | cos. (default: l2 for options 1, 5, 8, 11, dot for the sigmoid options)"},
         {"-holdout-baselines", Kind::Integer, &s.holdout_baselines, "<int>, 1: with -holdout, also rank the same hidden edges and non-edges by the classic neighbourhood scores of the training graph, computed on the GPU -- common neighbours, Jaccard, Adamic-Adar, resource allocation, preferential attachment -- and print, after the embedding's line, \"Held-out baseline(<cn|jaccard|aa|ra|pa>): <H> edges :AUC: <a> AP: <p>\" for each: the yardstick the embedding's AUC and AP are read against. (default:0)"},
         {"-metric", Kind::Text, &s.metric, "<string>, similarity of -nearest: dot | l2 | cos. (default: l2 for options 5, 8, 11, dot for the sigmoid options)"},
@@ -397,6 +400,14 @@ int main(int argc, char *argv[]) {
         printf("-holdout-baselines needs -holdout (it scores the pairs that the split hides).\n");
         return 1;
     }
+    if (s.holdout_ranks < -1 || s.holdout_ranks > 0x7FFFFFFF) {
+        printf("-holdout-ranks must be -1 (every hidden edge), 0 (off) or a number of hidden edges.\n");
+        return 1;
+    }
+    if (s.holdout_ranks && !holdout) {
+        printf("-holdout-ranks needs -holdout (it ranks the edges that the split hides).\n");
+        return 1;
+    }
     if (s.components < 0 || s.components > 1) {
         printf("-components must be 0 or 1.\n");
         return 1;
@@ -470,6 +481,7 @@ int main(int argc, char *argv[]) {
             if (holdout && rank == 0)
                 algo.heldOut(split, holdout_metric, s.holdout_metric.c_str(), s.linkpredict.empty() ? -1 : linkpredict_feature, (uint32_t)s.linkpredict_ratio, (uint64_t)s.seed);
             if (holdout && s.holdout_baselines && rank == 0) algo.heldOutBaselines(split);
+            if (holdout && s.holdout_ranks && rank == 0) algo.heldOutRanks(split, holdout_metric, s.holdout_metric.c_str(), s.holdout_ranks);
             if (s.components && rank == 0) algo.writeComponents();
             if (s.communities && rank == 0)
                 algo.writeCommunities((uint32_t)s.communities_levels, (uint64_t)s.communities_seed,

@@ -44,6 +44,7 @@
 #include "f2v_linkpairs.hip.h"
 #include "f2v_heldout.hip.h"
 #include "f2v_neighbourhood.hip.h"
+#include "f2v_pairranks.hip.h"
 #include "f2v_louvain.hip.h"
 #include "f2v_components.hip.h"
 #include "f2v_tsne.hip.h"
@@ -424,6 +425,18 @@ struct f2v_ctx {
         bool spread = true;
         uint64_t last_items = 0;  // "last_neighbourhood_items": the piece items of the last call
     } nb;
+    // ranks of pairs (f2v_pair_ranks): the workspace f2v.h states, allocated on first use and grown for a larger call; "ranks_chunk":
+    // pairs per launch, "ranks_splits" (0 = from the query blocks and the tiles): candidate ranges a query block's work is cut into --
+    // placement only.  timer: [0] targets and gather, [1] the base counts, [2] the correction
+    struct Ranks {
+        DevBuf<uint32_t> d_u, d_v, d_greater, d_equal;
+        DevBuf<float> d_t, d_Q, d_rc;
+        DevBuf<PrankItem> d_item;
+        DevBuf<unsigned long long> d_excluded;
+        DevTimer timer[3];
+        uint32_t chunk = 8192, splits = 0;
+        double base_seconds = 0.0, correct_seconds = 0.0;  // "last_ranks_base_us", "last_ranks_correct_us": of the last call
+    } pr;
     // communities (f2v_louvain, f2v_partition_agreement): the workspace f2v.h states, allocated on first use and grown for a larger call;
     // "louvain_short_max": the longest row of a unit that 16 lanes gather, "louvain_lds_slots": the largest table kept in LDS --
     // placement only.  rows_symmetric: -1 not checked yet (checked once per handle, on the device)
@@ -2391,6 +2404,13 @@ const Param kParams[] = {
     // f2v_pair_neighbourhood: 1 = the pieces of a pair whose S row has several are work items of their own, 0 = one wavefront walks them; placement only
     {"neighbourhood_spread", F2V_FIELD(nb.spread), kFlag},
     {"last_neighbourhood_items", F2V_GET(nb.last_items)},
+    // f2v_pair_ranks: pairs per launch: bounds its workspace (chunk x D floats and 20 bytes a pair); results do not depend on it
+    {"ranks_chunk", F2V_FIELD(pr.chunk), kValue, kKeep, in<1, 65536>, "ranks_chunk must be 1..65536"},
+    // candidate ranges a query block's counting is cut into (0: chosen from the query blocks and the tiles); results do not depend on it
+    {"ranks_splits", F2V_FIELD(pr.splits), kValue, kKeep, in<0, 256>, "ranks_splits must be 0..256"},
+    // device time of the last f2v_pair_ranks' base-count launches and of its correction launches
+    {"last_ranks_base_us", [](const f2v_ctx *c) { return (int64_t)(c->pr.base_seconds * 1e6 + 0.5); }, nullptr},
+    {"last_ranks_correct_us", [](const f2v_ctx *c) { return (int64_t)(c->pr.correct_seconds * 1e6 + 0.5); }, nullptr},
     // f2v_louvain: a unit whose rows hold at most this many nonzeros is gathered by 16 lanes (table in LDS), a longer one by a workgroup; placement only
     {"louvain_short_max", F2V_FIELD(lv.short_max), kValue, kKeep, in<0, kLouvainShortLimit>, "louvain_short_max must be 0..256"},
     // f2v_louvain: the largest table (slots) a workgroup keeps in LDS; a longer one lies in the workspace; placement only
@@ -5268,6 +5288,158 @@ int f2v_pair_neighbourhood(f2v_handle c, const uint32_t *u_ids, const uint32_t *
         w.degrees_built = true;
     }
     if (seconds_out) *seconds_out = seconds;
+    return F2V_OK;
+}
+
+}  // extern "C"
+
+// ---- ranks of pairs (f2v_pairranks.hip.h; definition in include/f2v.h) --------------------------------------------------------------
+template <bool L2, int WQ, int MI, int NI>
+int launch_prank_t(f2v_ctx *c, const PrankArgs &a, uint32_t qblocks, uint32_t splits) {
+    const size_t lds = prank_lds_bytes(32u * WQ * MI, a.D);
+    F2VC(allow_lds(c, reinterpret_cast<const void *>(&prank_count_kernel<L2, WQ, MI, NI>), lds));
+    hipLaunchKernelGGL((prank_count_kernel<L2, WQ, MI, NI>), dim3(qblocks, splits), dim3(kNnThreads), lds, c->stream, a);
+    HIPC(hipGetLastError());
+    return F2V_OK;
+}
+
+extern "C" {
+
+int f2v_pair_ranks(f2v_handle c, const uint32_t *u_ids, const uint32_t *v_ids, uint64_t m, int metric, uint32_t flags, uint32_t *greater_out,
+                   uint32_t *equal_out, const uint32_t *ks, uint32_t nk, uint64_t *hits_out, f2v_pair_ranks_t *info) {
+    const char *who = "f2v_pair_ranks";
+    if (!c || (m && (!u_ids || !v_ids || !greater_out || !equal_out)) || (nk && (!ks || !hits_out))) return fail(F2V_EINVAL, "%s: null argument", who);
+    if (nk > F2V_RANKS_MAX_KS) return fail(F2V_EINVAL, "%s: nk = %u is above %d", who, nk, F2V_RANKS_MAX_KS);
+    for (uint32_t j = 0; j < nk; j++)
+        if (ks[j] == 0) return fail(F2V_EINVAL, "%s: ks[%u] is 0", who, j);
+    for (uint64_t i = 0; i < m; i++)
+        if (u_ids[i] >= c->n || v_ids[i] >= c->n)
+            return fail(F2V_EINVAL, "%s: pair %llu = (%u, %u) names a vertex that is not one of the %u", who, (unsigned long long)i, u_ids[i], v_ids[i], c->n);
+    if (info) *info = f2v_pair_ranks_t{};
+    for (uint32_t j = 0; j < nk; j++) hits_out[j] = 0;
+    const bool by_row = (flags & F2V_NEAREST_EXCLUDE_NEIGHBOURS) != 0;
+    const int rc = nearest_enter(c, who, m ? 1u : 0u, 1, metric, flags, by_row);  // (no k here: 1 passes its range check)
+    if (rc) return rc < 0 ? rc : F2V_OK;
+
+    f2v_ctx::Ranks &w = c->pr;
+    const char *what = "pair ranks";
+    const uint32_t n = c->n, D = c->D, tiles = (n + kNnTile - 1) / kNnTile;
+    const bool cosine = metric == F2V_SIM_COSINE;
+    const float *X = c->d_X[c->cur];
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(w.chunk, m);
+    F2VC(w.d_u.reserve(c, chunk, what));
+    F2VC(w.d_v.reserve(c, chunk, what));
+    F2VC(w.d_t.reserve(c, chunk, what));
+    F2VC(w.d_greater.reserve(c, chunk, what));
+    F2VC(w.d_equal.reserve(c, chunk, what));
+    F2VC(w.d_Q.reserve(c, (size_t)chunk * D, what));
+    F2VC(w.d_excluded.reserve(c, 1, what));
+    if (cosine) F2VC(w.d_rc.reserve(c, n, what));
+    PrankArgs a{};
+    a.X = X;
+    a.Q = w.d_Q;
+    a.rc = cosine ? (const float *)w.d_rc : nullptr;
+    a.t = w.d_t;
+    a.u = w.d_u;
+    a.v = w.d_v;
+    a.rowptr = c->d_rowptr;
+    a.colids = c->d_colids;
+    a.greater = w.d_greater;
+    a.equal = w.d_equal;
+    a.excluded = w.d_excluded;
+    a.n = n;
+    a.D = D;
+    a.flags = flags;
+    PairArgs t{};
+    t.X = X;
+    t.u = w.d_u;
+    t.v = w.d_v;
+    t.out = w.d_t;
+    t.D = D;
+    double seconds[3] = {0.0, 0.0, 0.0};
+    uint64_t excluded = 0;
+    std::vector<PrankItem> items;
+    for (uint64_t i0 = 0; i0 < m; i0 += chunk) {
+        const uint32_t cm = (uint32_t)std::min<uint64_t>(chunk, m - i0);
+        // the correction's work items: the pair itself, then -- under EXCLUDE_NEIGHBOURS -- the pieces of row u
+        items.clear();
+        for (uint32_t i = 0; i < cm; i++) {
+            items.push_back({i, kPrankPairItem});
+            const uint32_t u = u_ids[i0 + i], pieces = by_row ? (c->rowptr[u + 1] - c->rowptr[u] + kPrankPiece - 1) / kPrankPiece : 0u;
+            for (uint32_t p = 0; p < pieces; p++) items.push_back({i, p});
+        }
+        if (items.size() > 0x7FFFFFFFull) return fail(F2V_EINVAL, "%s: a chunk of %u pairs has %zu work items: lower \"ranks_chunk\"", who, cm, items.size());
+        F2VC(w.d_item.reserve(c, items.size(), what));
+        const uint32_t qb = D <= 128 && cm > 32 ? 128u : 32u, qblocks = (cm + qb - 1) / qb;
+        uint32_t splits = w.splits ? w.splits : std::min((1024u + qblocks - 1) / qblocks, 256u);  // workgroups for every CU a few times over
+        splits = std::min(splits, tiles);
+        const uint32_t tps = (tiles + splits - 1) / splits;
+        splits = (tiles + tps - 1) / tps;
+        a.nq = t.m = cm;
+        a.tiles_per_split = tps;
+        a.item = w.d_item;
+        a.items = (uint32_t)items.size();
+        HIPC(hipMemcpyAsync(w.d_u, u_ids + i0, (size_t)cm * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIPC(hipMemcpyAsync(w.d_v, v_ids + i0, (size_t)cm * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIPC(hipMemcpyAsync(w.d_item, items.data(), items.size() * sizeof(PrankItem), hipMemcpyHostToDevice, c->stream));
+        HIPC(hipMemsetAsync(w.d_greater, 0, (size_t)cm * sizeof(uint32_t), c->stream));
+        HIPC(hipMemsetAsync(w.d_equal, 0, (size_t)cm * sizeof(uint32_t), c->stream));
+        HIPC(hipMemsetAsync(w.d_excluded, 0, sizeof(unsigned long long), c->stream));
+        F2VC(w.timer[0].start(c->stream));
+        hipLaunchKernelGGL(nearest_gather_kernel, dim3(std::min<size_t>(((size_t)cm * D + 255) / 256, 4096)), dim3(256), 0, c->stream, X, (const uint32_t *)w.d_u, cm, D, w.d_Q);
+        if (cosine && i0 == 0) hipLaunchKernelGGL(nearest_rnorm_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, X, n, D, w.d_rc);
+        const dim3 tgrid((cm + 63u) / 64u);  // (a chunk has at most 65536 pairs)
+        if (metric == F2V_SIM_DOT) hipLaunchKernelGGL(pair_score_kernel<F2V_SIM_DOT>, tgrid, dim3(64), 0, c->stream, t);
+        else if (metric == F2V_SIM_L2) hipLaunchKernelGGL(pair_score_kernel<F2V_SIM_L2>, tgrid, dim3(64), 0, c->stream, t);
+        else hipLaunchKernelGGL(pair_score_kernel<F2V_SIM_COSINE>, tgrid, dim3(64), 0, c->stream, t);
+        HIPC(hipGetLastError());
+        F2VC(w.timer[0].stop(c->stream));
+        F2VC(w.timer[1].start(c->stream));
+        if (metric == F2V_SIM_L2) F2VC((qb == 128 ? launch_prank_t<true, 2, 2, 2>(c, a, qblocks, splits) : launch_prank_t<true, 1, 1, 1>(c, a, qblocks, splits)));
+        else F2VC((qb == 128 ? launch_prank_t<false, 2, 2, 2>(c, a, qblocks, splits) : launch_prank_t<false, 1, 1, 1>(c, a, qblocks, splits)));
+        F2VC(w.timer[1].stop(c->stream));
+        F2VC(w.timer[2].start(c->stream));
+        const dim3 cgrid(a.items);  // a workgroup of one wavefront per item (below 2^31: checked above)
+        if (metric == F2V_SIM_DOT) hipLaunchKernelGGL(prank_correct_kernel<F2V_SIM_DOT>, cgrid, dim3(64), 0, c->stream, a);
+        else if (metric == F2V_SIM_L2) hipLaunchKernelGGL(prank_correct_kernel<F2V_SIM_L2>, cgrid, dim3(64), 0, c->stream, a);
+        else hipLaunchKernelGGL(prank_correct_kernel<F2V_SIM_COSINE>, cgrid, dim3(64), 0, c->stream, a);
+        HIPC(hipGetLastError());
+        F2VC(w.timer[2].stop(c->stream));
+        unsigned long long ex = 0;
+        HIPC(hipMemcpyAsync(greater_out + i0, w.d_greater, (size_t)cm * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipMemcpyAsync(equal_out + i0, w.d_equal, (size_t)cm * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipMemcpyAsync(&ex, w.d_excluded, sizeof ex, hipMemcpyDeviceToHost, c->stream));
+        HIPC(hipStreamSynchronize(c->stream));
+        for (int k = 0; k < 3; k++) F2VC(w.timer[k].seconds(&seconds[k]));
+        excluded += ex;
+    }
+    F2VC(check_kernel_err(c, "pair ranks"));
+    w.base_seconds = seconds[1];
+    w.correct_seconds = seconds[2];
+
+    // the summary, from the integers: rank2 = 2 + 2 greater + equal, twice the mid-rank
+    uint64_t rank2_sum = 0, tied = 0;
+    double mrr_sum = 0.0;
+    for (uint64_t b0 = 0; b0 < m; b0 += 1024) {  // blocks of 1024 pairs, each summed from +0 in input order, then added in ascending order
+        double block = 0.0;
+        for (uint64_t i = b0; i < std::min(m, b0 + 1024); i++) {
+            const uint64_t rank2 = 2 + 2 * (uint64_t)greater_out[i] + equal_out[i];
+            rank2_sum += rank2;
+            tied += equal_out[i] ? 1u : 0u;
+            block += 2.0 / (double)rank2;
+            for (uint32_t j = 0; j < nk; j++) hits_out[j] += rank2 <= 2 * (uint64_t)ks[j] ? 1u : 0u;
+        }
+        mrr_sum += block;
+    }
+    if (info) {
+        info->seconds = seconds[0] + seconds[1] + seconds[2];
+        info->pairs = m;
+        info->rank2_sum = rank2_sum;
+        info->mean_rank = (double)rank2_sum / (2.0 * (double)m);
+        info->mrr = mrr_sum / (double)m;
+        info->candidates = m * (uint64_t)(n - 1) - excluded;
+        info->tied_pairs = tied;
+    }
     return F2V_OK;
 }
 

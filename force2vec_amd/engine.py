@@ -47,6 +47,7 @@ Forest = namedtuple("Forest", "seconds edges forest_edges components rounds roun
 Subgraph = namedtuple("Subgraph", "rowptr colids ids new_id")
 Ranking = namedtuple("Ranking", "auc ap concordant tied positives negatives groups seconds")
 HeldoutScores = namedtuple("HeldoutScores", "auc ap classifier_auc classifier_ap")
+PairRanks = namedtuple("PairRanks", "greater equal mrr mean_rank hits candidates tied_pairs seconds")
 # Engine.communities, Engine.agreement (include/f2v.h: communities)
 Communities = namedtuple("Communities", "modularity communities levels edges seconds level_records level_labels")
 LouvainLevel = namedtuple("LouvainLevel", "nodes communities sweeps moves qnum")
@@ -856,6 +857,43 @@ class Engine:
         v = np.concatenate([split.held_v, split.neg_v]).astype(np.uint32)
         y = np.concatenate([np.ones(len(split.held_u), dtype=np.uint8), np.zeros(len(split.neg_u), dtype=np.uint8)])
         return {k: self.ranking(s, y) for k, s in self.pair_neighbourhood(u, v, kinds).items()}
+
+    # -- ranks of pairs (include/f2v.h: definition; two integers per pair, a function of the matrix, the CSR, the pair, metric and flags) --
+    def pair_ranks(self, u, v, metric="dot", exclude_self=True, exclude_neighbours=True, ks=(1, 10, 50, 100)):
+        """Where v[i] stands among all vertices ordered by similarity to u[i] (metric as `nearest` defines it), with u[i] itself and
+        its neighbours in this engine's graph left out of the candidates -> PairRanks(greater uint32[m], equal uint32[m]: the
+        candidates that rank above v[i] / tie with it; mrr and mean_rank of the mid-ranks 1 + greater + equal / 2; hits: dict K ->
+        the number of pairs with mid-rank <= K; candidates: the sum of the candidate counts; tied_pairs; seconds).  Counted over all n
+        rows on the GPU: no top-k, no limit on the rank.  `last_ranks_seconds` keeps the device time."""
+        u, v = np.ascontiguousarray(u, dtype=np.uint32).reshape(-1), np.ascontiguousarray(v, dtype=np.uint32).reshape(-1)
+        if len(u) != len(v):
+            raise ValueError("pair_ranks: u and v must be two arrays of one length")
+        kk = np.ascontiguousarray(list(ks), dtype=np.uint32)
+        flags = (_lib.NEAREST_EXCLUDE_SELF if exclude_self else 0) | (_lib.NEAREST_EXCLUDE_NEIGHBOURS if exclude_neighbours else 0)
+        greater, equal = np.empty(len(u), dtype=np.uint32), np.empty(len(u), dtype=np.uint32)
+        hits, info = np.zeros(len(kk), dtype=np.uint64), _lib.PairRanksInfo()
+        self._ck(self._L.f2v_pair_ranks(self._h, _u32(u), _u32(v), len(u), METRICS[metric] if isinstance(metric, str) else int(metric), flags,
+                                        _u32(greater), _u32(equal), _u32(kk) if len(kk) else None, len(kk),
+                                        hits.ctypes.data_as(C.POINTER(C.c_uint64)) if len(kk) else None, C.byref(info)))
+        self.last_ranks_seconds = info.seconds
+        return PairRanks(greater, equal, info.mrr, info.mean_rank, {int(k): int(h) for k, h in zip(kk, hits)}, info.candidates, info.tied_pairs, info.seconds)
+
+    def heldout_ranks(self, split, metric="dot", sample=None, both_ends=True, ks=(1, 10, 50, 100)):
+        """The filtered ranks of a split's hidden edges.  Called on the engine that was built on split.rowptr / split.colids and trained
+        there: `pair_ranks` of the hidden edges with both exclusions set, so that a vertex's training edges are no rivals of its hidden
+        one -> PairRanks.  With H hidden edges and 0 < sample < H the edges ranked are those of index floor(j H / sample), j < sample
+        (no random numbers; the held list is ordered by u, so the stride spreads over the vertices).  Each chosen edge {a, b} gives the
+        pair (a, b) and, with `both_ends`, (b, a) behind it."""
+        hu, hv = np.asarray(split.held_u, dtype=np.uint32), np.asarray(split.held_v, dtype=np.uint32)
+        H = len(hu)
+        if sample is not None and 0 < int(sample) < H:
+            pick = [j * H // int(sample) for j in range(int(sample))]  # (Python integers: no overflow)
+            hu, hv = hu[pick], hv[pick]
+        if both_ends:
+            u, v = np.stack([hu, hv], axis=1).reshape(-1), np.stack([hv, hu], axis=1).reshape(-1)
+        else:
+            u, v = hu, hv
+        return self.pair_ranks(u, v, metric, True, True, ks)
 
     # -- communities (include/f2v.h: definition; a function of the CSR, seed, max_levels and max_sweeps alone) --
     def communities(self, seed=1, max_levels=32, max_sweeps=64, details=False):

@@ -11,7 +11,9 @@
  * logistic-regression scorers of node labels and links (f2v_logreg_*), the separation of a labelling in the embedding space
  * (f2v_silhouette, f2v_davies_bouldin), a two-dimensional picture of the matrix with the score of how faithful it is (f2v_pca,
  * f2v_trustworthiness), and -- the yardstick for the clusters' modularity -- the communities of the graph itself with the agreement of
- * two labellings (f2v_louvain, f2v_partition_agreement).  Each has a definition below that fixes every order of summation, so that its results are
+ * two labellings (f2v_louvain, f2v_partition_agreement); for a held-out link prediction the edge split, the scores and neighbourhood
+ * scores of pairs, their ranking, and the filtered rank of every hidden edge among all vertices (f2v_edge_split, f2v_pair_scores,
+ * f2v_pair_neighbourhood, f2v_ranking, f2v_pair_ranks).  Each has a definition below that fixes every order of summation, so that its results are
  * functions of its inputs alone.
  *
  * Conventions: every function returns 0 on success and a negative F2V_E* code on failure
@@ -1065,6 +1067,61 @@ F2V_API int f2v_ranking(f2v_handle h, const double *scores, const uint8_t *y, ui
 #define F2V_NB_ALL 31u
 F2V_API int f2v_pair_neighbourhood(f2v_handle h, const uint32_t *u_ids, const uint32_t *v_ids, uint64_t m, uint32_t kinds,
                            double *scores_out /* popcount(kinds) arrays of m, kind-major, ascending bit */, double *seconds_out /* may be NULL */);
+
+/* ---- ranks of pairs -----------------------------------------------------------------------------------------------------------------
+ * For a hidden edge (u, v): where does v stand among ALL vertices when they are ordered by similarity to u, the edges already known
+ * filtered out?  The answers over a set of pairs are the mean reciprocal rank, the mean rank and Hits@K.  The sampled negatives of
+ * f2v_edge_split are mostly easy ones; a rank of 5000 among n says what an AUC against them cannot, and a top-k stops at
+ * F2V_NEAREST_MAX_K.
+ *   scores      for pair i let u = u_ids[i], v = v_ids[i].  For every vertex w, s_w is the similarity of "nearest neighbours" with q = row
+ *               u and c = row w (the fp32 fma chain from +0 over ascending d; cosine with r = 0 for a zero row): bit-equal to
+ *               f2v_pair_scores(u, w) and to the score f2v_nearest_rows reports.  t = s_v;
+ *   order       W(s) = 0 for a NaN; otherwise, with b = bits(s + 0.0f), W = ~b where the sign bit is set, else b | 0x80000000.  w ranks
+ *               above v iff W(s_w) > W(t) and ties with v iff W(s_w) == W(t): -0 and +0 are one score, a NaN is below every number, all
+ *               NaNs tie -- the rules of f2v_nearest_* and f2v_ranking;
+ *   filter      E(u, v) is the set of DISTINCT vertices made of {u} if F2V_NEAREST_EXCLUDE_SELF is set and of N(u), the CSR row of u in
+ *               the handle's graph, if F2V_NEAREST_EXCLUDE_NEIGHBOURS is set (a duplicated nonzero counts once; a self-loop makes u a
+ *               member once); v itself is then always removed from E: the target stays a target even where it is u or a neighbour of
+ *               u in the handle's CSR.  The candidates are C = {0 .. n-1} \ E \ {v}.  On the training graph's handle with both flags
+ *               set this is the "filtered" setting of the literature.  Only the edges that the handle's CSR knows are filtered: other
+ *               hidden edges of u remain candidates;
+ *   outputs     greater_out[i] = #{w in C : w ranks above v}; equal_out[i] = #{w in C : w ties with v}; rank2_i = 2 + 2 greater + equal,
+ *               twice the mid-rank, an exact uint64 (ties count half, as in f2v_ranking); hits_out[j] = #{i : rank2_i <= 2 ks[j]}, nk <=
+ *               F2V_RANKS_MAX_KS, every ks[j] >= 1;
+ *   info        seconds (device time between events around the call's own launches), pairs = m, rank2_sum (uint64), mean_rank =
+ *               (double)rank2_sum / (2.0 m), mrr = sum / (double)m -- the terms are 2.0 / (double)rank2_i in input order, blocks of 1024
+ *               pairs are each summed sequentially from +0 and the block sums added sequentially in ascending order, on the host from
+ *               the integers --, candidates = the sum of |C| over the pairs, tied_pairs = the pairs with equal > 0.
+ * Guarantees.  The two integers of a pair are a function of (the matrix, the CSR, u, v, metric, flags) alone: never of which other pairs
+ * share the call or of their order, of "ranks_chunk" (f2v_set_param: pairs per launch, default 8192) or "ranks_splits" (candidate ranges a
+ * block of pairs is counted in, 0 = automatic .. 256), of the handle, or of the order in which workgroups or atomics land: the only
+ * atomics are integer additions.  Where equal == 0, v is not excluded by the flags and greater < k, f2v_nearest_rows(u, k, metric,
+ * flags) holds v at index `greater`.  The call works on the matrix as f2v_get_embeddings would return it (pending minibatches are
+ * committed first), on the handle's stream, and touches neither the matrices nor the rand() stream nor any later training result.  On a
+ * handle attached to a push exchange it reads this rank's replica.
+ * Launches, per chunk of pairs, all plain: the targets by the kernel of f2v_pair_scores; the base counts over all n rows by a kernel of
+ * the shape of the nearest-neighbour one (the chunk's u rows resident in LDS, candidate tiles of 128, dot and cosine on
+ * v_mfma_f32_32x32x2_f32, L2 on the vector ALU) that compares where that one selects and keeps two counters per pair, no scores and
+ * no keys; a correction, one wavefront per (pair, piece of 256 nonzeros of row u), that scores the members of E by the chain of
+ * f2v_pair_scores and subtracts those that ranked above or tied -- and v itself, which ties with itself.  "last_ranks_base_us" and
+ * "last_ranks_correct_us" read the device time of the last call's base and correction launches.
+ * Workspace of its own, allocated on first use, grown for a larger call and freed by f2v_destroy: per pair of a chunk D + 5 words, 8
+ * bytes per work item of the correction, n words of reciprocal norms for cosine.
+ * F2V_ESTATE without valid embeddings; F2V_EINVAL for null pointers, an id >= n, an unknown metric or flag bit, nk > F2V_RANKS_MAX_KS, a
+ * zero K and -- with F2V_NEAREST_EXCLUDE_NEIGHBOURS -- rows that are not ascending (checked once per handle).  m = 0 is F2V_OK and touches
+ * nothing. */
+#define F2V_RANKS_MAX_KS 16
+typedef struct {
+    double seconds;
+    uint64_t pairs;
+    uint64_t rank2_sum;
+    double mean_rank, mrr;
+    uint64_t candidates;
+    uint64_t tied_pairs;
+} f2v_pair_ranks_t;
+F2V_API int f2v_pair_ranks(f2v_handle h, const uint32_t *u_ids, const uint32_t *v_ids, uint64_t m, int metric, uint32_t flags,
+                   uint32_t *greater_out /* m */, uint32_t *equal_out /* m */, const uint32_t *ks /* nk, may be NULL with nk = 0 */, uint32_t nk,
+                   uint64_t *hits_out /* nk */, f2v_pair_ranks_t *info /* may be NULL */);
 
 /* ---- components and spanning forests ----------------------------------------------------------------------------------------------
  * What the graph is made of: its connected components, a spanning forest of them under a keyed order, a hold-out split that the forest
